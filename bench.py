@@ -9,7 +9,16 @@ step with every row also copied to pinned host memory (PCIe-inclusive, the
 reference's host-side rollout, ppo_agent.py:175-187).  `value` = env steps/s
 summed over ranks.
 
-  python bench.py --gpus N --steps K --warmup W [--workload c3|c1]
+  python bench.py --gpus N --steps K --warmup W [--workload c3|c1] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set-up, burn-in, warmup, the K
+timed steps, the --dump-outputs files, the result line.  --full adds every other leg
+(host_mirror, the rooflines and their eager event steps, C4 2-ply, C2 1-ply self-play,
+PPO iterations, the CPU baseline); their options (--horizon, --two-ply-batches,
+--c2-steps, --mirror-steps, --cpu-seconds, ...) take effect only with it.
+--dump-outputs DIR writes what the last timed step computed (its rollout row and the
+lane records after it) as DIR/<name>.npy in float32; the same arguments give the same
+inputs, so two builds can be compared array for array.
 
 Multi-GPU: one process per GPU, independent game shards (weak scaling), no
 collective on the rollout path; barrier + max-over-ranks timing.  Launched as
@@ -81,7 +90,17 @@ def parse():
                     help="C3: rollout steps per HIP graph (even: the engine's host state is a 2-step fixed point; "
                          "the timed steps replay K // G graphs, the rest run eagerly)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: host_mirror, rooflines (16 eager event steps), "
+                         "C4 2-ply, C2 1-ply self-play, PPO iterations, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's rollout row (records, action, log_prob, "
+                         "value, reward, done) and the lane records after it as DIR/<name>.npy (float32)")
+    args = ap.parse_args()
+    if not args.full:                # a plain run: the headline's timed steps only
+        args.horizon = args.two_ply_batches = args.c2_steps = args.mirror_steps = 0
+        args.no_cpu_baseline = True
+    return args
 
 
 def _free_port() -> int:
@@ -462,7 +481,7 @@ def _issued_over_algorithmic(nt: int, leaves_per_root: float, flop_per_leaf: int
         return None
 
 
-EVAL_PMC_ARGS = ("--steps 2 --warmup 1 --burn-in 150 --horizon 0 --no-cpu-baseline --two-ply-batches 1 "
+EVAL_PMC_ARGS = ("--full --steps 2 --warmup 1 --burn-in 150 --horizon 0 --no-cpu-baseline --two-ply-batches 1 "
                  "--c2-steps 0 --mirror-steps 0")
 
 
@@ -534,6 +553,101 @@ def issue_roofline(sq: dict, lanes: int, kern_ms: float, src) -> dict:
             "unit": "G wave-instructions/s", "frac": pipes[top]["frac"], "pipes": pipes,
             "wave_time_split": sq.get("wave_time_split"), "lanes_per_launch": lanes, "kernel_ms": kern_ms,
             "counters_source": src}
+
+
+def env_step_roofline(args, B: int, S: int, mean_moves: float, dev_span_ms: float, kern_ms: float, ms_step: float):
+    """The headline's `roofline` object (--full): the env step's algorithmic bytes over the
+    device-timed step window, over one shard's eager event window (kern_ms) and over
+    ms_per_step, beside the committed profile's traffic.  Returns (roofline, the profile's
+    env-step SQ block, the profile summary, whether the summary loaded)."""
+    Bs = B // S
+    # algorithmic bytes per lane-step of the env-step kernel (DESIGN.md §Roofline):
+    # record in+out 128, action 4, chosen move 8, new move list 8*n, reward 4, done 1, rng ctr 8+8
+    bytes_per_lane = 128 + 4 + 8 + 8 * mean_moves + 4 + 1 + 16
+    achieved = Bs * bytes_per_lane / (kern_ms * 1e-3) / 1e9    # one shard's env step per window
+    # HBM bytes per env step of one shard (all kernels bgx_step launches: both k_step
+    # launches, the order sort, the overflow tiers) from the committed rocprofv3 PMC
+    # passes (tools/profile.sh -> profiles/latest_summary.json; (FETCH_SIZE + WRITE_SIZE)
+    # x 1024: the step's 64-B record / 4-8-B scalar reads are single 64-B requests that
+    # FETCH_SIZE counts exactly, calibrated in profiles/r2_fetch_calibration.json)
+    traffic, traffic_src, prof_kernels, sq, summ, prof_ok = None, None, None, None, None, False
+    prof = os.path.join(ROOT, "profiles", "latest_summary.json")
+    if os.path.exists(prof):
+        try:
+            summ = json.load(open(prof))
+            prof_ok = True
+            env = summ.get("env_step")
+            if env and env["hbm_bytes_per_step"] > 0:
+                traffic, traffic_src = env["hbm_bytes_per_step"], summ.get("command")
+                prof_kernels = {k["name"]: round(k["avg_ns"] / 1e3, 1) for k in env["kernels"]}
+            sq = (env or {}).get("sq")
+        except Exception:
+            traffic = None
+    roofline = {"kernel": "env step = k_step<0,9,0,false,1> (predicted-doubles prefix) then "
+                          "k_step<0,8,0,true,1> (the rest) + k_order_count/scatter + k_movegen_over tiers, "
+                          "one wave per game, "
+                          + ("the light launch on the engine's side stream (event fork-join)" if args.fork_steps
+                             else "both launches on the shard's stream")
+                          + f"; {S} shards' steps overlap on {S} streams",
+                "bound": "hbm", "achieved": B * bytes_per_lane / (dev_span_ms / args.steps * 1e-3) / 1e9,
+                "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": B * bytes_per_lane / (dev_span_ms / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "window": "the timed region on the device clock (HIP events on every shard's stream before the "
+                          "first and after the last timed step) / steps: the shards' env-step launches overlap "
+                          "each other and the policy kernels, so the step window is the launches' union",
+                "window_ms": dev_span_ms / args.steps, "algorithmic_bytes_per_step": B * bytes_per_lane,
+                "traffic": traffic * S if traffic else None,
+                "traffic_unit": f"bytes per env step of all {S} shards (PMC, profiles/latest_summary.json)",
+                "traffic_per_lane_step": traffic / Bs if traffic else None,
+                "traffic_over_algorithmic": traffic / (Bs * bytes_per_lane) if traffic else None,
+                "traffic_source": traffic_src, "lanes_per_step": B, "bytes_per_lane_step": bytes_per_lane,
+                "mean_legal_moves": mean_moves,
+                "per_shard_eager": {"achieved": achieved, "frac": achieved / HBM_PEAK_GBS, "kernel_ms": kern_ms,
+                                    "lanes_per_launch": Bs, "algorithmic_bytes_per_step": Bs * bytes_per_lane,
+                                    "note": "one shard's env-step bytes / HIP events around its bgx_step in 16 "
+                                            "eager steps right after the timed region, the other shards' "
+                                            "kernels sharing the GPU"},
+                "rocprof_avg_us": prof_kernels,
+                "rocprof_note": "per-launch averages of the C3 step's kernels from the committed kernel trace "
+                                "(profiles/latest_summary.json env_step); under 4-shard overlap a launch's "
+                                "duration includes the time it shares the CUs with the other shards"}
+    # the same bytes chip-wide: every shard's env-step bytes over the whole step window
+    # (ms_per_step), while the per-shard figure above divides one shard's bytes by one
+    # shard's event window with the other shards' kernels sharing the GPU
+    chip = B * bytes_per_lane / (ms_step * 1e-3) / 1e9
+    roofline["chip_wide_wall"] = {"achieved": chip, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                  "frac": chip / HBM_PEAK_GBS, "window_ms": ms_step,
+                                  "note": "all shards' algorithmic env-step bytes / ms_per_step (host clock)"}
+    return roofline, sq, summ, prof_ok
+
+
+DUMP_LIMIT_BYTES = 64_000_000       # of all the files of one dump, .npy headers included
+
+
+def dump_outputs(path: str, arrays: dict, rank: int, ws: int) -> dict:
+    """--dump-outputs: each tensor of `arrays` ([lanes, ...], every rank's own lanes) as
+    path/<name>.npy in float32 (the rollout's bytes, int32 actions and fp32 values are all
+    exact in it).  Over DUMP_LIMIT_BYTES in all, the same fixed seeded sample of lanes of
+    every array is written instead, with the lanes' indices as lanes.npy (float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(4 * (a.numel() // n) for a in arrays.values())
+    idx = None
+    if n * row_bytes > DUMP_LIMIT_BYTES - 4096:
+        keep = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+    sfx = f".rank{rank}" if ws > 1 else ""
+    shapes = {}
+    for name, a in arrays.items():
+        h = a.detach().to("cpu").numpy()
+        h = np.ascontiguousarray((h if idx is None else h[idx]).astype(np.float32))
+        np.save(os.path.join(path, name + sfx + ".npy"), h)
+        shapes[name] = list(h.shape)
+    if idx is not None:
+        np.save(os.path.join(path, "lanes" + sfx + ".npy"), idx.astype(np.float64))
+        shapes["lanes"] = [len(idx)]
+    return shapes
 
 
 def main():
@@ -637,7 +751,7 @@ def main():
     nm_sum, nm_n = 0.0, 0
     for w in range(args.warmup):
         step(False)
-        if w >= args.warmup // 2:
+        if args.full and w >= args.warmup // 2:
             sync_all()
             nm_sum += sum(float(e.n_moves(out=counts[k]).float().mean().item()) for k, e in enumerate(engs)) / S
             nm_n += 1
@@ -709,7 +823,25 @@ def main():
     el_rank = time.perf_counter() - t0
     # device span of the timed region: first shard start to last shard end
     dev_span_ms = max(tev[0][0].elapsed_time(tev[k][1]) for k in range(S))
-    if graphs:
+    dumped = None
+    if args.dump_outputs:
+        # the last timed step's rollout row: the slot of the last replayed graph's last
+        # step, or of the last eager step (the remainder after the replays, or --no-graphs)
+        slot = None
+        if graphs and args.steps % G == 0:
+            if args.steps:
+                slot = (args.steps // G - 1) % len(graphs) * G + G - 1
+        elif args.steps:
+            slot = (state["i"] - 1) % ring
+        outs = {}
+        if slot is not None and args.workload == "c3":
+            for name, field in (("records", "records"), ("action", "act"), ("log_prob", "logp"), ("value", "value"),
+                                ("reward", "reward"), ("done", "done")):
+                outs[name] = torch.cat([bufs[k][field][slot] for k in range(S)])
+        outs["next_records"] = torch.cat([engs[k].records() for k in range(S)])
+        torch.cuda.synchronize(dev)
+        dumped = dump_outputs(args.dump_outputs, outs, rank, ws)
+    if graphs and args.full:
         # the roofline's kernel time: HIP events around bgx_step in eager steps right
         # after the timed replays (events cannot be timed inside a graph)
         for _ in range(16):
@@ -719,29 +851,7 @@ def main():
     per_rank = gather_ranks([float(B * args.steps), el_rank], ws)
     total_steps = sum(r[0] for r in per_rank)
     value = total_steps / el
-    kern_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / len(ev_pairs)
-    # algorithmic bytes per lane-step of the env-step kernel:
-    # record in+out 128, action 4, chosen move 8, new move list 8*n, reward 4, done 1, rng ctr 8+8
-    bytes_per_lane = 128 + 4 + 8 + 8 * mean_moves + 4 + 1 + 16
-    achieved = Bs * bytes_per_lane / (kern_ms * 1e-3) / 1e9    # one shard's env step per window
-    # HBM bytes per env step of one shard (all kernels bgx_step launches: both k_step
-    # launches, the order sort, the overflow tiers) from the committed rocprofv3 PMC
-    # passes (tools/profile.sh -> profiles/latest_summary.json; (FETCH_SIZE + WRITE_SIZE)
-    # x 1024: the step's 64-B record / 4-8-B scalar reads are single 64-B requests that
-    # FETCH_SIZE counts exactly, calibrated in profiles/r2_fetch_calibration.json)
-    traffic, traffic_src, prof_kernels, sq, summ, prof_ok = None, None, None, None, None, False
-    prof = os.path.join(ROOT, "profiles", "latest_summary.json")
-    if os.path.exists(prof):
-        try:
-            summ = json.load(open(prof))
-            prof_ok = True
-            env = summ.get("env_step")
-            if env and env["hbm_bytes_per_step"] > 0:
-                traffic, traffic_src = env["hbm_bytes_per_step"], summ.get("command")
-                prof_kernels = {k["name"]: round(k["avg_ns"] / 1e3, 1) for k in env["kernels"]}
-            sq = (env or {}).get("sq")
-        except Exception:
-            traffic = None
+    ms_step = el * 1e3 / args.steps
     line = {
         "metric": "self-play env steps/sec (whole node) + 2-ply evals/sec at batch=65536",
         "value": value,
@@ -749,7 +859,7 @@ def main():
         "n_gpus": ws,
         "steps": args.steps,
         "warmup": args.warmup,
-        "ms_per_step": el * 1e3 / args.steps,
+        "ms_per_step": ms_step,
         "higher_is_better": True,
         "scaling": "weak",
         "vs_baseline": None,
@@ -766,47 +876,17 @@ def main():
                    "streams_per_gpu": S, "step_fork": bool(args.fork_steps),
                    "hip_graph": ({"steps_per_graph": G, "replays": args.steps // G, "eager_steps": args.steps % G}
                                  if graphs else None)},
-        "roofline": {"kernel": "env step = k_step<0,9,0,false,1> (predicted-doubles prefix) then "
-                               "k_step<0,8,0,true,1> (the rest) + k_order_count/scatter + k_movegen_over tiers, "
-                               "one wave per game, "
-                               + ("the light launch on the engine's side stream (event fork-join)" if args.fork_steps
-                                  else "both launches on the shard's stream")
-                               + f"; {S} shards' steps overlap on {S} streams",
-                     "bound": "hbm", "achieved": B * bytes_per_lane / (dev_span_ms / args.steps * 1e-3) / 1e9,
-                     "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": B * bytes_per_lane / (dev_span_ms / args.steps * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "window": "the timed region on the device clock (HIP events on every shard's stream before the "
-                               "first and after the last timed step) / steps: the shards' env-step launches overlap "
-                               "each other and the policy kernels, so the step window is the launches' union",
-                     "window_ms": dev_span_ms / args.steps, "algorithmic_bytes_per_step": B * bytes_per_lane,
-                     "traffic": traffic * S if traffic else None,
-                     "traffic_unit": f"bytes per env step of all {S} shards (PMC, profiles/latest_summary.json)",
-                     "traffic_per_lane_step": traffic / Bs if traffic else None,
-                     "traffic_over_algorithmic": traffic / (Bs * bytes_per_lane) if traffic else None,
-                     "traffic_source": traffic_src, "lanes_per_step": B, "bytes_per_lane_step": bytes_per_lane,
-                     "mean_legal_moves": mean_moves,
-                     "per_shard_eager": {"achieved": achieved, "frac": achieved / HBM_PEAK_GBS, "kernel_ms": kern_ms,
-                                         "lanes_per_launch": Bs, "algorithmic_bytes_per_step": Bs * bytes_per_lane,
-                                         "note": "one shard's env-step bytes / HIP events around its bgx_step in 16 "
-                                                 "eager steps right after the timed region, the other shards' "
-                                                 "kernels sharing the GPU"},
-                     "rocprof_avg_us": prof_kernels,
-                     "rocprof_note": "per-launch averages of the C3 step's kernels from the committed kernel trace "
-                                     "(profiles/latest_summary.json env_step); under 4-shard overlap a launch's "
-                                     "duration includes the time it shares the CUs with the other shards"},
     }
-    # the same bytes chip-wide: every shard's env-step bytes over the whole step window
-    # (ms_per_step), while the per-shard figure above divides one shard's bytes by one
-    # shard's event window with the other shards' kernels sharing the GPU
-    ms_step = el * 1e3 / args.steps
-    chip = B * bytes_per_lane / (ms_step * 1e-3) / 1e9
-    line["roofline"]["chip_wide_wall"] = {"achieved": chip, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                          "frac": chip / HBM_PEAK_GBS, "window_ms": ms_step,
-                                          "note": "all shards' algorithmic env-step bytes / ms_per_step (host clock)"}
+    kern_ms, sq, summ, prof_ok = None, None, None, False
+    if args.full:
+        kern_ms = sum(a.elapsed_time(b) for a, b in ev_pairs) / len(ev_pairs)
+        line["roofline"], sq, summ, prof_ok = env_step_roofline(args, B, S, mean_moves, dev_span_ms, kern_ms, ms_step)
     line["host_enqueue_ms"] = t_enq * 1e3
     line["per_rank"] = [{"rank": k, "env_steps": r[0], "seconds": r[1]} for k, r in enumerate(per_rank)]
     if backend is not None:
         line["dist_backend"] = backend
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
     if args.mirror_steps > 0 and not args.host_mirror and args.workload == "c3":
         # north_star's "rollout into pinned host buffers": the same C3 step with every
         # rollout row also copied to pinned host memory.  Graph form (default): each
@@ -884,7 +964,7 @@ def main():
             mirror.update(eager)
             mirror["form"] = "eager launches, one copy launch (6 fields) per step and shard"
         line["host_mirror"] = mirror
-    if pol_pairs:
+    if args.full and pol_pairs:
         line["roofline_policy"] = policy_roofline(pol_pairs, Bs, (summ or {}).get("policy") if prof_ok else None,
                                                   (summ or {}).get("pmc_command") if prof_ok else None)
     if sq and sq.get("instructions_per_lane_step") and args.workload == "c3":

@@ -33,7 +33,7 @@ def _bench(extra, env_extra, timeout=300):
 
 
 def test_bench_one_rank_rccl_with_graphs():
-    r = _bench(["--two-ply-batches", "1", "--c2-steps", "4", "--horizon", "4", "--mirror-steps", "4"],
+    r = _bench(["--full", "--two-ply-batches", "1", "--c2-steps", "4", "--horizon", "4", "--mirror-steps", "4"],
                {"BGX_DIST_FORCE": "1", "BGX_DIST_BACKEND": "nccl"})
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -50,7 +50,7 @@ def test_bench_one_rank_rccl_with_graphs():
 
 @pytest.mark.parametrize("site,extra", [
     ("c3", ["--two-ply-batches", "0", "--c2-steps", "0", "--horizon", "0", "--mirror-steps", "0"]),
-    ("trainer", ["--no-graphs", "--two-ply-batches", "0", "--c2-steps", "0", "--horizon", "4", "--mirror-steps", "0"]),
+    ("trainer", ["--full", "--no-graphs", "--two-ply-batches", "0", "--c2-steps", "0", "--horizon", "4", "--mirror-steps", "0"]),
 ])
 def test_capture_failure_is_terminal(site, extra):
     r = _bench(extra, {"BGX_INJECT_CAPTURE_FAILURE": site}, timeout=240)

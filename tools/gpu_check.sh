@@ -11,7 +11,7 @@ tail -3 $O/tests.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc         # 1 = test failures (keep going), else a crash / time limit
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 300 python bench.py > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
+timeout -k 10 300 python bench.py --full > $O/bench.log 2>&1 || { tail -5 $O/bench.log; exit 1; }
 python - $O/bench.log <<'PY'
 import json, sys
 l = json.loads([x for x in open(sys.argv[1]).read().splitlines() if x.startswith("{")][-1])
