@@ -299,7 +299,9 @@ int bgx_ppo_head_ex(const void* logits_dev, int32_t dtype, int64_t ld_logits, co
  * gradient where relu's output > 0) in place on dh [n][hidden] fp16, given the
  * stored activations h [n][hidden] fp16 (16-byte aligned, hidden % 8 == 0,
  * hidden <= 256), with the bias gradient's partial column sums of the masked dh
- * in colsum[blocks][hidden] (fp32; the caller sums the rows). */
+ * in colsum[blocks][hidden] (fp32; the caller sums the rows).  The grid is `blocks`
+ * workgroups and every one writes its whole colsum row: a block that had no row of
+ * dh to walk (n small next to blocks) writes zeros, so colsum needs no clearing. */
 int bgx_relu_backward(void* dh, const void* h, int32_t n, int32_t hidden, float* colsum, int32_t blocks,
                       void* stream);
 
