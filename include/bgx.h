@@ -265,6 +265,66 @@ int bgx_one_ply(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float v
 int bgx_two_ply(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float value_bias, int32_t* best_out,
                 float* bestq_out, float* q_out, uint64_t* stats_host, void* stream);
 
+/* bgx_one_ply / bgx_two_ply for the lanes with lane_sel_dev[i] != 0 only (uint8[B] on the
+ * device; NULL = every lane, which is exactly bgx_one_ply / bgx_two_ply).  An unselected
+ * lane forms no rows (no afterstates, jobs or leaves: the work is that of the selected
+ * lanes alone), its entries of best_out, bestv_out / bestq_out and values_out / q_out are
+ * not written, stats_host counts the selected lanes only, and it is never reported as
+ * changed (BGX_ESTATE / error bit 1).  Selected lanes get bit for bit what the unselected
+ * call gives them.  An all-zero selection is legal: BGX_OK, nothing written, zero stats.
+ * (The reference has one player act for every env, ppo_agent.py:138-191; a match between
+ * two players needs each to act only where it is on move: bgx_arena_*.) */
+int bgx_one_ply_sel(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float value_bias,
+                    const uint8_t* lane_sel_dev, int32_t* best_out, float* bestv_out, float* values_out,
+                    void* stream);
+int bgx_two_ply_sel(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float value_bias,
+                    const uint8_t* lane_sel_dev, int32_t* best_out, float* bestq_out, float* q_out,
+                    uint64_t* stats_host, void* stream);
+
+/* ---- head-to-head arena (csrc/bg_engine.hip; bgx/arena.py) ----
+ * Two players A and B play each other on the n lanes of an engine created with
+ * auto_reset = 1 until every lane has finished games_per_lane games (the reference has no
+ * evaluation match; its train.py:55-99 logs self-play statistics only).  The caller owns
+ * the state, plain device arrays: games_done int32[n], sel_a / sel_b uint8[n] (the lanes
+ * where A / B is on move now: the lane selection of bgx_one_ply_sel / bgx_two_ply_sel) and
+ * tally int64[16] (indices below).  Seat rule: in game g of lane i, A is PLAYER1 iff
+ * ((i + g) & 1) == 0.  A lane is active while games_done[i] < games_per_lane; afterwards it
+ * belongs to neither player, is given action 0 and is not counted.  records_dev = the
+ * engine's lane records (bgx_buffers.lanes), read in place on the caller's stream.  No
+ * entry point synchronises or allocates: all three can be captured into a HIP graph.
+ * bgx_arena_begin: games_done = 0, tally = 0, sel_a / sel_b from the lanes' movers,
+ * tally[BGX_ARENA_ACTIVE] = number of active lanes.
+ * bgx_arena_merge: actions[i] = sel_a[i] ? act_a[i] : sel_b[i] ? act_b[i] : 0.
+ * bgx_arena_advance: after bgx_step, with that step's done and info.  Every lane that was
+ * active in the step adds a ply; a done with a winner adds the game to the tally (winner
+ * and game_score from info) and to games_done; sel_a / sel_b are set for the new position;
+ * tally[BGX_ARENA_ACTIVE] drops by the lanes that finished their last game. */
+enum bgx_arena_field {
+    BGX_ARENA_GAMES = 0,          /* finished games */
+    BGX_ARENA_WINS_A = 1,         BGX_ARENA_WINS_B = 2,
+    BGX_ARENA_POINTS_A = 3,       BGX_ARENA_POINTS_B = 4,        /* 1 / 2 / 3 per game won */
+    BGX_ARENA_GAMMONS_A = 5,      BGX_ARENA_GAMMONS_B = 6,
+    BGX_ARENA_BACKGAMMONS_A = 7,  BGX_ARENA_BACKGAMMONS_B = 8,
+    BGX_ARENA_GAMES_A_P1 = 9,     /* finished games in which A sat as PLAYER1 */
+    BGX_ARENA_WINS_A_P1 = 10,     /* A's wins in those games */
+    BGX_ARENA_WINS_P1 = 11,       /* wins by the PLAYER1 seat, whoever held it */
+    BGX_ARENA_PLIES = 12,         /* steps of active lanes, passes included */
+    BGX_ARENA_ACTIVE = 13         /* active lanes remaining; 14, 15 stay zero */
+};
+int bgx_arena_begin(const uint8_t* records_dev, int32_t n, int32_t games_per_lane, int32_t* games_done_dev,
+                    uint8_t* sel_a_dev, uint8_t* sel_b_dev, int64_t* tally_dev, void* stream);
+int bgx_arena_merge(const uint8_t* sel_a_dev, const uint8_t* sel_b_dev, const int32_t* act_a_dev,
+                    const int32_t* act_b_dev, int32_t n, int32_t* actions_dev, void* stream);
+int bgx_arena_advance(const uint8_t* records_dev, const uint8_t* done_dev, const int32_t* info_dev, int32_t n,
+                      int32_t games_per_lane, int32_t* games_done_dev, uint8_t* sel_a_dev, uint8_t* sel_b_dev,
+                      int64_t* tally_dev, void* stream);
+/* A uniformly random legal action per lane record (the arena's baseline opponent; the
+ * reference has no counterpart): act_out[i] =
+ * floor(u * count_i), u in [0, 1) hashed from (seed, step, i), count_i = the record's legal
+ * count (bytes 60-61); 0 when the lane has no legal move.  Graph-capturable. */
+int bgx_random_act(const uint8_t* records_dev, int32_t n, uint64_t seed, uint32_t step, int32_t* act_out,
+                   void* stream);
+
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row
  * stride ld_logits; mask from the legal count in bytes 60-61 of each 64-byte
@@ -470,7 +530,9 @@ int bgx_two_ply_timings(bgx_engine* e, float* ms2);
  * evaluator), BGX_2PLY_BARROW 0 (bar rows per job), BGX_2PLY_DUMP path (pool, row sides,
  * V per slot), BGX_2PLY_DEBUG (round sizes on stderr), BGX_POLICY_SKIP 0 (no tile skip),
  * BGX_POLICY_HEAVY n (the policy's heavy-row bound); read at engine creation: BGX_XCD 0,
- * BGX_ORDER 0 (lane-order dispatch), BGX_STAMPS, BGX_STEP_DEBUG.  Every alternative is
+ * BGX_ORDER 0 (lane-order dispatch), BGX_STAMPS, BGX_STEP_DEBUG, BGX_TIER1_CAP n and
+ * BGX_MOVEGEN_CAP n (the unique-afterstate caps of the step's first overflow tier and of
+ * bgx_movegen's main table, clamped to [1, the table's own cap]).  Every alternative is
  * exact: results are identical, only the schedule or the diagnostics change. */
 int bgx_debug_option(const char* name, const char* value_or_null);
 

@@ -31,6 +31,8 @@ flat step-major memory in which the environments are interleaved
 
     python -m bgx.train --batch 65536 --horizon 64 --updates 10 [--metrics m.jsonl]
     torchrun --nproc-per-node 8 -m bgx.train ...            (one process per GPU)
+    python -m bgx.train ... --eval-every 5 --eval-opponent random   (a head-to-head match of
+        the current weights after every 5th update, bgx.arena; one rank only)
 """
 from __future__ import annotations
 
@@ -1220,6 +1222,30 @@ class PPOTrainer:
     def save(self, path: str):
         torch.save(self.net.state_dict(), path)
 
+    def evaluate(self, opponent="random", player: str = "policy", batch: int = 4096, games_per_lane: int = 2,
+                 max_steps: int = 4000, opponent_player: str = "policy"):
+        """The current weights as player A of a head-to-head match (bgx.arena) against
+        `opponent`: "random", a PolicyNet or the path of a saved state_dict (playing as
+        `opponent_player`).  `player`: how A decides ("policy" sample, "greedy" argmax,
+        "1ply", "2ply").  Returns the arena's result dict.  Training is not disturbed: the
+        match runs on an engine and seeds of its own (the k-th evaluation of a trainer is
+        seeded from (seed, k)), the players pack the weights into buffers of their own, and
+        neither the trainer's engines, step counter, packed weights or captured graphs nor
+        torch's global generator are touched."""
+        if self.group is not None or _world(self.group) > 1:
+            raise NotImplementedError("PPOTrainer.evaluate runs on one rank only: multi-rank evaluation is not "
+                                      "implemented (evaluate a saved checkpoint with python -m bgx.arena)")
+        from . import arena as AR
+        k = getattr(self, "_evals_done", 0)
+        self._evals_done = k + 1
+        base = (self.seed * 1_000_003 + 15_485_863 * (k + 1)) & (2**63 - 1)
+        if isinstance(opponent, str) and opponent != "random":
+            opponent = AR.load_net(opponent, self.dev)
+        a = AR.make_player(player, self.net, seed=base + 1)
+        b = AR.make_player(opponent_player, opponent, seed=base + 2)
+        ar = AR.Arena(batch, games_per_lane, seed=base, dice="philox", max_moves=self.A, device=self.dev)
+        return ar.play(a, b, max_steps=max_steps)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -1232,8 +1258,17 @@ def main():
     ap.add_argument("--save", default=None)
     ap.add_argument("--returns", default="lane", choices=["lane", "reference"])
     ap.add_argument("--entropy-anneal", default="train", choices=["train", "train_single"])
+    # periodic head-to-head evaluation of the current weights (PPOTrainer.evaluate, bgx.arena)
+    ap.add_argument("--eval-every", type=int, default=0, help="evaluate after every N-th update (0: never)")
+    ap.add_argument("--eval-games", type=int, default=2, help="games per lane of an evaluation")
+    ap.add_argument("--eval-batch", type=int, default=4096)
+    ap.add_argument("--eval-max-steps", type=int, default=4000)
+    ap.add_argument("--eval-opponent", default="random", help="'random' or a saved state_dict")
+    ap.add_argument("--eval-player", default="policy", choices=["policy", "greedy", "1ply", "2ply"])
     args = ap.parse_args()
     ws = int(os.environ.get("WORLD_SIZE", "1"))
+    if ws > 1 and args.eval_every > 0:
+        ap.error("--eval-every needs a single rank (multi-rank evaluation is not implemented)")
     local = int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1)
     torch.cuda.set_device(local)
     if ws > 1:
@@ -1247,6 +1282,11 @@ def main():
     for u in range(args.updates):
         m = tr.iteration()
         m["update"] = u
+        if args.eval_every > 0 and (u + 1) % args.eval_every == 0:
+            ev = tr.evaluate(args.eval_opponent, player=args.eval_player, batch=args.eval_batch,
+                             games_per_lane=args.eval_games, max_steps=args.eval_max_steps)
+            m.update({"eval_win_rate": ev["win_rate_a"], "eval_ppg": ev["ppg_a"], "eval_games": ev["games"],
+                      "eval_unfinished": ev["unfinished_lanes"]})
         if tr.rank == 0:
             print(json.dumps(m), flush=True)
             if args.metrics:

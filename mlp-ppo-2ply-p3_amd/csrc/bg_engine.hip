@@ -485,6 +485,117 @@ __global__ __launch_bounds__(256) void k_copy_regions(CopyRegions R) {
     }
 }
 
+// ---- head-to-head arena (bgx/arena.py drives it) ----
+// Bookkeeping of a match between two players A and B on the engine's lanes: each has its
+// own weights and decision rule, every lane plays exactly G games, and the whole
+// accounting stays on the device in arrays the caller owns:
+//   games_done int32[B]   finished, counted games of the lane (active while < G)
+//   sel_a, sel_b uint8[B] the lanes on which A / B is on move in the current position
+//                         (the lane selection of bgx_one_ply_sel / bgx_two_ply_sel)
+//   tally int64[16]       the result (BGX_ARENA_* indices, bgx.h)
+// Seat rule: in game g of lane i, A sits as PLAYER1 (mover 0) iff ((i + g) & 1) == 0, so
+// with B even A holds each seat in exactly half of all games.  A lane that has finished
+// its G games keeps stepping (the engine steps every lane) with action 0, belongs to
+// neither player and is not counted: counting exactly G games per lane keeps the result
+// unbiased, where a fixed step budget would over-represent short games.
+// The tally fields are integer sums, so the order of the additions does not matter: each
+// wave counts its lanes with ballots and adds once per field (64-bit atomic add).
+__device__ __forceinline__ void tally_add(int64_t* tally, int field, long long v) {
+    if (v != 0 && lane_id() == 0) atomicAdd((unsigned long long*)tally + field, (unsigned long long)v);
+}
+__device__ __forceinline__ long long count(bool p) { return (long long)__popcll(__ballot(p)); }
+
+// sel_a / sel_b of lane i for its current position: the mover's seat in the lane's game g
+__device__ __forceinline__ void select_lane(const uint8_t* recs, int i, int g, bool active, uint8_t* sel_a,
+                                            uint8_t* sel_b) {
+    const int mover = recs[(size_t)i * 64 + R_CUR] & 1;
+    const bool a_p1 = ((i + g) & 1) == 0;
+    const bool a_moves = (mover == 0) == a_p1;
+    sel_a[i] = (uint8_t)(active && a_moves);
+    sel_b[i] = (uint8_t)(active && !a_moves);
+}
+
+// tally is zero already (the entry point's memset, ordered before this kernel)
+__global__ __launch_bounds__(256) void k_arena_begin(const uint8_t* recs, int n, int G, int32_t* games_done,
+                                                     uint8_t* sel_a, uint8_t* sel_b, int64_t* tally) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < n, active = in && G > 0;
+    if (in) {
+        games_done[i] = 0;
+        select_lane(recs, i, 0, active, sel_a, sel_b);
+    }
+    tally_add(tally, BGX_ARENA_ACTIVE, count(active));
+}
+
+__global__ __launch_bounds__(256) void k_arena_merge(const uint8_t* sel_a, const uint8_t* sel_b, const int32_t* act_a,
+                                                     const int32_t* act_b, int n, int32_t* actions) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < n) actions[i] = sel_a[i] ? act_a[i] : (sel_b[i] ? act_b[i] : 0);
+}
+
+// After bgx_step, with that step's done / info.  The engine runs with auto_reset = 1: a
+// lane never sits in a finished game when a step begins, so done == 1 is always a win by
+// the mover of that step (info's winner field == its mover field, kind 0: apply_lane) and
+// the record read here is already the first position of the lane's next game.  A pass
+// (kind 1) or a refused action (kind 2) is a ply without a result; a done without a winner
+// (kind 3, the auto_reset = 0 engine's reset step) would be no result either.
+__global__ __launch_bounds__(256) void k_arena_advance(const uint8_t* recs, const uint8_t* done, const int32_t* info,
+                                                       int n, int G, int32_t* games_done, uint8_t* sel_a,
+                                                       uint8_t* sel_b, int64_t* tally) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < n;
+    int g = in ? games_done[i] : G;
+    const bool active = in && g < G;
+    const int inf = active ? info[i] : 0;
+    const int winner = ((inf >> 8) & 0xFF) - 1, score = (inf >> 16) & 0xFF;
+    const bool fin = active && done[i] != 0 && winner >= 0;
+    const bool a_p1 = ((i + g) & 1) == 0;
+    const bool a_won = fin && ((winner == 0) == a_p1), b_won = fin && !a_won;
+    bool retired = false;
+    if (active) {
+        if (fin) {
+            games_done[i] = ++g;
+            retired = g >= G;
+        }
+        select_lane(recs, i, g, !retired, sel_a, sel_b);
+    }
+    // every thread of the wave reaches the ballots (no early return above)
+    tally_add(tally, BGX_ARENA_GAMES, count(fin));
+    tally_add(tally, BGX_ARENA_WINS_A, count(a_won));
+    tally_add(tally, BGX_ARENA_WINS_B, count(b_won));
+    tally_add(tally, BGX_ARENA_POINTS_A, count(a_won && score == 1) + 2 * count(a_won && score == 2) +
+                                             3 * count(a_won && score == 3));
+    tally_add(tally, BGX_ARENA_POINTS_B, count(b_won && score == 1) + 2 * count(b_won && score == 2) +
+                                             3 * count(b_won && score == 3));
+    tally_add(tally, BGX_ARENA_GAMMONS_A, count(a_won && score == 2));
+    tally_add(tally, BGX_ARENA_GAMMONS_B, count(b_won && score == 2));
+    tally_add(tally, BGX_ARENA_BACKGAMMONS_A, count(a_won && score == 3));
+    tally_add(tally, BGX_ARENA_BACKGAMMONS_B, count(b_won && score == 3));
+    tally_add(tally, BGX_ARENA_GAMES_A_P1, count(fin && a_p1));
+    tally_add(tally, BGX_ARENA_WINS_A_P1, count(a_won && a_p1));
+    tally_add(tally, BGX_ARENA_WINS_P1, count(fin && winner == 0));
+    tally_add(tally, BGX_ARENA_PLIES, count(active));
+    tally_add(tally, BGX_ARENA_ACTIVE, -count(retired));
+}
+
+// murmur3's 64-bit finalizer
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
+    x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull;
+    x ^= x >> 33;
+    return x;
+}
+
+// a uniformly random legal action per record: floor(u * count), u in [0, 1) from (seed, step, i)
+__global__ __launch_bounds__(256) void k_random_act(const uint8_t* recs, int n, uint64_t seed, uint32_t step,
+                                                    int32_t* act) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t cnt = (uint32_t)recs[(size_t)i * 64 + R_NM0] | ((uint32_t)recs[(size_t)i * 64 + R_NM1] << 8);
+    const uint64_t h = mix64(mix64(seed ^ 0x9E3779B97F4A7C15ull) + (((uint64_t)step << 32) | (uint32_t)i));
+    act[i] = (int32_t)(((h >> 32) * (uint64_t)cnt) >> 32);      // 0 when the lane has no legal move
+}
+
 thread_local std::string g_err;
 
 int fail(hipError_t e, int code = BGX_EDEVICE) {
@@ -1021,6 +1132,48 @@ int bgx_copy_regions(const bgx_region* regions, int32_t n, int32_t workgroups, v
     const int64_t need = (acc + 255) / 256;
     const int wg = (int)(workgroups > 0 && workgroups < need ? workgroups : (need < 64 ? need : 64));
     hipLaunchKernelGGL(k_copy_regions, dim3(wg), dim3(256), 0, (hipStream_t)stream, R);
+    CKL();
+    return BGX_OK;
+}
+
+int bgx_arena_begin(const uint8_t* records_dev, int32_t n, int32_t games_per_lane, int32_t* games_done_dev,
+                    uint8_t* sel_a_dev, uint8_t* sel_b_dev, int64_t* tally_dev, void* stream) {
+    if (!records_dev || n <= 0 || games_per_lane < 0 || !games_done_dev || !sel_a_dev || !sel_b_dev || !tally_dev)
+        return BGX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    CK(hipMemsetAsync(tally_dev, 0, 16 * sizeof(int64_t), s));
+    hipLaunchKernelGGL(k_arena_begin, dim3((n + 255) / 256), dim3(256), 0, s, records_dev, n, games_per_lane,
+                       games_done_dev, sel_a_dev, sel_b_dev, tally_dev);
+    CKL();
+    return BGX_OK;
+}
+
+int bgx_arena_merge(const uint8_t* sel_a_dev, const uint8_t* sel_b_dev, const int32_t* act_a_dev,
+                    const int32_t* act_b_dev, int32_t n, int32_t* actions_dev, void* stream) {
+    if (!sel_a_dev || !sel_b_dev || !act_a_dev || !act_b_dev || n <= 0 || !actions_dev) return BGX_EINVAL;
+    hipLaunchKernelGGL(k_arena_merge, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, sel_a_dev, sel_b_dev,
+                       act_a_dev, act_b_dev, n, actions_dev);
+    CKL();
+    return BGX_OK;
+}
+
+int bgx_arena_advance(const uint8_t* records_dev, const uint8_t* done_dev, const int32_t* info_dev, int32_t n,
+                      int32_t games_per_lane, int32_t* games_done_dev, uint8_t* sel_a_dev, uint8_t* sel_b_dev,
+                      int64_t* tally_dev, void* stream) {
+    if (!records_dev || !done_dev || !info_dev || n <= 0 || games_per_lane < 0 || !games_done_dev || !sel_a_dev ||
+        !sel_b_dev || !tally_dev)
+        return BGX_EINVAL;
+    hipLaunchKernelGGL(k_arena_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, records_dev,
+                       done_dev, info_dev, n, games_per_lane, games_done_dev, sel_a_dev, sel_b_dev, tally_dev);
+    CKL();
+    return BGX_OK;
+}
+
+int bgx_random_act(const uint8_t* records_dev, int32_t n, uint64_t seed, uint32_t step, int32_t* act_out,
+                   void* stream) {
+    if (!records_dev || n <= 0 || !act_out) return BGX_EINVAL;
+    hipLaunchKernelGGL(k_random_act, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, records_dev, n, seed,
+                       step, act_out);
     CKL();
     return BGX_OK;
 }

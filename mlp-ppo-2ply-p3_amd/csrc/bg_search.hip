@@ -27,6 +27,8 @@
 //             in registers, segmented min per job + atomicMin into minv[job];
 //   k_two_ply_reduce  Q(a) and the first argmax.
 // 1-ply: k_scan, k_expand, k_rows (row keys), k_eval_rows (V per row), k_one_ply_reduce.
+// bgx_one_ply_sel / bgx_two_ply_sel run the same pipelines over the rows of the selected
+// lanes only (lane_selected): a player in a match acts where it is on move.
 // The reference's filter_full_moves_by_max_submoves (get_all_moves.py:73-94) is
 // applied by the evaluator: a leaf counts iff its sub-move count equals the
 // job's final maximum (written at job end), which is exactly "first insertion
@@ -1385,22 +1387,30 @@ __device__ __forceinline__ void wave_first_argmax(int n, F value, int& best, flo
     bestv = n ? bv : 0.0f;
 }
 
-// a lane's legal-move count, held inside the scanned row range [0, total) (equal to the
-// record's count whenever the lanes did not change since k_scan: bgx.h stream ordering)
-__device__ __forceinline__ int row_count(const uint8_t* rr, int32_t off, int64_t total) {
-    const int n = (int)rr[R_NM0] | ((int)rr[R_NM1] << 8);
+// Lane selection (bgx_one_ply_sel / bgx_two_ply_sel): sel = uint8[B], null = every lane.
+// A lane with sel[i] == 0 has no rows at all: k_scan counts 0 for it, so it takes no room
+// in lane_off, row_lane, the job list or the leaf pool, no row of it reaches k_rows (which
+// therefore never reports it as changed), and the reduce kernels leave its outputs alone.
+__device__ __forceinline__ bool lane_selected(const uint8_t* sel, int i) { return !sel || sel[i] != 0; }
+
+// a lane's legal-move count (0 for an unselected lane), held inside the scanned row range
+// [0, total) (equal to the record's count whenever the lanes did not change since k_scan:
+// bgx.h stream ordering)
+__device__ __forceinline__ int row_count(const uint8_t* rr, bool selected, int32_t off, int64_t total) {
+    const int n = selected ? (int)rr[R_NM0] | ((int)rr[R_NM1] << 8) : 0;
     const int64_t room = off >= 0 && off <= total ? total - off : 0;
     return n < room ? n : (int)room;
 }
 
 // 1-ply choice per lane: first argmax of V over its rows (values_out row a = V(a)); one
 // wave per lane.
-__global__ __launch_bounds__(256) void k_one_ply_reduce(Args A, const int32_t* lane_off, const int64_t* total,
-                                                        const float* vrow, int32_t* best, float* bestv, float* vout) {
+__global__ __launch_bounds__(256) void k_one_ply_reduce(Args A, const uint8_t* sel, const int32_t* lane_off,
+                                                        const int64_t* total, const float* vrow, int32_t* best,
+                                                        float* bestv, float* vout) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= A.B) return;
+    if (i >= A.B || !lane_selected(sel, i)) return;
     const uint8_t* rr = A.lanes + (size_t)i * 64;
-    const int n = row_count(rr, lane_off[i], *total);
+    const int n = row_count(rr, true, lane_off[i], *total);
     const float* v = vrow + lane_off[i];
     int ba;
     float bv;
@@ -1416,13 +1426,13 @@ __global__ __launch_bounds__(256) void k_one_ply_reduce(Args A, const int32_t* l
 }
 
 // Q(a) = sum_r p_r minv[a][r] (fp32 FMA, r in roll order), first argmax; one wave per lane.
-__global__ __launch_bounds__(256) void k_two_ply_reduce(Args A, const int32_t* lane_off, const int64_t* total,
-                                                        const int32_t* minv, int32_t* best, float* bestq,
-                                                        float* qout) {
+__global__ __launch_bounds__(256) void k_two_ply_reduce(Args A, const uint8_t* sel, const int32_t* lane_off,
+                                                        const int64_t* total, const int32_t* minv, int32_t* best,
+                                                        float* bestq, float* qout) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= A.B) return;
+    if (i >= A.B || !lane_selected(sel, i)) return;
     const uint8_t* rr = A.lanes + (size_t)i * 64;
-    const int n = row_count(rr, lane_off[i], *total);
+    const int n = row_count(rr, true, lane_off[i], *total);
     int ba;
     float bq;
     wave_first_argmax(n, [&](int a) {
@@ -1506,8 +1516,9 @@ __global__ __launch_bounds__(1024) void k_value_pack16(const float* W1, const fl
 // lane_off[i].  by_mover (2-ply): the rows of lanes whose mover is PLAYER1 come first, then
 // PLAYER2's (each group in lane order), so the enumerators' pool output -- every wave walks
 // rows a grid stride apart -- holds long runs of one replier, which the factored evaluator
-// needs per leaf pair (eval_leaves_fact).
-__global__ __launch_bounds__(1024) void k_scan(Args A, int32_t* lane_off, int64_t* total, int by_mover) {
+// needs per leaf pair (eval_leaves_fact).  An unselected lane (lane_selected) counts 0 rows.
+__global__ __launch_bounds__(1024) void k_scan(Args A, const uint8_t* sel, int32_t* lane_off, int64_t* total,
+                                               int by_mover) {
     __shared__ int64_t part[2][1024];
     const int t = threadIdx.x;
     const int per = (A.B + 1023) / 1024;
@@ -1515,7 +1526,7 @@ __global__ __launch_bounds__(1024) void k_scan(Args A, int32_t* lane_off, int64_
     int64_t sum[2] = {0, 0};
     for (int i = lo; i < hi; ++i) {
         const uint8_t* rr = A.lanes + (size_t)i * 64;
-        sum[by_mover ? rr[R_CUR] & 1 : 0] += (int)rr[R_NM0] | ((int)rr[R_NM1] << 8);
+        sum[by_mover ? rr[R_CUR] & 1 : 0] += lane_selected(sel, i) ? (int)rr[R_NM0] | ((int)rr[R_NM1] << 8) : 0;
     }
     part[0][t] = sum[0];
     part[1][t] = sum[1];
@@ -1532,19 +1543,19 @@ __global__ __launch_bounds__(1024) void k_scan(Args A, int32_t* lane_off, int64_
         const uint8_t* rr = A.lanes + (size_t)i * 64;
         const int g = by_mover ? rr[R_CUR] & 1 : 0;
         lane_off[i] = (int32_t)run[g];
-        run[g] += (int)rr[R_NM0] | ((int)rr[R_NM1] << 8);
+        run[g] += lane_selected(sel, i) ? (int)rr[R_NM0] | ((int)rr[R_NM1] << 8) : 0;
     }
     if (t == 1023) *total = part[0][1023] + part[1][1023];
 }
 
 // row -> lane map, one wave per lane (coalesced stores; one thread per lane walked up to
 // 500 rows serially)
-__global__ __launch_bounds__(256) void k_expand(Args A, const int32_t* lane_off, const int64_t* total,
-                                                int32_t* row_lane) {
+__global__ __launch_bounds__(256) void k_expand(Args A, const uint8_t* sel, const int32_t* lane_off,
+                                                const int64_t* total, int32_t* row_lane) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= A.B) return;
     const int o = lane_off[i];
-    const int n = row_count(A.lanes + (size_t)i * 64, o, *total);
+    const int n = row_count(A.lanes + (size_t)i * 64, lane_selected(sel, i), o, *total);
     for (int a = lane_id(); a < n; a += 64) row_lane[o + a] = i;
 }
 
@@ -1630,6 +1641,11 @@ int bgx_value_pack(const float* W1, const float* b1, const float* wv, const floa
 
 int bgx_one_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, int32_t* best_out,
                 float* bestv_out, float* values_out, void* stream) {
+    return bgx_one_ply_sel(e, vpacked, hidden, value_bias, nullptr, best_out, bestv_out, values_out, stream);
+}
+
+int bgx_one_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                    int32_t* best_out, float* bestv_out, float* values_out, void* stream) {
     if (!e || !vpacked || !best_out || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
     SCK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1657,8 +1673,8 @@ int bgx_one_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value
     uint4* rowkey = (uint4*)(ws + o_key);
     float* vrow = (float*)(ws + o_v);
     const int NT = value_tiles16(hidden);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, lane_off, total, 0);
-    hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, lane_off, total, row_lane);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, sel, lane_off, total, 0);
+    hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, total, row_lane);
     // ~20 legal moves per lane on average: one wave per ~5 rows at B = 4,096
     const size_t gr = B * 6 < 16384 ? (B * 6 > 64 ? B * 6 : 64) : 16384;
     hipLaunchKernelGGL(k_rows, dim3((unsigned)gr), dim3(256), 0, s, A, row_lane, lane_off, total, nullptr, rowside,
@@ -1667,14 +1683,19 @@ int bgx_one_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value
     const EvalRowsArgs E{rowkey, rowside, total, vrow, (const uint4*)(vpacked + 4), vpacked + 4 + kKB * slices(NT) * 64 * 4,
                          value_bias};
     hipLaunchKernelGGL(kr, dim3(eval_grid(e, kr, NT)), dim3(64 * eval_waves(NT)), 0, s, E);
-    hipLaunchKernelGGL(k_one_ply_reduce, dim3((A.B + 3) / 4), dim3(256), 0, s, A, lane_off, total, vrow, best_out,
-                       bestv_out, values_out);
+    hipLaunchKernelGGL(k_one_ply_reduce, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, total, vrow,
+                       best_out, bestv_out, values_out);
     SCK(hipGetLastError());
     return BGX_OK;
 }
 
 int bgx_two_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, int32_t* best_out,
                 float* bestq_out, float* q_out, uint64_t* stats_host, void* stream) {
+    return bgx_two_ply_sel(e, vpacked, hidden, value_bias, nullptr, best_out, bestq_out, q_out, stats_host, stream);
+}
+
+int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                    int32_t* best_out, float* bestq_out, float* q_out, uint64_t* stats_host, void* stream) {
     if (!e || !vpacked || !best_out || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
     SCK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1705,7 +1726,7 @@ int bgx_two_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value
     if (rc != BGX_OK) return rc;
     char* ws = (char*)e->search_ws;
     SCK(hipMemsetAsync(ws + o_ctr, 0, 256, s));
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, (int32_t*)ws, (int64_t*)(ws + o_ctr), 1);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, sel, (int32_t*)ws, (int64_t*)(ws + o_ctr), 1);
     SCK(hipGetLastError());
     int64_t rows64 = 0;
     SCK(hipMemcpyAsync(&rows64, ws + o_ctr, 8, hipMemcpyDeviceToHost, s));
@@ -1744,7 +1765,7 @@ int bgx_two_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value
     float* rowpart = (float*)(ws + o_rp);
 
     if (rows > 0) {
-        hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, lane_off, &ctr->rows, row_lane);
+        hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows, row_lane);
         SCK(hipMemsetAsync(minv, 0x7F, (size_t)jobs * 4, s));
         SCK(hipMemsetAsync(maxlen, 0xFF, (size_t)jobs, s));
         hipLaunchKernelGGL(k_rows, dim3((rows + 3) / 4 < 16384 ? (rows + 3) / 4 : 16384), dim3(256), 0, s, A, row_lane,
@@ -1922,8 +1943,8 @@ int bgx_two_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value
             SCK(hipMemsetAsync(ctr->qcount, 0, 16, s));          // qcount[3], retry_count
         }
     }
-    hipLaunchKernelGGL(k_two_ply_reduce, dim3((A.B + 3) / 4), dim3(256), 0, s, A, lane_off, &ctr->rows, minv, best_out,
-                       bestq_out, q_out);
+    hipLaunchKernelGGL(k_two_ply_reduce, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows, minv,
+                       best_out, bestq_out, q_out);
     SCK(hipGetLastError());
     if (stats_host) {
         unsigned long long lv = 0;
