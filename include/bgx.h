@@ -74,6 +74,13 @@ int bgx_engine_create(int device, int32_t batch, int32_t max_moves, uint64_t see
  * calls it before capturing and as its last captured call, so the graph holds no
  * work it does not join. */
 int bgx_engine_join(bgx_engine* e, void* stream);
+/* Test accessor of the dispatch order (Philox engines; never on a step's path): joins a
+ * pending order into `stream`, copies the order perm (int32[batch], launch position ->
+ * lane), the resolved cost classes (uint8[batch], 0 = heaviest .. 4) and the Philox
+ * counters with their roll-cache bits (uint64[batch]) to HOST buffers, and synchronises
+ * the stream.  Any pointer may be NULL.  BGX_EINVAL for perm / classes when the engine
+ * has no order (MT dice, BGX_ORDER 0) or has not built one yet (before the first reset). */
+int bgx_engine_order(bgx_engine* e, int32_t* perm_host, uint8_t* cls_host, uint64_t* ctr_host, void* stream);
 /* Where a Philox step's light launch (the non-predicted-doubles rest of the dispatch
  * order) and the next step's dispatch order run: fork = 1 (default) on the engine's
  * side stream, fork-joined on events beside the heavy launch; fork = 0 on the caller's

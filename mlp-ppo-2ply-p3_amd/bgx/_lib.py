@@ -50,6 +50,7 @@ SIGNATURES = {
                                           _P, _P, _P, _P, _P]),
     "bgx_counter_add": (ctypes.c_int, [_P, ctypes.c_uint32, _P]),
     "bgx_engine_join": (ctypes.c_int, [_P, _P]),
+    "bgx_engine_order": (ctypes.c_int, [_P, _P, _P, _P, _P]),
     "bgx_value_packed_size": (ctypes.c_int, [_I32]),
     "bgx_value_pack": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P]),
     "bgx_one_ply": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P]),

@@ -141,6 +141,19 @@ class Engine:
         HIP graph capture of steps and as the capture's last call (bgx_engine_join)."""
         check(self._lib.bgx_engine_join(self._h, self._stream()), "bgx_engine_join")
 
+    def order(self):
+        """Test accessor (bgx_engine_order; synchronises): the Philox dispatch order as host
+        numpy arrays (perm int32[B], classes uint8[B], counters uint64[B] with the roll
+        cache in bits 48-63), after joining a pending order."""
+        import numpy as np
+        perm = np.empty(self.batch, np.int32)
+        cls = np.empty(self.batch, np.uint8)
+        ctr = np.empty(self.batch, np.uint64)
+        check(self._lib.bgx_engine_order(self._h, perm.ctypes.data_as(ctypes.c_void_p),
+                                         cls.ctypes.data_as(ctypes.c_void_p), ctr.ctypes.data_as(ctypes.c_void_p),
+                                         self._stream()), "bgx_engine_order")
+        return perm, cls, ctr
+
     def set_fork(self, fork: bool):
         """fork=True (default): a Philox step's light launch and the next dispatch order
         run on the engine's side stream beside the heavy launch; False: all of a step

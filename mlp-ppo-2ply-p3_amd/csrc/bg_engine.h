@@ -166,10 +166,12 @@ struct Args {
     uint64_t* stamps;         // diagnostics only (debug option BGX_STAMPS): [B][2] start/end s_memrealtime
     int cap_mid;              // tier 1's unique-afterstate cap (cap_fast<kLogMid>; tests: BGX_TIER1_CAP)
     int cap_main;             // bgx_movegen's main-table cap (cap_fast<9>; tests: BGX_MOVEGEN_CAP)
-    // dispatch order (Philox mode): each step predicts its lane's next-turn cost class
-    // into cls; k_order turns the classes into perm (heaviest first) for the next launch.
+    // dispatch order (Philox mode): each step leaves its lane's pre-class byte in pre;
+    // k_order_count resolves it with the lane's next roll into the cost class cls, and
+    // k_order_scatter turns the classes into perm (heaviest first) for the next launch.
     int32_t* perm;            // blockIdx -> lane, or null (identity)
-    uint8_t* cls;             // [B] predicted cost class, or null
+    uint8_t* cls;             // [B] predicted cost class (written by k_order_count), or null
+    uint8_t* pre;             // [B] pre-class byte (pre_class), written by k_step / k_reset; null with cls
     int xcd;                  // B % 128 == 0: XCD-aware dispatch (16-lane runs per XCD, bg_engine.hip k_order_*)
 };
 
@@ -185,32 +187,45 @@ __device__ __forceinline__ int lane_of_block(const Args& A, int bi) {
 constexpr int kClasses = 5;
 
 // Philox counters (the low 48 bits) carry in bits 48-63 the lane's next roll as
-// the previous step predicted it (predict_class): valid << 15 | r0 | r1 << 3 |
-// draws << 6.  The next normal roll takes it instead of running the same Philox
-// block again and advances the counter by the draws; a reset ignores it (it
-// draws from the counter as if nothing had been predicted), so the dice stream
-// is exactly the one without the cache.
+// the order pass after the previous step predicted it (predict_class): valid << 15 |
+// r0 | r1 << 3 | draws << 6.  The next normal roll takes it instead of running
+// the same Philox block again and advances the counter by the draws; a reset
+// ignores it (it draws from the counter as if nothing had been predicted), so
+// the dice stream is exactly the one without the cache.
 constexpr uint64_t kCtrMask = (1ull << 48) - 1ull;
 
-// Cost class of the lane's NEXT movegen (0 = heaviest).  Philox dice are a pure
-// function of (key, lane, counter), so the next roll is known now; the mover
-// after the next apply is 1 - cur.  Doubles dominate (a 4-deep DFS) and grow
-// with the number of points the mover occupies.  Only a scheduling hint.
-__device__ __forceinline__ int predict_class(int bv, uint64_t ctr, const Args& A, int gi, uint32_t& cache) {
-    cache = 0u;
-    if (rd(bv, R_OVER)) return kClasses - 1;              // next: reset -> opening roll (never doubles)
-    Rng r;
-    const uint64_t c0 = ctr & kCtrMask;
-    r.init_philox(c0, A.key0, A.key1, (uint32_t)gi);
-    const int a = r.die(), b = r.die();
-    const uint64_t draws = r.ctr - c0;
-    if (draws < 32) cache = 0x8000u | (uint32_t)a | ((uint32_t)b << 3) | ((uint32_t)draws << 6);
-    if (a != b) return kClasses - 1;
+// Pre-class byte of a lane: what its NEXT movegen's cost class needs from the board
+// (the mover after the next apply is 1 - cur): kPreOver when the game is over, else
+// the points that mover occupies, + 2 with a checker on the bar (0..26).  The
+// wave's part of the prediction (one ballot); the roll is predict_class's.
+constexpr int kPreOver = 0x80;
+__device__ __forceinline__ int pre_class(int bv) {
+    if (rd(bv, R_OVER)) return kPreOver;                  // next: reset -> opening roll (never doubles)
     const int nxt = 1 - rd(bv, R_CUR);
     const int l = lane_id();
     const int off = nxt * 24;
     const bool mine = l >= off && l < off + 24 && bv > 0;
-    const int pts = __popcll(__ballot(mine)) + (rd(bv, 48 + nxt) > 0 ? 2 : 0);
+    return __popcll(__ballot(mine)) + (rd(bv, 48 + nxt) > 0 ? 2 : 0);
+}
+
+// Cost class of the lane's NEXT movegen (0 = heaviest) from its pre-class byte and
+// Philox counter.  Philox dice are a pure function of (key, lane, counter), so the
+// next roll is known now.  Doubles dominate (a 4-deep DFS) and grow with the
+// number of points the mover occupies.  Only a scheduling hint; `cache` is the
+// roll for bits 48-63 of the counter (0 = none).  One thread per lane
+// (k_order_count): no wave intrinsics, correct under divergence.
+__device__ __forceinline__ int predict_class(int pre, uint64_t ctr, uint32_t key0, uint32_t key1, uint32_t lane_no,
+                                             uint32_t& cache) {
+    cache = 0u;
+    if (pre & kPreOver) return kClasses - 1;
+    Rng r;
+    const uint64_t c0 = ctr & kCtrMask;
+    r.init_philox(c0, key0, key1, lane_no);
+    const int a = r.die(), b = r.die();
+    const uint64_t draws = r.ctr - c0;
+    if (draws < 32) cache = 0x8000u | (uint32_t)a | ((uint32_t)b << 3) | ((uint32_t)draws << 6);
+    if (a != b) return kClasses - 1;
+    const int pts = pre;
     // tail risk of a doubles movegen grows with the points the mover occupies and
     // falls with the die (tools/stamps.py table: p99 150-270 us at >= 9 points
     // for 1-1 .. 4-4, ~60 us at 5 points): longest-first order
@@ -425,7 +440,7 @@ struct bgx_engine {
     int slow_waves;
     int32_t* perm;        // dispatch order for k_step (Philox mode), built by k_order
     bool perm_valid;
-    int32_t* order_cnt;   // k_order_count -> k_order_scatter, [B/1024+1][kClasses]
+    int32_t* order_cnt;   // k_order_count -> k_order_scatter, [B/256+1][8 sub-lists][kClasses]
     // overflow counters, two 16-byte sets: a Philox step uses set `ovf_parity`
     // (Args::ovf_count) and its k_order_count zeroes the other set for the next
     // step, so the step needs no separate memset launch

@@ -34,8 +34,8 @@ using namespace bg;
 
 // -------------------------------------------------------------- kernels --
 // PHASE 0: apply + advance fused (per-lane dice); 1: apply only; 2: advance only.
-// One lane's step: apply (PHASE 0/1), roll + movegen (PHASE 0/2), record, next
-// dispatch class.
+// One lane's step: apply (PHASE 0/1), roll + movegen (PHASE 0/2), record, the
+// next dispatch class's pre-class byte (the order pass resolves it).
 template <int PHASE, int LOG, int MEMO, bool NO_DOUBLES = false>
 __device__ __forceinline__ void step_lane(const Args& A, int gi, uint4* tab, uint4* memo, const int32_t* actions,
                                           float* obs, float* reward, uint8_t* done, int32_t* info) {
@@ -50,13 +50,9 @@ __device__ __forceinline__ void step_lane(const Args& A, int gi, uint4* tab, uin
         if (obs) write_obs(bv, obs + (size_t)gi * 198);
     }
     store_rec(A, gi, bv);
-    if (PHASE == 0 && A.cls) {
-        uint32_t cache;
-        const int c = predict_class(bv, ctr, A, gi, cache);
-        if (lane_id() == 0) {
-            A.cls[gi] = (uint8_t)c;
-            if (cache) A.ctr[gi] = (ctr & kCtrMask) | ((uint64_t)cache << 48);
-        }
+    if (PHASE == 0 && A.pre) {
+        const int p = pre_class(bv);
+        if (lane_id() == 0) A.pre[gi] = (uint8_t)p;
     }
     if (A.stamps && lane_id() == 0) {
         A.stamps[2 * gi] = t0;
@@ -90,21 +86,18 @@ __global__ __launch_bounds__(64) void k_reset(Args A, const uint8_t* lane_mask, 
     if (!mark_only) {
         bv = advance_lane<LOG>(bv, gi, A, tab, memo, &ctr);
         if (obs) write_obs(bv, obs + (size_t)gi * 198);
-        if (A.cls) {
-            uint32_t cache;
-            const int c = predict_class(bv, ctr, A, gi, cache);
-            if (lane_id() == 0) {
-                A.cls[gi] = (uint8_t)c;
-                if (cache) A.ctr[gi] = (ctr & kCtrMask) | ((uint64_t)cache << 48);
-            }
+        if (A.pre) {
+            const int p = pre_class(bv);
+            if (lane_id() == 0) A.pre[gi] = (uint8_t)p;
         }
     }
     store_rec(A, gi, bv);
 }
 
 // Next dispatch order = lanes grouped by predicted class (class 0 first), in
-// lane order within a class: a two-pass counting sort over blocks of 1024
-// lanes.  perm is a full permutation of 0..B-1 whatever cls holds.
+// lane order within a class: a two-pass counting sort (pass 1 also resolves the
+// classes; it counts blocks of 256 lanes, pass 2 places blocks of 1024).  perm
+// is a full permutation of 0..B-1 whatever pre and the counters hold.
 //
 // XCD-aware form (B % 128 == 0): the lanes are split into 8 sub-lists by
 // x = (lane >> 4) & 7 (runs of 16 lanes), each sub-list is class-sorted on its
@@ -120,15 +113,33 @@ __device__ __forceinline__ int order_class(const uint8_t* cls, int i, int B) {
     return i < B ? min((int)cls[i], kClasses - 1) : kClasses;     // kClasses = padding, never written
 }
 
-// pass 1: cnt[b][x][c] = lanes of class c in sub-list x of block b (x = 0 when !xcd)
-__global__ __launch_bounds__(1024) void k_order_count(const uint8_t* cls, int32_t* cnt, int B, int32_t* zero_next,
+// pass 1: thread i resolves lane i's class from the step's pre-class byte and the
+// lane's next roll (predict_class: the Philox block as VALU work for 64 lanes per
+// instruction, where the step's waves would each run it on their CU's scalar unit),
+// leaves the roll in the counter's cache bits for the next roll_lane, and counts:
+// cnt[b][x][c] = lanes of class c in sub-list x of block b (x = 0 when !xcd).
+// Blocks of kCountThreads lanes, a quarter of pass 2's: the Philox block is a chain of
+// dependent multiplies, so the pass is latency-bound and spreads over 4x the CUs.
+// Run again with no step between, it finds the same counter (low 48 bits) and
+// pre-class byte and writes the same cache word and class.
+constexpr int kCountThreads = 256;
+__global__ __launch_bounds__(kCountThreads) void k_order_count(const uint8_t* pre, uint8_t* cls, uint64_t* ctr, uint32_t key0,
+                                                      uint32_t key1, int32_t* cnt, int B, int32_t* zero_next,
                                                       int xcd) {
     __shared__ int sc[kXcd][kClasses];
-    const int t = threadIdx.x, i = blockIdx.x * 1024 + t, w = t >> 6;
+    const int t = threadIdx.x, i = blockIdx.x * kCountThreads + t, w = t >> 6;
     if (blockIdx.x == 0 && t < 4) zero_next[t] = 0;     // the next step's overflow counters
     if (t < kXcd * kClasses) sc[t / kClasses][t % kClasses] = 0;
     __syncthreads();
-    const int c = order_class(cls, i, B);
+    int c = kClasses;                                   // padding past B: no Philox, never written
+    if (i < B) {
+        const int p = (int)pre[i];
+        const uint64_t cv = (p & kPreOver) ? 0ull : ctr[i];
+        uint32_t cache;
+        c = predict_class(p, cv, key0, key1, (uint32_t)i, cache);
+        if (cache) ctr[i] = (cv & kCtrMask) | ((uint64_t)cache << 48);
+        cls[i] = (uint8_t)c;
+    }
     #pragma unroll
     for (int k = 0; k < kClasses; ++k) {
         const uint64_t m = __ballot(c == k);
@@ -150,22 +161,24 @@ __global__ __launch_bounds__(1024) void k_order_count(const uint8_t* cls, int32_
 // pass 2: position (within the lane's sub-list) = (lanes of lower classes) +
 // (class-c lanes of earlier blocks) + (class-c lanes earlier in this block)
 __global__ __launch_bounds__(1024) void k_order_scatter(const uint8_t* cls, const int32_t* cnt, int32_t* perm, int B,
-                                                        int nblk, int xcd) {
-    constexpr int NC = kXcd * kClasses;
+                                                        int ncnt, int xcd) {
+    constexpr int NC = kXcd * kClasses, STRIPES = 1024 / NC, PER = 1024 / kCountThreads;
     __shared__ int tot[NC], pre[NC], wsum[16][4][kClasses];
     const int t = threadIdx.x, b = blockIdx.x, w = t >> 6, l = t & 63;
     if (t < NC) { tot[t] = 0; pre[t] = 0; }
     __syncthreads();
-    // thread t < NC sums counter t over the blocks (40 counters, <= B/1024 blocks)
-    if (t < NC) {
+    // the 40 counters summed over pass 1's ncnt blocks (PER of them per block of this
+    // pass), in STRIPES strided partial sums per counter
+    if (t < NC * STRIPES) {
+        const int k = t % NC;
         int a_tot = 0, a_pre = 0;
-        for (int j = 0; j < nblk; ++j) {
-            const int v = cnt[j * NC + t];
+        for (int j = t / NC; j < ncnt; j += STRIPES) {
+            const int v = cnt[j * NC + k];
             a_tot += v;
-            a_pre += j < b ? v : 0;
+            a_pre += j < b * PER ? v : 0;
         }
-        tot[t] = a_tot;
-        pre[t] = a_pre;
+        if (a_tot) atomicAdd(&tot[k], a_tot);
+        if (a_pre) atomicAdd(&pre[k], a_pre);
     }
     const int i = b * 1024 + t;
     const int c = order_class(cls, i, B);
@@ -629,11 +642,11 @@ long long bgx_dbg_int(const char* name, long long dflt) {
 #define CKL() do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return fail(_e); } while (0)
 
 static void launch_order(bgx_engine* e, hipStream_t s) {
-    const int nblk = (e->a.B + 1023) / 1024;
-    hipLaunchKernelGGL(k_order_count, dim3(nblk), dim3(1024), 0, s, e->a.cls, e->order_cnt, e->a.B,
-                       e->ovf_base + 4 * (e->ovf_parity ^ 1), e->a.xcd);
+    const int nblk = (e->a.B + 1023) / 1024, ncnt = (e->a.B + kCountThreads - 1) / kCountThreads;
+    hipLaunchKernelGGL(k_order_count, dim3(ncnt), dim3(kCountThreads), 0, s, e->a.pre, e->a.cls, e->a.ctr, e->a.key0, e->a.key1,
+                       e->order_cnt, e->a.B, e->ovf_base + 4 * (e->ovf_parity ^ 1), e->a.xcd);
     e->ovf_next_zeroed = true;
-    hipLaunchKernelGGL(k_order_scatter, dim3(nblk), dim3(1024), 0, s, e->a.cls, e->order_cnt, e->perm, e->a.B, nblk,
+    hipLaunchKernelGGL(k_order_scatter, dim3(nblk), dim3(1024), 0, s, e->a.cls, e->order_cnt, e->perm, e->a.B, ncnt,
                        e->a.xcd);
     e->perm_valid = true;
 }
@@ -715,12 +728,14 @@ int bgx_engine_create(int device, int32_t batch, int32_t max_moves, uint64_t see
     if (dice_mode == BGX_DICE_PHILOX && bgx_dbg_int("BGX_ORDER", 1) != 0) {
         alloc((void**)&e->perm, B * 4);
         alloc((void**)&A.cls, B);
-        alloc((void**)&e->order_cnt, (B / 1024 + 1) * kXcd * kClasses * 4);
+        alloc((void**)&A.pre, B);
+        alloc((void**)&e->order_cnt, (B / kCountThreads + 1) * kXcd * kClasses * 4);
     }
     if (err != hipSuccess) { bgx_engine_destroy(e); return fail(err, BGX_ENOMEM); }
     if (hipMemset(A.lanes, 0, B * 64) != hipSuccess || hipMemset(A.ctr, 0, B * 8) != hipSuccess ||
         hipMemset(e->ovf_base, 0, 32) != hipSuccess || hipMemset(A.err, 0, 16) != hipSuccess ||
-        hipMemset(A.n_total, 0, B * 4) != hipSuccess || (A.cls && hipMemset(A.cls, 0, B) != hipSuccess)) {
+        hipMemset(A.n_total, 0, B * 4) != hipSuccess || (A.cls && hipMemset(A.cls, 0, B) != hipSuccess) ||
+        (A.pre && hipMemset(A.pre, 0, B) != hipSuccess)) {
         bgx_engine_destroy(e);
         return fail(hipGetLastError());
     }
@@ -745,6 +760,28 @@ int bgx_engine_join(bgx_engine* e, void* stream) {
     return BGX_OK;
 }
 
+int bgx_engine_order(bgx_engine* e, int32_t* perm_host, uint8_t* cls_host, uint64_t* ctr_host, void* stream) {
+    if (!e) return BGX_EINVAL;
+    // no dispatch order (not Philox, or BGX_ORDER 0), or none built yet (before the first reset / step)
+    if ((perm_host || cls_host) && (!e->a.cls || !e->perm_valid)) return BGX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t B = (size_t)e->a.B;
+    CK(hipSetDevice(e->device));
+    {
+        EngineUse use(e, s);
+        CK(use.err);
+        if (e->order_pending) {              // the last step's dispatch order, on the side stream
+            CK(hipStreamWaitEvent(s, e->step_ev[3], 0));
+            e->order_pending = false;
+        }
+        if (perm_host) CK(hipMemcpyAsync(perm_host, e->perm, B * 4, hipMemcpyDeviceToHost, s));
+        if (cls_host) CK(hipMemcpyAsync(cls_host, e->a.cls, B, hipMemcpyDeviceToHost, s));
+        if (ctr_host) CK(hipMemcpyAsync(ctr_host, e->a.ctr, B * 8, hipMemcpyDeviceToHost, s));
+    }
+    CK(hipStreamSynchronize(s));
+    return BGX_OK;
+}
+
 int bgx_engine_set_fork(bgx_engine* e, int32_t fork, void* stream) {
     if (!e) return BGX_EINVAL;
     CK(hipSetDevice(e->device));
@@ -765,7 +802,8 @@ int bgx_engine_destroy(bgx_engine* e) {
     if (e->use_ev) (void)hipEventDestroy(e->use_ev);
     Args& A = e->a;
     void* ptrs[] = {A.lanes, A.moves, A.n_total, A.mt, A.ctr, A.shared_rolls, e->ovf_base, A.ovf_queue, A.err,
-                    e->slow_tables, e->search_ws, e->search_pool, e->oneply_ws, A.stamps, e->perm, A.cls, e->order_cnt};
+                    e->slow_tables, e->search_ws, e->search_pool, e->oneply_ws, A.stamps, e->perm, A.cls, A.pre,
+                    e->order_cnt};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t ev : e->search_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->step_ev) if (ev) (void)hipEventDestroy(ev);
@@ -931,9 +969,12 @@ int bgx_step(bgx_engine* e, const int32_t* actions_dev, float* obs_dev, float* r
             CK(hipEventRecord(e->step_ev[1], e->step_side));
             if (A.cls) {
                 // the next dispatch order on the side stream once both launches have
-                // written their classes: it runs beside this stream's overflow tiers
-                // and the caller's next policy kernel instead of before them; the
-                // next bgx_step waits for it (step_ev[3]) before its own launches
+                // written their pre-class bytes and counters: it runs beside this
+                // stream's overflow tiers and the caller's next policy kernel instead
+                // of before them (neither touches pre, cls, perm or the counters); the
+                // order pass writes the counters' roll cache, so the next bgx_step and
+                // every other call that reads or rewrites counters waits for it
+                // (step_ev[3], order_pending) before its own launches
                 CK(hipEventRecord(e->step_ev[2], s));
                 CK(hipStreamWaitEvent(e->step_side, e->step_ev[2], 0));
                 launch_order(e, e->step_side);
