@@ -447,6 +447,32 @@ int bgx_ppo_gw1(const void* dh_dev, const uint8_t* records_dev, int32_t m, int32
 int bgx_lane_returns(const float* rewards_dev, const uint8_t* dones_dev, int32_t T, int32_t B, float gamma,
                      float* out_dev, void* stream);
 
+/* Zero-sum GAE(lambda) of a [T][B] self-play rollout per game lane (bgx.train.selfplay_gae;
+ * DESIGN.md §6 "Self-play returns").  Both players of a game share a lane; records_dev
+ * uint8[T][B][64] holds the mover of step t in byte 52, values_dev [T][B] that mover's
+ * value.  Walking t = T-1 .. 0 with A_T = 0, cut = done_t, same = (mover_{t+1} == mover_t):
+ *   nv = cut ? 0 : (same ? v_{t+1} : -v_{t+1});   na = cut ? 0 : (same ? A_{t+1} : -A_{t+1})
+ *   A_t = ((r_t + g nv) - v_t) + gl na;           Ret_t = A_t + v_t
+ * in fp32, each product and sum rounded once (no fma); g = fp32(gamma), gl = fp32(g lambda).
+ * boot_values_dev [B] and boot_records_dev uint8[B][64] (only byte 52 is read) are v_T and
+ * mover_T, the position the rollout stopped in; both NULL: step T-1 is a cut.  adv_dev,
+ * ret_dev [T][B] fp32.  sums_dev (fp64[3], may be NULL) receives (sum A, sum A^2, T B):
+ * fp64 per-block partials in workspace_dev (bgx_selfplay_gae_workspace(B) bytes; may be
+ * NULL with sums_dev NULL) added in a fixed order, identical from run to run.  No host
+ * sync, no allocation.  BGX_EINVAL: T <= 0, B <= 0, a NULL required pointer, or exactly one
+ * boot pointer. */
+int64_t bgx_selfplay_gae_workspace(int32_t B);
+int bgx_selfplay_gae(const float* rewards_dev, const uint8_t* dones_dev, const uint8_t* records_dev,
+                     const float* values_dev, const float* boot_values_dev, const uint8_t* boot_records_dev,
+                     int32_t T, int32_t B, float g, float gl, float* adv_dev, float* ret_dev, double* workspace_dev,
+                     double* sums_dev, void* stream);
+
+/* Advantage normalisation in place from sums_dev fp64[3] = (sum, sum of squares, count)
+ * read on the device (bgx_selfplay_gae's, all-reduced across ranks where there are several;
+ * bgx.ppo.global_normalize's arithmetic): mean = s0 / n and var = (s1 - n mean^2) / (n - 1)
+ * in fp64, var clamped at 0, then adv = (adv - fp32(mean)) / (fp32(sqrt(var)) + eps) in fp32. */
+int bgx_normalize_adv(float* adv_dev, int64_t n, const double* sums_dev, float eps, void* stream);
+
 /* The fused fp16 PPO epoch's prologue and epilogue (bgx.train._ppo_epoch_amp_fused), one
  * launch each.  bgx_ppo_epoch_prep: from the fp32 parameters (fc1 weight [H][198] and bias,
  * action_head [A][H] and bias, value_head [1][H] and bias) the packed fc1 fragments of

@@ -81,6 +81,10 @@ SIGNATURES = {
     "bgx_copy_regions": (ctypes.c_int, [_P, _I32, _I32, _P]),
     "bgx_host_device_ptr": (ctypes.c_int, [_P, ctypes.POINTER(_P)]),
     "bgx_lane_returns": (ctypes.c_int, [_P, _P, _I32, _I32, ctypes.c_float, _P, _P]),
+    "bgx_selfplay_gae_workspace": (ctypes.c_int64, [_I32]),
+    "bgx_selfplay_gae": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float, ctypes.c_float, _P, _P, _P,
+                                        _P, _P]),
+    "bgx_normalize_adv": (ctypes.c_int, [_P, ctypes.c_int64, _P, ctypes.c_float, _P]),
     "bgx_ppo_epoch_prep": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                           _P, _P]),
     "bgx_ppo_epoch_grads": (ctypes.c_int, [_P, _P, _P, _I32, _I32, ctypes.c_float, _P, _P, _P, _P, _P, _P, _P, _P,

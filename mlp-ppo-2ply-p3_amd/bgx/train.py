@@ -27,12 +27,20 @@ train.py, so `entropy_anneal="train"` (constant 0.15) is the default;
 Returns: `returns="lane"` (default) discounts within each game lane;
 `returns="reference"` reproduces the reference's quirk of discounting over the
 flat step-major memory in which the environments are interleaved
-(ppo_agent.py:206-216).
+(ppo_agent.py:206-216).  Both restate the reference: one unsigned
+reward stream runs across both players of a lane, and nothing is bootstrapped at
+the horizon.  `returns="selfplay"` treats the lane as the two-player zero-sum game
+it is: GAE(lambda) from the mover's point of view, the sign flipped where the turn
+passes, cut at each game end, bootstrapped from the value of the position the
+rollout stopped in (selfplay_gae, two HIP calls; `gae_lambda`, `gamma`; DESIGN.md §6
+"Self-play returns").  The advantages are normalised over all rows, the value
+targets are not.
 
     python -m bgx.train --batch 65536 --horizon 64 --updates 10 [--metrics m.jsonl]
     torchrun --nproc-per-node 8 -m bgx.train ...            (one process per GPU)
     python -m bgx.train ... --eval-every 5 --eval-opponent random   (a head-to-head match of
         the current weights after every 5th update, bgx.arena; one rank only)
+    python -m bgx.train ... --returns selfplay [--gae-lambda 0.95] [--gamma 0.99]
 """
 from __future__ import annotations
 
@@ -86,6 +94,106 @@ def _lane_returns_torch(rewards: torch.Tensor, dones: torch.Tensor, gamma: float
         R = rewards[t] + gamma * R
         out[t] = R
     return out
+
+
+RETURNS_MODES = ("lane", "reference", "selfplay")
+
+
+def check_returns_mode(returns: str) -> str:
+    if returns not in RETURNS_MODES:
+        raise ValueError(f"returns must be one of {RETURNS_MODES}, got {returns!r}")
+    return returns
+
+
+def _gae_scalars(gamma: float, lam: float):
+    """g = fp32(gamma), gl = fp32(fp32(gamma) * fp32(lam)) as Python floats."""
+    g = np.float32(gamma)
+    return float(g), float(np.float32(g * np.float32(lam)))
+
+
+def selfplay_gae(rewards: torch.Tensor, dones: torch.Tensor, records: torch.Tensor, values: torch.Tensor,
+                 boot_values: torch.Tensor | None = None, boot_records: torch.Tensor | None = None,
+                 gamma: float = GAMMA, lam: float = 0.95, normalize: bool = True, group=None):
+    """Zero-sum GAE(lambda) of a self-play rollout, per game lane (DESIGN.md §6 "Self-play
+    returns"): both players move in one lane, `values[t]` is the value of the player on move
+    at step t (record byte 52), so the next step's value and advantage change sign where the
+    mover changes and are dropped at a done.  boot_values [B] / boot_records [B, 64]: value
+    and record of the position the rollout stopped in (both or neither; without them the
+    horizon is a cut).  Returns (adv, ret) [T, B]: ret = A + v un-normalised, adv = A
+    normalised as global_normalize does over all ranks' rows (normalize=False: A itself).
+    On the GPU two HIP calls and no host sync (bgx_selfplay_gae, bgx_normalize_adv; with a
+    process group the three sums are all-reduced between them); _selfplay_gae_torch
+    elsewhere."""
+    if (boot_values is None) != (boot_records is None):
+        raise ValueError("selfplay_gae: boot_values and boot_records go together")
+    if not (rewards.is_cuda and rewards.dtype == torch.float32 and values.dtype == torch.float32
+            and dones.dtype == torch.uint8 and records.dtype == torch.uint8):
+        return _selfplay_gae_torch(rewards, dones, records, values, boot_values, boot_records, gamma, lam,
+                                   normalize, group)
+    T, B = rewards.shape[0], rewards[0].numel()
+    if records.numel() != T * B * 64 or values.numel() != T * B or dones.numel() != T * B:
+        raise ValueError("selfplay_gae: rewards, dones, values [T, B] and records [T, B, 64] do not agree")
+    r, d, rec, v = rewards.contiguous(), dones.contiguous(), records.contiguous(), values.contiguous()
+    bv = br = None
+    if boot_values is not None:
+        bv, br = boot_values.contiguous(), boot_records.contiguous()
+        if bv.dtype != torch.float32 or br.dtype != torch.uint8 or bv.numel() != B or br.numel() != B * 64:
+            raise ValueError("selfplay_gae: boot_values must be float32 [B], boot_records uint8 [B, 64]")
+    g, gl = _gae_scalars(gamma, lam)
+    L = _lib.load()
+    dev = r.device
+    adv, ret = torch.empty_like(r), torch.empty_like(r)
+    sums = ws = None
+    if normalize:
+        sums = torch.empty(3, dtype=torch.float64, device=dev)
+        ws = torch.empty(max(int(L.bgx_selfplay_gae_workspace(B)) // 8, 1), dtype=torch.float64, device=dev)
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    check(L.bgx_selfplay_gae(_ptr_or_none(r), _ptr_or_none(d), _ptr_or_none(rec), _ptr_or_none(v), _ptr_or_none(bv),
+                             _ptr_or_none(br), T, B, g, gl, _ptr_or_none(adv), _ptr_or_none(ret), _ptr_or_none(ws),
+                             _ptr_or_none(sums), stream), "bgx_selfplay_gae")
+    if normalize:
+        if _world(group) > 1:
+            dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
+        check(L.bgx_normalize_adv(_ptr_or_none(adv), adv.numel(), _ptr_or_none(sums), 1e-5, stream),
+              "bgx_normalize_adv")
+    return adv, ret
+
+
+def _selfplay_gae_torch(rewards: torch.Tensor, dones: torch.Tensor, records: torch.Tensor, values: torch.Tensor,
+                        boot_values: torch.Tensor | None = None, boot_records: torch.Tensor | None = None,
+                        gamma: float = GAMMA, lam: float = 0.95, normalize: bool = True, group=None):
+    """selfplay_gae as a torch loop over the T steps, in the dtype of `rewards` (fp32: the
+    kernel's roundings; fp64: the tests' reference).  gamma and gamma * lambda are the
+    fp32-rounded scalars in either dtype."""
+    if (boot_values is None) != (boot_records is None):
+        raise ValueError("selfplay_gae: boot_values and boot_records go together")
+    T = rewards.shape[0]
+    g, gl = _gae_scalars(gamma, lam)
+    values = values.to(rewards.dtype)
+    movers = records[..., 52]
+    adv, ret = torch.empty_like(rewards), torch.empty_like(rewards)
+    zero = torch.zeros_like(rewards[0])
+    A1 = zero
+    if boot_values is not None:
+        v1, m1 = boot_values.to(rewards.dtype).reshape(zero.shape), boot_records[..., 52].reshape(zero.shape)
+        cut_next = torch.zeros_like(dones[0], dtype=torch.bool)
+    else:
+        v1, m1 = zero, movers[T - 1]
+        cut_next = torch.ones_like(dones[0], dtype=torch.bool)
+    for t in range(T - 1, -1, -1):
+        cut = dones[t].bool() | cut_next
+        same = movers[t] == m1
+        nv = torch.where(cut, zero, torch.where(same, v1, -v1))
+        na = torch.where(cut, zero, torch.where(same, A1, -A1))
+        delta = (rewards[t] + g * nv) - values[t]
+        A1 = delta + gl * na
+        adv[t] = A1
+        ret[t] = A1 + values[t]
+        v1, m1 = values[t], movers[t]
+        cut_next = torch.zeros_like(cut)
+    if normalize:
+        adv = global_normalize(adv.reshape(-1), group).view_as(adv)
+    return adv, ret
 
 
 EPISODE_STATS = ("episodes", "episode_reward_sum", "wins", "p1_wins", "gammons", "backgammons")
@@ -722,15 +830,18 @@ class PPOTrainer:
                  seed: int = 0, device=None, process_group=None, pinned: bool = False, returns: str = "lane",
                  chunk: int = 1 << 21, fused: bool | None = None, amp: bool = True,
                  entropy_anneal: str = "train", shards: int | None = None, graphs: bool | None = None,
-                 fork: bool | None = None, streams=None, update_graphs: bool | None = None):
+                 fork: bool | None = None, streams=None, update_graphs: bool | None = None,
+                 gae_lambda: float = 0.95, gamma: float = GAMMA):
         if entropy_anneal not in ("train", "train_single"):
             raise ValueError(f"entropy_anneal must be 'train' or 'train_single', got {entropy_anneal!r}")
         self.entropy_anneal = entropy_anneal
-        self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.returns_mode = check_returns_mode(returns)
+        self.dev =torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.group = process_group
         self.rank = dist.get_rank(process_group) if _world(process_group) > 1 else 0
         self.B, self.T, self.A = batch, horizon, n_actions
-        self.returns_mode = returns
+        # returns="selfplay" only: GAE's lambda and the discount (the other modes discount by GAMMA)
+        self.gae_lambda, self.gamma = float(gae_lambda), float(gamma)
         # rows per update chunk (gradient accumulation over chunks): 2^21 = a whole 65,536 x 32
         # rollout in one chunk, the reference's single full batch; 2^20-row chunks cost
         # 8.4 vs 7.8 ms per update (twice the per-call partial sums and launches)
@@ -811,8 +922,15 @@ class PPOTrainer:
             if (B // self.S) % 16:
                 raise ValueError(f"pinned=True copies each shard's lanes in 16-byte chunks: the shard batch "
                                  f"{B // self.S} must be a multiple of 16")
-            self.mirror = HostMirror(self.buf)
+            self.mirror = HostMirror(dict(self.buf))        # the [T, B] step fields only
             self.pinned = self.mirror.host
+        # returns="selfplay": value and record of the position each lane's rollout stopped in
+        # (GAE's bootstrap), written by rollout()'s closing value pass or load_rollout
+        self._boot = False
+        if self.returns_mode == "selfplay":
+            self.buf["boot_values"] = torch.empty(B, dtype=torch.float32, **kw)
+            self.buf["boot_records"] = torch.empty(B, 64, dtype=torch.uint8, **kw)
+            self._boot_scratch = (torch.empty(B, dtype=torch.int32, **kw), torch.empty(B, dtype=torch.float32, **kw))
         self.ep_carry = torch.zeros(B, dtype=torch.float64, **kw)     # train.py:58 episode_rewards
         self.last_episode_stats = None
         for e in self.engs:
@@ -863,6 +981,17 @@ class PPOTrainer:
         self.net.act(self.engs[k], seed=self.seed * 7919 + self.rank + 104_729 * k, step=step, step_ctr=step_ctr,
                      out=out, records_out=rec)
         self.engs[k].step(out[0], want_obs=False, want_info=False, out=env_out)
+
+    def _boot_pass(self, k: int):
+        """returns="selfplay": one value pass over shard k's lanes as the rollout left them
+        (the packed weights the rollout used), into boot_values / boot_records.  Greedy: no
+        noise is drawn, so neither the step counter nor any generator moves; the action and
+        log-prob go to scratch.  Eager, after the replayed graphs, on the shard's stream."""
+        n = self.B // self.S
+        lo, hi = k * n, (k + 1) * n
+        a, lp = self._boot_scratch
+        self.net.act(self.engs[k], greedy=True, out=(a[lo:hi], lp[lo:hi], self.buf["boot_values"][lo:hi]),
+                     records_out=self.buf["boot_records"][lo:hi])
 
     def _capture(self):
         """One graph per (slot pair, shard): act + step for slots t and t + 1 with the
@@ -925,6 +1054,11 @@ class PPOTrainer:
             for k in range(self.S):
                 with torch.cuda.stream(self._streams[k]):
                     self._join_copies(k)
+        if self.returns_mode == "selfplay":
+            for k in range(self.S):
+                with torch.cuda.stream(self._streams[k]):
+                    self._boot_pass(k)
+            self._boot = True
         for st in self._streams[1:]:
             cur.wait_stream(st)
         if cur is not None and cur != torch.cuda.current_stream(self.dev):
@@ -947,12 +1081,24 @@ class PPOTrainer:
         self.total_episodes += eps
         return eps
 
-    def load_rollout(self, records, actions, logp, values, rewards, dones):
+    def load_rollout(self, records, actions, logp, values, rewards, dones, boot_values=None, boot_records=None):
         """Fill the [T, B] rollout buffers from given data (e.g. a reference
-        agent's memory, step-major) instead of running rollout()."""
+        agent's memory, step-major) instead of running rollout().  boot_values [B] /
+        boot_records [B, 64] (returns="selfplay" only): value and record of the position
+        after the last step; without them the horizon is a cut."""
+        if (boot_values is None) != (boot_records is None):
+            raise ValueError("load_rollout: boot_values and boot_records go together")
+        if boot_values is not None and self.returns_mode != "selfplay":
+            raise ValueError("load_rollout: a bootstrap is used by returns='selfplay' only")
         src = {"records": records, "actions": actions, "logp": logp, "values": values, "rewards": rewards,
                "dones": dones}
         for k, v in src.items():
+            v = torch.as_tensor(v)
+            if v.numel() != self.buf[k].numel():
+                raise ValueError(f"load_rollout: {k} has {v.numel()} elements, the buffer {self.buf[k].numel()}")
+            self.buf[k].copy_(v.reshape(self.buf[k].shape).to(self.buf[k].dtype))
+        self._boot = boot_values is not None
+        for k, v in (("boot_values", boot_values), ("boot_records", boot_records)) if self._boot else ():
             v = torch.as_tensor(v)
             if v.numel() != self.buf[k].numel():
                 raise ValueError(f"load_rollout: {k} has {v.numel()} elements, the buffer {self.buf[k].numel()}")
@@ -966,12 +1112,19 @@ class PPOTrainer:
         # the snapshot's host work first: it overlaps the rollout's last kernels instead of
         # idling the GPU between the return computation and the epochs (~0.17 ms)
         snap = self._snapshot() if fused_head else None
-        if self.returns_mode == "reference":
-            R = reference_returns(buf["rewards"], buf["dones"])
+        if self.returns_mode == "selfplay":
+            adv, R = selfplay_gae(buf["rewards"], buf["dones"], buf["records"], buf["values"],
+                                  buf["boot_values"] if self._boot else None,
+                                  buf["boot_records"] if self._boot else None, self.gamma, self.gae_lambda,
+                                  group=self.group)
+            adv, R = adv.reshape(-1), R.reshape(-1)
         else:
-            R = lane_returns(buf["rewards"], buf["dones"])
-        R = global_normalize(R.reshape(-1), self.group)
-        adv = R - buf["values"].reshape(-1)
+            if self.returns_mode == "reference":
+                R = reference_returns(buf["rewards"], buf["dones"])
+            else:
+                R = lane_returns(buf["rewards"], buf["dones"])
+            R = global_normalize(R.reshape(-1), self.group)
+            adv = R - buf["values"].reshape(-1)
         recs = buf["records"].reshape(-1, 64)
         acts = buf["actions"].reshape(-1)
         old = buf["logp"].reshape(-1)
@@ -1256,7 +1409,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--metrics", default=None)
     ap.add_argument("--save", default=None)
-    ap.add_argument("--returns", default="lane", choices=["lane", "reference"])
+    ap.add_argument("--returns", default="lane", choices=list(RETURNS_MODES))
+    ap.add_argument("--gae-lambda", type=float, default=0.95, help="GAE's lambda (--returns selfplay only)")
+    ap.add_argument("--gamma", type=float, default=GAMMA, help="discount (--returns selfplay only)")
     ap.add_argument("--entropy-anneal", default="train", choices=["train", "train_single"])
     # periodic head-to-head evaluation of the current weights (PPOTrainer.evaluate, bgx.arena)
     ap.add_argument("--eval-every", type=int, default=0, help="evaluate after every N-th update (0: never)")
@@ -1278,7 +1433,8 @@ def main():
         else:
             dist.init_process_group(backend)
     tr = PPOTrainer(batch=args.batch, horizon=args.horizon, hidden=args.hidden, seed=args.seed,
-                    returns=args.returns, entropy_anneal=args.entropy_anneal)
+                    returns=args.returns, entropy_anneal=args.entropy_anneal, gae_lambda=args.gae_lambda,
+                    gamma=args.gamma)
     for u in range(args.updates):
         m = tr.iteration()
         m["update"] = u
