@@ -288,6 +288,28 @@ int bgx_two_ply_sel(bgx_engine* e, const float* vpacked_dev, int32_t hidden, flo
                     const uint8_t* lane_sel_dev, int32_t* best_out, float* bestq_out, float* q_out,
                     uint64_t* stats_host, void* stream);
 
+/* bgx_two_ply_sel behind a 1-ply move filter (DESIGN.md §5 "Move filter"; GNU Backgammon's
+ * move filter, which the reference's commented-out expect_minmax.py lacks): the 1-ply value
+ * V1(a) of every legal afterstate of the selected lanes (exactly bgx_one_ply_sel's values),
+ * then per lane, on the order-preserving integer encoding of the float bits,
+ *   rank(a) = #{b : V1(b) > V1(a)} + #{b < a : V1(b) == V1(a)}
+ *   a is kept iff rank(a) < top_k and (rank(a) == 0 or V1(a) >= fp32(V1best - margin))
+ * (margin = +inf: no threshold; margin = 0: the moves tied for best, top_k of them at most),
+ * and the 2-ply search runs on the kept afterstates only.  best_out = the move index of the
+ * first argmax of Q over the kept moves, bestq_out its Q; q_out[i][a] = Q(a) for a kept
+ * move -- bit for bit its Q in the full search -- and -inf for a legal move that is not kept
+ * (entries a >= n untouched); v1_out float[B][max_moves] (may be NULL) receives V1(a), a < n.
+ * With top_k >= max_moves and margin = +inf, best_out, bestq_out and q_out are those of
+ * bgx_two_ply_sel.  Unselected lanes: nothing is written; a lane without a legal move gets
+ * what bgx_two_ply_sel gives it.  stats_host (uint64[4], may be NULL) receives {leaves
+ * evaluated, (afterstate, roll) jobs, kept afterstates, candidate afterstates}.
+ * BGX_EINVAL for top_k < 1, margin < 0 or NaN (nothing is written), and whatever
+ * bgx_two_ply_sel rejects; BGX_ESTATE as there.  Synchronises the stream (sizes its
+ * workspace from the kept afterstate count). */
+int bgx_two_ply_topk(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float value_bias,
+                     const uint8_t* lane_sel_dev, int32_t top_k, float margin, int32_t* best_out,
+                     float* bestq_out, float* q_out, float* v1_out, uint64_t* stats_host, void* stream);
+
 /* ---- head-to-head arena (csrc/bg_engine.hip; bgx/arena.py) ----
  * Two players A and B play each other on the n lanes of an engine created with
  * auto_reset = 1 until every lane has finished games_per_lane games (the reference has no

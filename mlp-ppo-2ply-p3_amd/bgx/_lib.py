@@ -57,6 +57,7 @@ SIGNATURES = {
     "bgx_two_ply": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P]),
     "bgx_one_ply_sel": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P]),
     "bgx_two_ply_sel": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
+    "bgx_two_ply_topk": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
     "bgx_two_ply_timings": (ctypes.c_int, [_P, _P]),
     "bgx_arena_begin": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
     "bgx_arena_merge": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P]),

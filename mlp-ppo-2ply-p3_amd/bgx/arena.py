@@ -115,20 +115,24 @@ class OnePlyPlayer(_SearchPlayer):
 
 
 class TwoPlyPlayer(_SearchPlayer):
-    """2-ply expectimax over the 21 rolls, on the lanes it is on move in only; `totals`
-    sums the calls' work (leaves, jobs, afterstates)."""
+    """2-ply expectimax over the 21 rolls, on the lanes it is on move in only; `top_k` /
+    `margin`: behind the 1-ply move filter (search.two_ply); `totals` sums the calls' work
+    (leaves, jobs, searched afterstates, candidate afterstates)."""
     sync_free = False               # bgx_two_ply_sel sizes its workspace on the host
 
-    def __init__(self, net):
+    def __init__(self, net, top_k=None, margin=None):
         super().__init__(net)
-        self.totals = {"calls": 0, "leaves": 0, "jobs": 0, "afterstates": 0}
+        self.top_k, self.margin = top_k, margin
+        self.totals = {"calls": 0, "leaves": 0, "jobs": 0, "afterstates": 0, "candidates": 0}
 
     def act(self, eng, sel, step):
         from .search import two_ply
-        best, _, _, stats = two_ply(eng, self.vh, sel=sel, out=self._out(eng))
+        best, _, _, stats = two_ply(eng, self.vh, sel=sel, out=self._out(eng), top_k=self.top_k, margin=self.margin)
         self.totals["calls"] += 1
         for k, v in stats.items():
             self.totals[k] += v
+        if "candidates" not in stats:           # no filter: every candidate was searched
+            self.totals["candidates"] += stats["afterstates"]
         return best
 
 
@@ -247,8 +251,11 @@ def load_net(path: str, device):
     return net.to(device).eval()
 
 
-def make_player(kind: str, net, seed: int = 0):
-    """`net` None or the string "random": the uniformly random player (kind ignored)."""
+def make_player(kind: str, net, seed: int = 0, top_k=None, margin=None):
+    """`net` None or the string "random": the uniformly random player (kind ignored).
+    `top_k` / `margin`: the 2ply player's move filter (TwoPlyPlayer), no other kind's."""
+    if (top_k is not None or margin is not None) and (kind != "2ply" or net is None or net == "random"):
+        raise ValueError("top_k / margin (the move filter) belong to a 2ply player")
     if net is None or (isinstance(net, str) and net == "random"):
         return RandomPlayer(seed)
     if kind == "policy":
@@ -258,12 +265,30 @@ def make_player(kind: str, net, seed: int = 0):
     if kind == "1ply":
         return OnePlyPlayer(net)
     if kind == "2ply":
-        return TwoPlyPlayer(net)
+        return TwoPlyPlayer(net, top_k=top_k, margin=margin)
     raise ValueError(f"player kind must be one of {PLAYER_KINDS}, got {kind!r}")
 
 
+class _Parser(argparse.ArgumentParser):
+    """The move-filter options are an error for any player but a 2ply one with weights."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        for side in "ab":
+            top_k, margin = getattr(ns, f"top_k_{side}"), getattr(ns, f"margin_{side}")
+            if top_k is None and margin is None:
+                continue
+            if getattr(ns, f"player_{side}") != "2ply" or getattr(ns, side) == "random":
+                self.error(f"--top-k-{side} / --margin-{side} need --player-{side} 2ply with weights")
+            if top_k is not None and top_k < 1:
+                self.error(f"--top-k-{side} must be >= 1")
+            if margin is not None and not margin >= 0:
+                self.error(f"--margin-{side} must be >= 0")
+        return ns
+
+
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(prog="python -m bgx.arena", description="Play two players against each other.")
+    ap = _Parser(prog="python -m bgx.arena", description="Play two players against each other.")
     ap.add_argument("--a", required=True, help="player A: a state_dict file (PPOTrainer.save) or 'random'")
     ap.add_argument("--b", required=True, help="player B: a state_dict file or 'random'")
     ap.add_argument("--player-a", default="policy", choices=PLAYER_KINDS)
@@ -274,6 +299,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="env steps after which the match stops (unfinished lanes are reported)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dice", default="philox", choices=["philox", "mt", "shared"])
+    for side in "ab":
+        ap.add_argument(f"--top-k-{side}", type=int, default=None,
+                        help=f"player {side.upper()} (2ply only): search only its top-k 1-ply moves")
+        ap.add_argument(f"--margin-{side}", type=float, default=None,
+                        help=f"player {side.upper()} (2ply only): ... within this 1-ply value of its best move")
     return ap
 
 
@@ -283,8 +313,9 @@ def main(argv=None):
     dev = torch.device("cuda", torch.cuda.current_device())
     nets = [None if p == "random" else load_net(p, dev) for p in (args.a, args.b)]
     max_moves = min([n.action_head.out_features for n in nets if n is not None] + [500])
-    players = [make_player(k, n, seed=args.seed * 2 + 1 + i)
-               for i, (k, n) in enumerate(zip((args.player_a, args.player_b), nets))]
+    players = [make_player(k, n, seed=args.seed * 2 + 1 + i, top_k=tk, margin=mg)
+               for i, (k, n, tk, mg) in enumerate(zip((args.player_a, args.player_b), nets,
+                                                      (args.top_k_a, args.top_k_b), (args.margin_a, args.margin_b)))]
     arena = Arena(args.batch, args.games_per_lane, seed=args.seed, dice=args.dice, max_moves=max_moves, device=dev)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
@@ -293,6 +324,7 @@ def main(argv=None):
     res.update(a=args.a, b=args.b, player_a="random" if nets[0] is None else args.player_a,
                player_b="random" if nets[1] is None else args.player_b, batch=args.batch,
                games_per_lane=args.games_per_lane, max_steps=args.max_steps, seed=args.seed, seconds=dt,
+               top_k_a=args.top_k_a, top_k_b=args.top_k_b, margin_a=args.margin_a, margin_b=args.margin_b,
                games_per_s=res["games"] / dt if dt > 0 else 0.0,
                env_steps_per_s=res["steps"] * args.batch / dt if dt > 0 else 0.0)
     print(json.dumps(res), flush=True)

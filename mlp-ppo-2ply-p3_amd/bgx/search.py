@@ -80,11 +80,59 @@ def one_ply(eng: Engine, vh: ValueHead, want_values: bool = False, sel: torch.Te
     return (best, bestv, vals) if want_values else (best, bestv)
 
 
-def two_ply(eng: Engine, vh: ValueHead, want_q: bool = False, sel: torch.Tensor | None = None, out=None):
+def _ord_f32(v: torch.Tensor) -> torch.Tensor:
+    """The order-preserving integer encoding of fp32 bits (csrc/bg_search.hip ord_f32)."""
+    b = v.contiguous().view(torch.int32).to(torch.int64)
+    return torch.where(b >= 0, b, b ^ 0x7FFFFFFF)
+
+
+def move_filter_reference(v1, n, top_k: int, margin: float) -> torch.Tensor:
+    """The move filter's rule in plain torch (any device; the specification of the k_filter
+    kernel behind bgx_two_ply_topk): the bool kept mask [B, max_moves] of 1-ply values
+    v1 f32[B, max_moves] with n[B] legal moves per lane.  On the order-preserving integer
+    encoding of the float bits,
+        rank(a) = #{b : V1(b) > V1(a)} + #{b < a : V1(b) == V1(a)}
+        keep(a) = rank(a) < top_k and (rank(a) == 0 or V1(a) >= fp32(V1best - margin));
+    margin = inf: no threshold."""
+    v1 = torch.as_tensor(v1, dtype=torch.float32)
+    if v1.dim() != 2:
+        raise ValueError("move_filter_reference: v1 must be [B, max_moves]")
+    top_k, margin = int(top_k), float(margin)
+    if top_k < 1 or not margin >= 0.0:
+        raise ValueError(f"move_filter_reference: top_k {top_k} must be >= 1 and margin {margin} >= 0")
+    B, M = v1.shape
+    n = torch.as_tensor(n, device=v1.device).to(torch.int64).reshape(B)
+    idx = torch.arange(M, device=v1.device)
+    valid = idx[None, :] < n[:, None]
+    key = _ord_f32(v1)
+    # rank = position in the stable order by falling value (equal values: rising index);
+    # entries a >= n sort behind every legal move
+    order = torch.sort(torch.where(valid, -key, torch.full_like(key, 1 << 40)), dim=1, stable=True).indices
+    rank = torch.empty_like(order)
+    rank.scatter_(1, order, idx[None, :].expand(B, M).contiguous())
+    keep = valid & (rank < top_k)
+    if margin != float("inf") and M > 0:
+        vbest = torch.gather(v1, 1, order[:, :1])                       # rank 0 (unused where n = 0)
+        thr = _ord_f32(vbest - torch.tensor(margin, dtype=torch.float32, device=v1.device))
+        keep &= (rank == 0) | (key >= thr)
+    return keep
+
+
+def two_ply(eng: Engine, vh: ValueHead, want_q: bool = False, sel: torch.Tensor | None = None, out=None,
+            top_k: int | None = None, margin: float | None = None, want_v1: bool = False):
     """2-ply expectimax for every lane: returns (best int32[B], best Q f32[B],
-    Q f32[B, max_moves] or None, stats {leaves, jobs, afterstates}).  `sel` (uint8[B] on
-    the device): only lanes with sel != 0 form rows, are searched, written and counted in
-    the stats (bgx_two_ply_sel); `out` = (best, bestq, q or None) as in one_ply."""
+    Q f32[B, max_moves] or None, stats {leaves, jobs, afterstates}).  `sel`
+    (uint8[B] on the device): only lanes with sel != 0 form rows, are searched, written and
+    counted in the stats (bgx_two_ply_sel); `out` = (best, bestq, q or None) as in one_ply.
+
+    `top_k` / `margin`: the 1-ply move filter (bgx_two_ply_topk; move_filter_reference is its
+    rule): only the top_k best 1-ply moves within margin of the best are searched; best is
+    the first argmax of Q over them, Q of a legal move that was not searched is -inf, and
+    stats["afterstates"] counts the searched moves and the stats gain "candidates", all the
+    legal ones (an unfiltered call searches every candidate and reports no such entry).
+    margin None = inf, top_k None with a margin = max_moves.  want_v1 (the filtered entry
+    point with either option or neither): a fifth result, the 1-ply values f32[B, max_moves]
+    (NaN where nothing was written)."""
     L = _lib.load()
     B, dev = eng.batch, eng.device
     _check_sel(eng, sel)
@@ -94,10 +142,19 @@ def two_ply(eng: Engine, vh: ValueHead, want_q: bool = False, sel: torch.Tensor 
         best = torch.empty(B, dtype=torch.int32, device=dev)
         bestq = torch.empty(B, dtype=torch.float32, device=dev)
         q = torch.full((B, eng.max_moves), float("nan"), dtype=torch.float32, device=dev) if want_q else None
-    stats = (ctypes.c_uint64 * 3)()
-    check(L.bgx_two_ply_sel(eng._h, _ptr(vh.packed), vh.hidden, vh.bias, _ptr(sel), _ptr(best), _ptr(bestq), _ptr(q),
-                            ctypes.cast(stats, ctypes.c_void_p), _stream(dev)), "bgx_two_ply_sel")
-    return best, bestq, q, {"leaves": int(stats[0]), "jobs": int(stats[1]), "afterstates": int(stats[2])}
+    if top_k is None and margin is None and not want_v1:
+        stats = (ctypes.c_uint64 * 3)()
+        check(L.bgx_two_ply_sel(eng._h, _ptr(vh.packed), vh.hidden, vh.bias, _ptr(sel), _ptr(best), _ptr(bestq),
+                                _ptr(q), ctypes.cast(stats, ctypes.c_void_p), _stream(dev)), "bgx_two_ply_sel")
+        return best, bestq, q, {"leaves": int(stats[0]), "jobs": int(stats[1]), "afterstates": int(stats[2])}
+    v1 = torch.full((B, eng.max_moves), float("nan"), dtype=torch.float32, device=dev) if want_v1 else None
+    stats = (ctypes.c_uint64 * 4)()
+    check(L.bgx_two_ply_topk(eng._h, _ptr(vh.packed), vh.hidden, vh.bias, _ptr(sel),
+                             eng.max_moves if top_k is None else int(top_k),
+                             float("inf") if margin is None else float(margin), _ptr(best), _ptr(bestq), _ptr(q),
+                             _ptr(v1), ctypes.cast(stats, ctypes.c_void_p), _stream(dev)), "bgx_two_ply_topk")
+    st = {"leaves": int(stats[0]), "jobs": int(stats[1]), "afterstates": int(stats[2]), "candidates": int(stats[3])}
+    return (best, bestq, q, st, v1) if want_v1 else (best, bestq, q, st)
 
 
 def two_ply_timings(eng: Engine):

@@ -1376,11 +1376,12 @@ class PPOTrainer:
         torch.save(self.net.state_dict(), path)
 
     def evaluate(self, opponent="random", player: str = "policy", batch: int = 4096, games_per_lane: int = 2,
-                 max_steps: int = 4000, opponent_player: str = "policy"):
+                 max_steps: int = 4000, opponent_player: str = "policy", top_k=None, margin=None):
         """The current weights as player A of a head-to-head match (bgx.arena) against
         `opponent`: "random", a PolicyNet or the path of a saved state_dict (playing as
         `opponent_player`).  `player`: how A decides ("policy" sample, "greedy" argmax,
-        "1ply", "2ply").  Returns the arena's result dict.  Training is not disturbed: the
+        "1ply", "2ply"; `top_k` / `margin`: the 2ply player's move filter, search.two_ply).
+        Returns the arena's result dict.  Training is not disturbed: the
         match runs on an engine and seeds of its own (the k-th evaluation of a trainer is
         seeded from (seed, k)), the players pack the weights into buffers of their own, and
         neither the trainer's engines, step counter, packed weights or captured graphs nor
@@ -1394,7 +1395,7 @@ class PPOTrainer:
         base = (self.seed * 1_000_003 + 15_485_863 * (k + 1)) & (2**63 - 1)
         if isinstance(opponent, str) and opponent != "random":
             opponent = AR.load_net(opponent, self.dev)
-        a = AR.make_player(player, self.net, seed=base + 1)
+        a = AR.make_player(player, self.net, seed=base + 1, top_k=top_k, margin=margin)
         b = AR.make_player(opponent_player, opponent, seed=base + 2)
         ar = AR.Arena(batch, games_per_lane, seed=base, dice="philox", max_moves=self.A, device=self.dev)
         return ar.play(a, b, max_steps=max_steps)
@@ -1420,7 +1421,13 @@ def main():
     ap.add_argument("--eval-max-steps", type=int, default=4000)
     ap.add_argument("--eval-opponent", default="random", help="'random' or a saved state_dict")
     ap.add_argument("--eval-player", default="policy", choices=["policy", "greedy", "1ply", "2ply"])
+    ap.add_argument("--eval-top-k", type=int, default=None,
+                    help="--eval-player 2ply: search only the top-k 1-ply moves (the move filter)")
+    ap.add_argument("--eval-margin", type=float, default=None,
+                    help="--eval-player 2ply: ... within this 1-ply value of the best move")
     args = ap.parse_args()
+    if (args.eval_top_k is not None or args.eval_margin is not None) and args.eval_player != "2ply":
+        ap.error("--eval-top-k / --eval-margin need --eval-player 2ply")
     ws = int(os.environ.get("WORLD_SIZE", "1"))
     if ws > 1 and args.eval_every > 0:
         ap.error("--eval-every needs a single rank (multi-rank evaluation is not implemented)")
@@ -1440,7 +1447,8 @@ def main():
         m["update"] = u
         if args.eval_every > 0 and (u + 1) % args.eval_every == 0:
             ev = tr.evaluate(args.eval_opponent, player=args.eval_player, batch=args.eval_batch,
-                             games_per_lane=args.eval_games, max_steps=args.eval_max_steps)
+                             games_per_lane=args.eval_games, max_steps=args.eval_max_steps,
+                             top_k=args.eval_top_k, margin=args.eval_margin)
             m.update({"eval_win_rate": ev["win_rate_a"], "eval_ppg": ev["ppg_a"], "eval_games": ev["games"],
                       "eval_unfinished": ev["unfinished_lanes"]})
         if tr.rank == 0:

@@ -29,6 +29,9 @@
 // 1-ply: k_scan, k_expand, k_rows (row keys), k_eval_rows (V per row), k_one_ply_reduce.
 // bgx_one_ply_sel / bgx_two_ply_sel run the same pipelines over the rows of the selected
 // lanes only (lane_selected): a player in a match acts where it is on move.
+// bgx_two_ply_topk: the 1-ply rows' V, k_filter (the top_k best moves within a margin of the
+// best, per lane), k_expand_kept (row -> lane, row -> move), then the 2-ply pipeline on
+// the kept rows alone (DESIGN.md §5 "Move filter").
 // The reference's filter_full_moves_by_max_submoves (get_all_moves.py:73-94) is
 // applied by the evaluator: a leaf counts iff its sub-move count equals the
 // job's final maximum (written at job end), which is exactly "first insertion
@@ -666,17 +669,18 @@ __global__ __launch_bounds__(64) void k_enum_slow(S2 S, uint4* tables) {
 // A row whose (lane, move index) is not a legal move of the lane as it stands now -- the
 // lanes changed between k_scan and this kernel, which the engine's stream ordering rules
 // out (bgx.h) -- sets *bad and becomes the empty board's row instead of reading past the
-// lane's move list.
+// lane's move list.  row_move (the move filter's kept rows, k_expand_kept; may be null):
+// the move index of each row; null: row a of a lane is its move a.
 __global__ __launch_bounds__(256) void k_rows(Args A, const int32_t* row_lane, const int32_t* lane_off,
-                                              const int64_t* nrows, uint8_t* rowrec, uint4* rowside, uint4* rowkey,
-                                              int32_t* bad) {
+                                              const int32_t* row_move, const int64_t* nrows, uint8_t* rowrec,
+                                              uint4* rowside, uint4* rowkey, int32_t* bad) {
     const int l = lane_id();
     const int nw = gridDim.x * (blockDim.x >> 6);
     const int rows = (int)*nrows;
     for (int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); row < rows; row += nw) {
         const int lane_g = row_lane[row];
         bool ok = lane_g >= 0 && lane_g < A.B;
-        const int a = ok ? row - lane_off[lane_g] : 0;
+        const int a = ok ? (row_move ? row_move[row] : row - lane_off[lane_g]) : 0;
         int bv = ok ? load_rec(A, lane_g) : 0;
         if (ok) {
             const int n = rd(bv, R_NM0) | (rd(bv, R_NM1) << 8);
@@ -1396,8 +1400,9 @@ __device__ __forceinline__ bool lane_selected(const uint8_t* sel, int i) { retur
 // a lane's legal-move count (0 for an unselected lane), held inside the scanned row range
 // [0, total) (equal to the record's count whenever the lanes did not change since k_scan:
 // bgx.h stream ordering)
-__device__ __forceinline__ int row_count(const uint8_t* rr, bool selected, int32_t off, int64_t total) {
-    const int n = selected ? (int)rr[R_NM0] | ((int)rr[R_NM1] << 8) : 0;
+__device__ __forceinline__ int row_count(const uint8_t* rr, bool selected, int32_t off, int64_t total,
+                                         const int32_t* kept = nullptr) {
+    const int n = selected ? (kept ? *kept : (int)rr[R_NM0] | ((int)rr[R_NM1] << 8)) : 0;
     const int64_t room = off >= 0 && off <= total ? total - off : 0;
     return n < room ? n : (int)room;
 }
@@ -1426,25 +1431,30 @@ __global__ __launch_bounds__(256) void k_one_ply_reduce(Args A, const uint8_t* s
 }
 
 // Q(a) = sum_r p_r minv[a][r] (fp32 FMA, r in roll order), first argmax; one wave per lane.
+// The move filter (kept, row_move non-null; k_filter, k_expand_kept): the lane's kept[i]
+// rows are its kept moves in ascending move order, row j is move row_move[lane_off[i] + j],
+// so the first argmax over the rows is the first argmax over the kept moves.
 __global__ __launch_bounds__(256) void k_two_ply_reduce(Args A, const uint8_t* sel, const int32_t* lane_off,
-                                                        const int64_t* total, const int32_t* minv, int32_t* best,
+                                                        const int64_t* total, const int32_t* minv,
+                                                        const int32_t* kept, const int32_t* row_move, int32_t* best,
                                                         float* bestq, float* qout) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= A.B || !lane_selected(sel, i)) return;
     const uint8_t* rr = A.lanes + (size_t)i * 64;
-    const int n = row_count(rr, true, lane_off[i], *total);
+    const int n = row_count(rr, true, lane_off[i], *total, kept ? kept + i : nullptr);
+    const int32_t* rm = row_move ? row_move + lane_off[i] : nullptr;
     int ba;
     float bq;
-    wave_first_argmax(n, [&](int a) {
-        const int32_t* mv = minv + ((size_t)lane_off[i] + a) * 21;
+    wave_first_argmax(n, [&](int j) {
+        const int32_t* mv = minv + ((size_t)lane_off[i] + j) * 21;
         float q = 0.0f;
         for (int r = 0; r < 21; ++r)
             q = fmaf(kRoll0[r] == kRoll1[r] ? 1.0f / 36.0f : 2.0f / 36.0f, unord_f32(mv[r]), q);
-        if (qout) qout[(size_t)i * A.max_moves + a] = q;
+        if (qout) qout[(size_t)i * A.max_moves + (rm ? rm[j] : j)] = q;
         return q;
     }, ba, bq);
     if (lane_id() == 0) {
-        best[i] = ba;
+        best[i] = rm && n ? rm[ba] : ba;
         if (bestq) bestq[i] = bq;
     }
 }
@@ -1517,16 +1527,21 @@ __global__ __launch_bounds__(1024) void k_value_pack16(const float* W1, const fl
 // PLAYER2's (each group in lane order), so the enumerators' pool output -- every wave walks
 // rows a grid stride apart -- holds long runs of one replier, which the factored evaluator
 // needs per leaf pair (eval_leaves_fact).  An unselected lane (lane_selected) counts 0 rows.
+// kept (the move filter, k_filter; may be null): the lanes' row counts instead of the
+// records' legal-move counts.
 __global__ __launch_bounds__(1024) void k_scan(Args A, const uint8_t* sel, int32_t* lane_off, int64_t* total,
-                                               int by_mover) {
+                                               int by_mover, const int32_t* kept) {
     __shared__ int64_t part[2][1024];
     const int t = threadIdx.x;
     const int per = (A.B + 1023) / 1024;
     const int lo = t * per, hi = min(A.B, lo + per);
     int64_t sum[2] = {0, 0};
+    auto count = [&](const uint8_t* rr, int i) {
+        return lane_selected(sel, i) ? (kept ? kept[i] : (int)rr[R_NM0] | ((int)rr[R_NM1] << 8)) : 0;
+    };
     for (int i = lo; i < hi; ++i) {
         const uint8_t* rr = A.lanes + (size_t)i * 64;
-        sum[by_mover ? rr[R_CUR] & 1 : 0] += lane_selected(sel, i) ? (int)rr[R_NM0] | ((int)rr[R_NM1] << 8) : 0;
+        sum[by_mover ? rr[R_CUR] & 1 : 0] += count(rr, i);
     }
     part[0][t] = sum[0];
     part[1][t] = sum[1];
@@ -1543,7 +1558,7 @@ __global__ __launch_bounds__(1024) void k_scan(Args A, const uint8_t* sel, int32
         const uint8_t* rr = A.lanes + (size_t)i * 64;
         const int g = by_mover ? rr[R_CUR] & 1 : 0;
         lane_off[i] = (int32_t)run[g];
-        run[g] += lane_selected(sel, i) ? (int)rr[R_NM0] | ((int)rr[R_NM1] << 8) : 0;
+        run[g] += count(rr, i);
     }
     if (t == 1023) *total = part[0][1023] + part[1][1023];
 }
@@ -1557,6 +1572,70 @@ __global__ __launch_bounds__(256) void k_expand(Args A, const uint8_t* sel, cons
     const int o = lane_off[i];
     const int n = row_count(A.lanes + (size_t)i * 64, lane_selected(sel, i), o, *total);
     for (int a = lane_id(); a < n; a += 64) row_lane[o + a] = i;
+}
+
+// The 1-ply move filter of bgx_two_ply_topk (DESIGN.md §5 "Move filter"), one wave per
+// lane over its n 1-ply values v1 = vrow + off1[i] (the 1-ply pipeline's row layout), on the
+// order-preserving integer encoding (ord_f32):
+//   rank(a) = #{b : v1[b] > v1[a]} + #{b < a : v1[b] == v1[a]}
+//   keep(a) = rank(a) < top_k && (rank(a) == 0 || v1[a] >= fp32(v1best - margin))
+// Rank by counting: thread j ranks moves j, j + 64, ... against all n values (a uniform
+// address per compare; <= 500 * 8 compares per thread).  The kept move indices go to
+// kept_move[off1[i] ..] in ascending move order (ballot + prefix popcount per 64-move
+// chunk), their count to kept[i] (0 for an unselected lane); q_out of a legal move that is
+// not kept becomes -inf, v1_out (may be null) receives v1.
+__global__ __launch_bounds__(256) void k_filter(Args A, const uint8_t* sel, const int32_t* off1, const int64_t* total1,
+                                                const float* vrow, int top_k, float margin, int32_t* kept,
+                                                int32_t* kept_move, float* qout, float* v1out) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.B) return;
+    const int l = lane_id();
+    const bool selected = lane_selected(sel, i);
+    const int off = off1[i];
+    const int n = min(row_count(A.lanes + (size_t)i * 64, selected, off, *total1), A.max_moves);
+    const float* v = vrow + off;
+    int vmax = (int)0x80000000;
+    for (int a = l; a < n; a += 64) vmax = max(vmax, ord_f32(v[a]));
+    #pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) vmax = max(vmax, __shfl_xor(vmax, o));
+    // margin = +inf: no threshold (and no inf - inf)
+    const int thr = margin == INFINITY ? (int)0x80000000 : ord_f32(unord_f32(vmax) - margin);
+    int count = 0;
+    for (int base = 0; base < n; base += 64) {         // uniform trip count: the ballot needs every thread
+        const int a = base + l;
+        bool keep = false;
+        if (a < n) {
+            const float x = v[a];
+            const int xa = ord_f32(x);
+            int rank = 0;
+            for (int b = 0; b < n; ++b) {
+                const int xb = ord_f32(v[b]);
+                rank += (xb > xa || (xb == xa && b < a)) ? 1 : 0;
+            }
+            keep = rank < top_k && (rank == 0 || xa >= thr);
+            if (v1out) v1out[(size_t)i * A.max_moves + a] = x;
+            if (!keep && qout) qout[(size_t)i * A.max_moves + a] = -INFINITY;
+        }
+        const uint64_t m = __ballot(keep);
+        if (keep) kept_move[off + count + __popcll(m & ((1ull << l) - 1ull))] = a;
+        count += __popcll(m);
+    }
+    if (l == 0) kept[i] = count;
+}
+
+// row -> lane and row -> move maps of the kept rows (k_filter), one wave per lane: row
+// lane_off[i] + j is the lane's j-th kept move.
+__global__ __launch_bounds__(256) void k_expand_kept(Args A, const uint8_t* sel, const int32_t* lane_off,
+                                                     const int64_t* total, const int32_t* kept, const int32_t* off1,
+                                                     const int32_t* kept_move, int32_t* row_lane, int32_t* row_move) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.B) return;
+    const int o = lane_off[i];
+    const int n = row_count(A.lanes + (size_t)i * 64, lane_selected(sel, i), o, *total, kept + i);
+    for (int j = lane_id(); j < n; j += 64) {
+        row_lane[o + j] = i;
+        row_move[o + j] = kept_move[off1[i] + j];
+    }
 }
 
 }  // namespace
@@ -1621,6 +1700,59 @@ static int eval_grid(const bgx_engine* e, K kernel, int NT) {
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// The 1-ply row pipeline on stream s, inside the caller's EngineUse: V of every legal
+// afterstate of the selected lanes, lane i's at vrow[lane_off[i] ..] in move order.
+// bgx_one_ply_sel reduces them to a choice; bgx_two_ply_topk filters its candidates by them
+// (with_kept: room for k_filter's kept counts and kept move lists).
+struct OnePlyRows {
+    int32_t* lane_off;       // [B] first row of each lane
+    int64_t* total;          // the row count (on the device)
+    float* vrow;             // [rows] V per row
+    int32_t* kept;           // [B], with_kept only
+    int32_t* kept_move;      // [B x max_moves], with_kept only
+};
+static int one_ply_rows(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                        bool with_kept, hipStream_t s, OnePlyRows& out) {
+    Args& A = e->a;
+    const size_t B = (size_t)A.B, R = B * (size_t)A.max_moves;
+    // [lane_off B i32][row total i64][row_lane R i32][rowside R][rowkey R][vrow R f32]: sized for
+    // the worst case, so the pass runs without a host sync (the row count stays on the device);
+    // the move filter's [kept B i32][kept_move R i32] after them
+    const size_t o_tot = align256(B * 4), o_rl = o_tot + 256, o_side = align256(o_rl + R * 4),
+                 o_key = align256(o_side + R * 16), o_v = align256(o_key + R * 16), o_kept = align256(o_v + R * 4),
+                 o_km = align256(o_kept + B * 4), need = with_kept ? align256(o_km + R * 4) : o_kept;
+    if (e->oneply_ws_bytes < need) {
+        SCK(hipStreamSynchronize(s));
+        if (e->oneply_ws) SCK(hipFree(e->oneply_ws));
+        e->oneply_ws = nullptr;
+        e->oneply_ws_bytes = 0;
+        SCK(hipMalloc(&e->oneply_ws, need));
+        e->oneply_ws_bytes = need;
+    }
+    char* ws = (char*)e->oneply_ws;
+    int32_t* lane_off = (int32_t*)ws;
+    int64_t* total = (int64_t*)(ws + o_tot);
+    int32_t* row_lane = (int32_t*)(ws + o_rl);
+    uint4* rowside = (uint4*)(ws + o_side);
+    uint4* rowkey = (uint4*)(ws + o_key);
+    float* vrow = (float*)(ws + o_v);
+    const int NT = value_tiles16(hidden);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, sel, lane_off, total, 0, (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, total, row_lane);
+    // ~20 legal moves per lane on average: one wave per ~5 rows at B = 4,096
+    const size_t gr = B * 6 < 16384 ? (B * 6 > 64 ? B * 6 : 64) : 16384;
+    hipLaunchKernelGGL(k_rows, dim3((unsigned)gr), dim3(256), 0, s, A, row_lane, lane_off, (const int32_t*)nullptr, total,
+                       (uint8_t*)nullptr, rowside, rowkey, A.err);
+    const EvalRowsFn kr = eval_rows_kernel(NT);
+    const EvalRowsArgs E{rowkey, rowside, total, vrow, (const uint4*)(vpacked + 4), vpacked + 4 + kKB * slices(NT) * 64 * 4,
+                         value_bias};
+    hipLaunchKernelGGL(kr, dim3(eval_grid(e, kr, NT)), dim3(64 * eval_waves(NT)), 0, s, E);
+    SCK(hipGetLastError());
+    out = OnePlyRows{lane_off, total, vrow, with_kept ? (int32_t*)(ws + o_kept) : nullptr,
+                     with_kept ? (int32_t*)(ws + o_km) : nullptr};
+    return BGX_OK;
+}
+
 extern "C" {
 
 int bgx_value_packed_size(int32_t hidden) {
@@ -1651,51 +1783,32 @@ int bgx_one_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float v
     hipStream_t s = (hipStream_t)stream;
     EngineUse use(e, s);
     SCK(use.err);
-    Args& A = e->a;
-    const size_t B = (size_t)A.B, R = B * (size_t)A.max_moves;
-    // [lane_off B i32][row total i64][row_lane R i32][rowside R][rowkey R][vrow R f32]: sized for
-    // the worst case, so the pass runs without a host sync (the row count stays on the device)
-    const size_t o_tot = align256(B * 4), o_rl = o_tot + 256, o_side = align256(o_rl + R * 4),
-                 o_key = align256(o_side + R * 16), o_v = align256(o_key + R * 16), need = align256(o_v + R * 4);
-    if (e->oneply_ws_bytes < need) {
-        SCK(hipStreamSynchronize(s));
-        if (e->oneply_ws) SCK(hipFree(e->oneply_ws));
-        e->oneply_ws = nullptr;
-        e->oneply_ws_bytes = 0;
-        SCK(hipMalloc(&e->oneply_ws, need));
-        e->oneply_ws_bytes = need;
-    }
-    char* ws = (char*)e->oneply_ws;
-    int32_t* lane_off = (int32_t*)ws;
-    int64_t* total = (int64_t*)(ws + o_tot);
-    int32_t* row_lane = (int32_t*)(ws + o_rl);
-    uint4* rowside = (uint4*)(ws + o_side);
-    uint4* rowkey = (uint4*)(ws + o_key);
-    float* vrow = (float*)(ws + o_v);
-    const int NT = value_tiles16(hidden);
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, sel, lane_off, total, 0);
-    hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, total, row_lane);
-    // ~20 legal moves per lane on average: one wave per ~5 rows at B = 4,096
-    const size_t gr = B * 6 < 16384 ? (B * 6 > 64 ? B * 6 : 64) : 16384;
-    hipLaunchKernelGGL(k_rows, dim3((unsigned)gr), dim3(256), 0, s, A, row_lane, lane_off, total, nullptr, rowside,
-                       rowkey, A.err);
-    const EvalRowsFn kr = eval_rows_kernel(NT);
-    const EvalRowsArgs E{rowkey, rowside, total, vrow, (const uint4*)(vpacked + 4), vpacked + 4 + kKB * slices(NT) * 64 * 4,
-                         value_bias};
-    hipLaunchKernelGGL(kr, dim3(eval_grid(e, kr, NT)), dim3(64 * eval_waves(NT)), 0, s, E);
-    hipLaunchKernelGGL(k_one_ply_reduce, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, total, vrow,
-                       best_out, bestv_out, values_out);
+    OnePlyRows r;
+    const int rc = one_ply_rows(e, vpacked, hidden, value_bias, sel, false, s, r);
+    if (rc != BGX_OK) return rc;
+    hipLaunchKernelGGL(k_one_ply_reduce, dim3((e->a.B + 3) / 4), dim3(256), 0, s, e->a, sel, r.lane_off, r.total,
+                       r.vrow, best_out, bestv_out, values_out);
     SCK(hipGetLastError());
     return BGX_OK;
 }
 
-int bgx_two_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, int32_t* best_out,
-                float* bestq_out, float* q_out, uint64_t* stats_host, void* stream) {
-    return bgx_two_ply_sel(e, vpacked, hidden, value_bias, nullptr, best_out, bestq_out, q_out, stats_host, stream);
-}
+}  // extern "C"
 
-int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
-                    int32_t* best_out, float* bestq_out, float* q_out, uint64_t* stats_host, void* stream) {
+// bgx_two_ply_topk's move filter (null: every legal afterstate is a row, bgx_two_ply_sel)
+struct MoveFilter {
+    int32_t top_k;
+    float margin;
+    float* v1_out;
+};
+
+// The 2-ply pipeline of bgx_two_ply_sel and bgx_two_ply_topk.  With a filter the rows are
+// the kept moves only: the 1-ply values (one_ply_rows), k_filter's kept counts and move
+// lists, the row layout scanned from the kept counts, and the row -> move map (row_move)
+// for k_rows and the reduce; enumerators, pool, tiers, retry rounds and evaluator see
+// nothing but a smaller row set.
+static int two_ply_search(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                          const MoveFilter* filter, int32_t* best_out, float* bestq_out, float* q_out,
+                          uint64_t* stats_host, void* stream) {
     if (!e || !vpacked || !best_out || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
     SCK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1703,6 +1816,16 @@ int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float v
     SCK(use.err);
     Args& A = e->a;
     const size_t B = (size_t)A.B;
+    OnePlyRows cand{};
+    int64_t cand64 = 0;                               // candidate afterstates (stats)
+    if (filter) {
+        const int rc1 = one_ply_rows(e, vpacked, hidden, value_bias, sel, true, s, cand);
+        if (rc1 != BGX_OK) return rc1;
+        hipLaunchKernelGGL(k_filter, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, cand.lane_off, cand.total, cand.vrow,
+                           filter->top_k, filter->margin, cand.kept, cand.kept_move, q_out, filter->v1_out);
+        SCK(hipGetLastError());
+        SCK(hipMemcpyAsync(&cand64, cand.total, 8, hipMemcpyDeviceToHost, s));     // read after the scan's sync
+    }
     // workspace head: [lane_off B i32][counters 256 B][overflow queues]
     struct Ctr {
         int64_t rows;
@@ -1726,7 +1849,8 @@ int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float v
     if (rc != BGX_OK) return rc;
     char* ws = (char*)e->search_ws;
     SCK(hipMemsetAsync(ws + o_ctr, 0, 256, s));
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, sel, (int32_t*)ws, (int64_t*)(ws + o_ctr), 1);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, sel, (int32_t*)ws, (int64_t*)(ws + o_ctr), 1,
+                       (const int32_t*)cand.kept);
     SCK(hipGetLastError());
     int64_t rows64 = 0;
     SCK(hipMemcpyAsync(&rows64, ws + o_ctr, 8, hipMemcpyDeviceToHost, s));
@@ -1735,13 +1859,14 @@ int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float v
     if (jobs64 >= (int64_t)0x1FFFFFFF) return BGX_EINVAL;     // job ids are 29-bit pool tags
     const int rows = (int)rows64, jobs = (int)jobs64;
     // [row_lane rows][rowrec rows*64][rowside rows*16][minv jobs*4][maxlen jobs][list jobs*4][retry jobs*4]
-    // [rowpart rows*16*slices f32]
+    // [rowpart rows*16*slices f32][row_move rows i32, with a filter]
     const int NT = value_tiles16(hidden);
     const size_t o_rl = head, o_rec = align256(o_rl + (size_t)rows * 4), o_side = align256(o_rec + (size_t)rows * 64),
                  o_minv = align256(o_side + (size_t)rows * 16), o_ml = align256(o_minv + (size_t)jobs * 4),
                  o_list = align256(o_ml + (size_t)jobs), o_retry = align256(o_list + (size_t)jobs * 4),
                  o_rp = align256(o_retry + (size_t)jobs * 4),
-                 need = align256(o_rp + (size_t)rows * 16 * slices(NT) * 4);
+                 o_rm = align256(o_rp + (size_t)rows * 16 * slices(NT) * 4),
+                 need = filter ? align256(o_rm + (size_t)rows * 4) : o_rm;
     if (e->search_ws_bytes < need) {
         // keep the head (lane_off, counters) across the regrow
         void* nw = nullptr;
@@ -1763,13 +1888,18 @@ int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float v
     int32_t* list = (int32_t*)(ws + o_list);
     int32_t* retry = (int32_t*)(ws + o_retry);
     float* rowpart = (float*)(ws + o_rp);
+    int32_t* row_move = filter ? (int32_t*)(ws + o_rm) : nullptr;
 
     if (rows > 0) {
-        hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows, row_lane);
+        if (filter)
+            hipLaunchKernelGGL(k_expand_kept, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows,
+                               cand.kept, cand.lane_off, cand.kept_move, row_lane, row_move);
+        else
+            hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows, row_lane);
         SCK(hipMemsetAsync(minv, 0x7F, (size_t)jobs * 4, s));
         SCK(hipMemsetAsync(maxlen, 0xFF, (size_t)jobs, s));
         hipLaunchKernelGGL(k_rows, dim3((rows + 3) / 4 < 16384 ? (rows + 3) / 4 : 16384), dim3(256), 0, s, A, row_lane,
-                           lane_off, &ctr->rows, rowrec, rowside, nullptr, &ctr->bad);
+                           lane_off, (const int32_t*)row_move, &ctr->rows, rowrec, rowside, (uint4*)nullptr, &ctr->bad);
         SCK(hipGetLastError());
         const bool barrow = bgx_dbg_int("BGX_2PLY_BARROW", 1) != 0;      // tests: 0 = the bar rows per job
         S2 S{rowrec, 0, rows, nullptr, nullptr, &ctr->cursor, 0ull, maxlen, &ctr->leaves,
@@ -1944,7 +2074,7 @@ int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float v
         }
     }
     hipLaunchKernelGGL(k_two_ply_reduce, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows, minv,
-                       best_out, bestq_out, q_out);
+                       (const int32_t*)cand.kept, (const int32_t*)row_move, best_out, bestq_out, q_out);
     SCK(hipGetLastError());
     if (stats_host) {
         unsigned long long lv = 0;
@@ -1953,8 +2083,30 @@ int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float v
         stats_host[0] = lv;
         stats_host[1] = (uint64_t)jobs64;
         stats_host[2] = (uint64_t)rows64;
+        if (filter) stats_host[3] = (uint64_t)cand64;
     }
     return BGX_OK;
+}
+
+extern "C" {
+
+int bgx_two_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, int32_t* best_out,
+                float* bestq_out, float* q_out, uint64_t* stats_host, void* stream) {
+    return two_ply_search(e, vpacked, hidden, value_bias, nullptr, nullptr, best_out, bestq_out, q_out, stats_host,
+                          stream);
+}
+
+int bgx_two_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                    int32_t* best_out, float* bestq_out, float* q_out, uint64_t* stats_host, void* stream) {
+    return two_ply_search(e, vpacked, hidden, value_bias, sel, nullptr, best_out, bestq_out, q_out, stats_host, stream);
+}
+
+int bgx_two_ply_topk(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                     int32_t top_k, float margin, int32_t* best_out, float* bestq_out, float* q_out, float* v1_out,
+                     uint64_t* stats_host, void* stream) {
+    if (top_k < 1 || !(margin >= 0.0f)) return BGX_EINVAL;       // !(>=): NaN too
+    const MoveFilter f{top_k, margin, v1_out};
+    return two_ply_search(e, vpacked, hidden, value_bias, sel, &f, best_out, bestq_out, q_out, stats_host, stream);
 }
 
 #ifdef BGX_COUNTERS
