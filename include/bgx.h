@@ -202,7 +202,8 @@ int bgx_copy_regions(const bgx_region* regions, int32_t n, int32_t workgroups, v
 int bgx_host_device_ptr(void* host_ptr, void** dev_ptr_out);
 
 /* Sticky device error word (bit 0: a position overflowed the slow-path dedup
- * table; bit 1: bgx_one_ply found a lane changed under it, see "Stream ordering").
+ * table; bit 1: bgx_one_ply found a lane changed under it, see "Stream ordering";
+ * bit 2: bgx_engine_set_starts found an invalid start record).
  * Synchronises the engine's device. */
 int bgx_engine_error(bgx_engine* e, int32_t* err_out);
 
@@ -353,6 +354,58 @@ int bgx_arena_advance(const uint8_t* records_dev, const uint8_t* done_dev, const
  * count (bytes 60-61); 0 when the lane has no legal move.  Graph-capturable. */
 int bgx_random_act(const uint8_t* records_dev, int32_t n, uint64_t seed, uint32_t step, int32_t* act_out,
                    void* stream);
+
+/* ---- start positions (no counterpart in the reference, whose env always resets to the
+ * opening, backgammon_env.py:78-113) ----
+ * starts_dev uint8[batch][64] in the lane-record layout (16-byte aligned), or NULL:
+ * standard openings again.  The engine keeps a copy of its own; the call is ordered on
+ * `stream` like every engine call and does not synchronise the host.  Lanes are not touched
+ * by the call: the table takes effect at each lane's next reset, whichever path triggers it
+ * (bgx_reset, masked or not; the auto-reset inside a step; the reset step of an
+ * auto_reset = 0 engine).  A reset of lane i with a valid start record s: board (bytes
+ * 0..51) and mover (byte 52) become s's, game_over 0, scores and the match flag as in the
+ * standard reset.  The roll is s's bytes 53, 54 when both are in 1..6 (no die is drawn);
+ * when both are 0 the lane draws two dice from its own stream as a mid-game roll does
+ * (doubles allowed, no starter draw, no rejection).  Bytes 55..63 of s are ignored.
+ * A record is valid when each side's points + bar + off == 15, no point is held by both
+ * sides, both off counts are < 15, the mover is 0 or 1 and the roll is (0, 0) or two dice
+ * in 1..6.  An invalid record sets bit 2 of the error word (bgx_engine_error) and its lane
+ * resets to the standard opening.  BGX_EINVAL for a BGX_DICE_MT_SHARED engine (one stream
+ * in lane order mirrors the reference's vector env, which has no start positions). */
+int bgx_engine_set_starts(bgx_engine* e, const uint8_t* starts_dev, void* stream);
+
+/* ---- position rollouts (csrc/bg_engine.hip; bgx/rollout.py; no counterpart in the
+ * reference) ----
+ * n lanes of an auto_reset = 1 engine whose start table is starts_dev play
+ * games_per_lane games each from their start records, one player acting for both sides;
+ * the results are tallied per position.  The caller owns the state, plain device arrays:
+ * group int32[n] (lane -> position in [0, n_groups); any other value: an idle lane, never
+ * selected, never counted, to be given action 0), games_done int32[n], plies int32[n]
+ * (steps of the lane's current game), sel uint8[n] (the lane is active: the lane selection
+ * of bgx_one_ply_sel / bgx_two_ply_sel), tally int64[n_groups][8] (bgx_rollout_field) and
+ * active int64[1].  A win is a win by the start record's mover (byte 52 of
+ * starts_dev[i]); 1 / 2 / 3 is info's game_score.  records_dev = the engine's lane records.
+ * No entry point synchronises or allocates: both can be captured into a HIP graph.
+ * bgx_rollout_begin: zeroes the state, sel from group and games_per_lane, active = the
+ * number of active lanes.
+ * bgx_rollout_advance: after bgx_step, with that step's done and info.  Every active lane
+ * adds a ply to its own counter; a done with a winner adds the game, its plies and its
+ * result to the lane's group row and zeroes the counter; a lane that finished its last game
+ * is deselected and active drops.  The sums are integers: run-to-run identical.
+ * BGX_EINVAL for n <= 0, n_groups <= 0, games_per_lane < 0 or a NULL pointer. */
+enum bgx_rollout_field {
+    BGX_ROLLOUT_GAMES = 0,        /* finished games */
+    BGX_ROLLOUT_PLIES = 1,        /* their steps, passes included */
+    BGX_ROLLOUT_WIN1 = 2,  BGX_ROLLOUT_WIN2 = 3,  BGX_ROLLOUT_WIN3 = 4,    /* won by the start mover: 1 / 2 / 3 points */
+    BGX_ROLLOUT_LOSS1 = 5, BGX_ROLLOUT_LOSS2 = 6, BGX_ROLLOUT_LOSS3 = 7
+};
+int bgx_rollout_begin(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev, int32_t n,
+                      int32_t n_groups, int32_t games_per_lane, int32_t* games_done_dev, int32_t* plies_dev,
+                      uint8_t* sel_dev, int64_t* tally_dev, int64_t* active_dev, void* stream);
+int bgx_rollout_advance(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev,
+                        const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
+                        int32_t games_per_lane, int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev,
+                        int64_t* tally_dev, int64_t* active_dev, void* stream);
 
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row

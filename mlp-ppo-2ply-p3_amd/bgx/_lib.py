@@ -62,6 +62,9 @@ SIGNATURES = {
     "bgx_arena_begin": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
     "bgx_arena_merge": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P]),
     "bgx_arena_advance": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P, _P]),
+    "bgx_engine_set_starts": (ctypes.c_int, [_P, _P, _P]),
+    "bgx_rollout_begin": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "bgx_rollout_advance": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),

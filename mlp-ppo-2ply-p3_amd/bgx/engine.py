@@ -24,6 +24,30 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def validate_starts(records: torch.Tensor) -> None:
+    """Raise ValueError naming the first bad lane of a start table (uint8[n, 64] records in the
+    lane-record layout, any device) and the reason: the rules of bgx_engine_set_starts."""
+    if records.dim() != 2 or records.shape[1] != 64 or records.dtype != torch.uint8:
+        raise ValueError(f"start records must be uint8 [n, 64], got {records.dtype} {tuple(records.shape)}")
+    r = records.to(torch.int32)
+    p1, p2 = r[:, 0:24], r[:, 24:48]
+    d0, d1 = r[:, R_ROLL0], r[:, R_ROLL1]
+    checks = (
+        ("PLAYER1's points, bar and off do not sum to 15", p1.sum(1) + r[:, 48] + r[:, 50] != 15),
+        ("PLAYER2's points, bar and off do not sum to 15", p2.sum(1) + r[:, 49] + r[:, 51] != 15),
+        ("a point is held by both sides", ((p1 > 0) & (p2 > 0)).any(1)),
+        ("a side has all 15 checkers off (the game is over)", (r[:, 50] >= 15) | (r[:, 51] >= 15)),
+        ("the mover (byte 52) is not 0 or 1", r[:, R_CUR] > 1),
+        ("the roll (bytes 53, 54) is neither (0, 0) nor two dice in 1..6",
+         ~(((d0 == 0) & (d1 == 0)) | ((d0 >= 1) & (d0 <= 6) & (d1 >= 1) & (d1 <= 6)))),
+    )
+    bad = torch.stack([c for _, c in checks])            # [checks, n]
+    if bool(bad.any()):
+        lane = int(bad.any(0).nonzero()[0])
+        why = checks[int(bad[:, lane].nonzero()[0])][0]
+        raise ValueError(f"start record of lane {lane}: {why}")
+
+
 class Engine:
     """B concurrent BackgammonEnv lanes (backgammon_env.py:35-405) on one GPU.
 
@@ -197,6 +221,25 @@ class Engine:
             raise ValueError(f"set_lanes: records must be [n, 64] bytes, got {tuple(r.shape)}")
         check(self._lib.bgx_set_lanes_ex(self._h, lane0, r.shape[0], _ptr(r), int(bool(regen)), self._stream()),
               "bgx_set_lanes_ex")
+
+    def set_starts(self, records: torch.Tensor | None):
+        """Per-lane start positions (bgx_engine_set_starts): uint8[B, 64] records whose board,
+        mover and roll (bytes 0..54; roll (0, 0) = drawn at the reset) every later reset of
+        the lane gives instead of the opening -- reset(), the auto-reset inside a step, the
+        reset step of an auto_reset=False engine.  None: standard openings again.  The
+        lanes are not touched by the call.  The records are validated first (this reads
+        them back, so it waits for the device): ValueError names the first bad lane."""
+        if self.dice == "shared":
+            raise ValueError("set_starts: a shared-dice engine has no start positions "
+                             "(one stream in lane order mirrors the reference's vector env)")
+        r = None
+        if records is not None:
+            r = torch.as_tensor(records)
+            if r.dim() != 2 or r.shape[0] != self.batch:
+                raise ValueError(f"set_starts: records must be [{self.batch}, 64] bytes, got {tuple(r.shape)}")
+            validate_starts(r)
+            r = r.to(device=self.device).contiguous()
+        check(self._lib.bgx_engine_set_starts(self._h, _ptr(r), self._stream()), "bgx_engine_set_starts")
 
     def n_moves(self, out: torch.Tensor | None = None) -> torch.Tensor:
         """Legal-action count per lane (int16[B]); mask = arange(max_moves) < count."""

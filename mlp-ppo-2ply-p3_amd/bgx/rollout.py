@@ -1,0 +1,388 @@
+"""Position rollouts: play a position to the end many times with a given player and
+average the results (DESIGN.md "Start positions and rollouts"; the device side is the
+engine's start table, bgx_engine_set_starts, and the rollout kernels of
+csrc/bg_engine.hip).  It answers "what is this position worth?" and, through
+rollout_moves, "which of these moves is best when the game is played out?".
+
+    python -m bgx.rollout --net ckpt.pt --player 1ply --positions pos.json --trials 1296 \\
+        --batch 4096 --max-steps 4000 --seed 0
+
+Every lane holds one position as its start record: the engine's auto-reset refills the lane
+with it in the step that ends a game, so no lane waits for the longest game of a wave.  One
+player acts for both sides.  Equity is in points (1 / 2 / 3 per game, cubeless) from the
+side of the position's mover.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes
+import json
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from .arena import PLAYER_KINDS, SYNC_EVERY, TRACE_LIMIT, _stream, load_net, make_player
+from .engine import Engine, R_CUR, R_ROLL0, R_ROLL1, _ptr, validate_starts
+
+# tally int64[n_groups][8] (include/bgx.h bgx_rollout_field)
+FIELDS = ("games", "plies", "win1", "win2", "win3", "loss1", "loss2", "loss3")
+ROLLS36 = [(a, b) for a in range(1, 7) for b in range(1, 7)]       # the 36 ordered rolls
+FIRST_ROLLS = ("stratified", "random")
+
+
+def summarize(tally_row, unfinished: int = 0) -> dict:
+    """One position's result from its 8 tally entries: `games`, `plies_per_game`, the
+    cumulative rates of each side (`win` = any win, `win_gammon` = gammon or backgammon,
+    `win_backgammon`; `loss*` likewise), `equity` = sum_k k (WINk - LOSSk) / games in points,
+    `equity_stderr` = sqrt((sum_k k^2 (WINk + LOSSk) - games equity^2) / (games - 1) / games),
+    the standard error of a mean of independent games, and `unfinished` (scheduled games that
+    did not end).  With stratified first rolls the games are not independent draws -- each
+    first roll occurs exactly equally often, which removes that part of the variance -- so
+    the standard error is a conservative bound there.  No games: the rates are 0; one game:
+    the standard error is 0."""
+    t = [int(v) for v in tally_row]
+    if len(t) != len(FIELDS):
+        raise ValueError(f"summarize: a tally row has {len(FIELDS)} entries, got {len(t)}")
+    r = dict(zip(FIELDS, t))
+    g = r["games"]
+    w, l = t[2:5], t[5:8]
+    inv = 1.0 / g if g > 0 else 0.0
+    eq = sum((k + 1) * (w[k] - l[k]) for k in range(3)) * inv
+    sq = sum((k + 1) ** 2 * (w[k] + l[k]) for k in range(3))
+    var = max(sq - g * eq * eq, 0.0) / (g - 1) / g if g > 1 else 0.0
+    r.update(plies_per_game=r["plies"] * inv,
+             win=sum(w) * inv, win_gammon=(w[1] + w[2]) * inv, win_backgammon=w[2] * inv,
+             loss=sum(l) * inv, loss_gammon=(l[1] + l[2]) * inv, loss_backgammon=l[2] * inv,
+             equity=eq, equity_stderr=math.sqrt(var), unfinished=int(unfinished))
+    return r
+
+
+def layout(n_positions: int, trials: int, first_roll: str = "stratified", batch: int = 4096):
+    """How `trials` games of each of `n_positions` positions go onto `batch` lanes.  Returns
+    (group int32[passes, batch], roll_of_lane uint8[passes, batch, 2], games_per_lane, passes):
+    lane -> position (-1 = idle) and the lane's start roll, per pass.
+
+    A unit is one position ("random": roll bytes (0, 0), drawn at every reset) or one
+    (position, ordered roll) pair ("stratified": `trials` is rounded up to a multiple of 36
+    and each of the 36 rolls gets trials / 36 games with that first roll).  Every unit gets
+    the same number of lanes, side by side, and every lane the same number of games.  More
+    games than lanes: several games per lane first; more units than lanes: several passes.
+    A unit's games (lanes x games_per_lane) can exceed its share by less than one game per
+    lane when the share does not divide; the tallies report what was played."""
+    if first_roll not in FIRST_ROLLS:
+        raise ValueError(f"first_roll must be one of {FIRST_ROLLS}, got {first_roll!r}")
+    if n_positions <= 0 or trials <= 0 or batch <= 0:
+        raise ValueError(f"layout: n_positions {n_positions}, trials {trials} and batch {batch} must be positive")
+    strat = first_roll == "stratified"
+    per_pos = 36 if strat else 1
+    share = -(-trials // 36) if strat else trials              # games per unit
+    units = n_positions * per_pos
+    per_pass = min(units, batch)
+    passes = -(-units // per_pass)
+    lanes = min(share, batch // per_pass)                        # lanes per unit
+    games = -(-share // lanes)
+    lanes = -(-share // games)
+    group = np.full((passes, batch), -1, np.int32)
+    roll = np.zeros((passes, batch, 2), np.uint8)
+    for k in range(passes):
+        u = np.arange(k * per_pass, min((k + 1) * per_pass, units))
+        lane_unit = np.repeat(u, lanes)
+        group[k, :lane_unit.size] = lane_unit // per_pos
+        if strat:
+            roll[k, :lane_unit.size] = np.asarray(ROLLS36, np.uint8)[lane_unit % 36]
+    return group, roll, games, passes
+
+
+def _records(positions) -> torch.Tensor:
+    p = torch.as_tensor(positions)
+    if p.dim() == 1:
+        p = p[None]
+    if p.dim() != 2 or p.shape[1] != 64 or p.dtype != torch.uint8 or p.shape[0] == 0:
+        raise ValueError(f"positions must be uint8 [P, 64] lane records, got {p.dtype} {tuple(p.shape)}")
+    p = p.cpu().clone()
+    p[:, R_ROLL0:] = 0
+    validate_starts(p)
+    return p
+
+
+class Rollout:
+    """`batch` lanes of an engine of its own (auto_reset, so a finished game's lane starts
+    its next one, from its start record, in the same step)."""
+
+    def __init__(self, batch: int, seed: int = 0, dice: str = "philox", max_moves: int = 500, device=None):
+        if batch <= 0:
+            raise ValueError(f"Rollout: batch {batch} must be positive")
+        if dice == "shared":
+            raise ValueError("Rollout: a shared-dice engine has no start positions")
+        self.B, self.seed = int(batch), int(seed)
+        self.eng = Engine(batch=self.B, max_moves=max_moves, seed=self.seed, dice=dice, auto_reset=True, device=device)
+        if dice != "philox":
+            self.eng.seed((np.arange(self.B, dtype=np.uint64) + self.seed) & 0xFFFFFFFF)
+        dev = self.eng.device
+        self.games_done = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.plies = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.sel = torch.zeros(self.B, dtype=torch.uint8, device=dev)
+        self.active = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.actions = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.steps = 0                  # steps of every run so far: the players' random streams go on
+
+    def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
+                  trace: bool = False):
+        """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
+        lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
+        `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
+        [act, step, advance] until no lane is active or `max_steps` env steps ran; the host
+        reads the active-lane count every SYNC_EVERY steps for a sync-free player.  The
+        engine keeps the table afterwards.  Returns (tally int64[n_groups, 8], unfinished
+        int64[n_groups] = scheduled games that did not end, trace): trace (None without
+        trace=True) holds per-step [steps, B] tensors mover, action, done, info, and the final
+        games_done and active."""
+        max_steps, G, P = int(max_steps), int(games_per_lane), int(n_groups)
+        if max_steps < 0 or G < 0 or P <= 0:
+            raise ValueError(f"run_lanes: max_steps {max_steps}, games_per_lane {G} must be >= 0, n_groups {P} > 0")
+        if trace and self.B * max_steps > TRACE_LIMIT:
+            raise ValueError(f"run_lanes: trace=True holds batch x max_steps = {self.B * max_steps} entries per "
+                             f"field; the limit is {TRACE_LIMIT} (it is for tests and small batches)")
+        L, eng, dev = _lib.load(), self.eng, self.eng.device
+        starts = torch.as_tensor(starts)
+        grp = torch.as_tensor(group).to(device=dev, dtype=torch.int32).contiguous()
+        if grp.shape != (self.B,) or bool((grp >= P).any()):
+            raise ValueError(f"run_lanes: group must be int32[{self.B}] with entries below n_groups = {P}")
+        recs = ctypes.c_void_p(eng.lanes_ptr())
+        tally = torch.zeros(P, 8, dtype=torch.int64, device=dev)
+        state = (_ptr(self.games_done), _ptr(self.plies), _ptr(self.sel), _ptr(tally), _ptr(self.active))
+        eng.set_starts(starts)              # validated where the records live (the host, from run())
+        starts = starts.to(dev).contiguous()    # the kernels' copy: the start movers
+        eng.reset(want_obs=False)
+        check(L.bgx_rollout_begin(recs, _ptr(starts), _ptr(grp), self.B, P, G, *state, _stream(dev)),
+              "bgx_rollout_begin")
+        tr = None
+        if trace:
+            tr = {n: torch.zeros(max_steps, self.B, dtype=dt, device=dev)
+                  for n, dt in (("mover", torch.uint8), ("action", torch.int32), ("done", torch.uint8),
+                                ("info", torch.int32))}
+            rec = torch.empty(self.B, 64, dtype=torch.uint8, device=dev)
+        every = SYNC_EVERY if getattr(player, "sync_free", False) else 1
+        steps = 0
+        active = int(self.active.item())
+        while active > 0 and steps < max_steps:
+            act = player.act(eng, self.sel, self.steps)
+            if (not isinstance(act, torch.Tensor) or act.dtype != torch.int32 or act.device != dev
+                    or not act.is_contiguous() or act.numel() != self.B):
+                raise ValueError("a player's act must return a contiguous int32[B] tensor on the engine's device")
+            # actions = sel ? act : 0 (the arena's merge with one player on both sides)
+            check(L.bgx_arena_merge(_ptr(self.sel), _ptr(self.sel), _ptr(act), _ptr(act), self.B,
+                                    _ptr(self.actions), _stream(dev)), "bgx_arena_merge")
+            if trace:
+                eng.records(out=rec)
+                tr["mover"][steps] = rec[:, R_CUR]
+                tr["action"][steps] = self.actions
+            _, _, done, info = eng.step(self.actions, want_obs=False, want_info=True)
+            check(L.bgx_rollout_advance(recs, _ptr(starts), _ptr(grp), _ptr(done), _ptr(info), self.B, P, G,
+                                        *state, _stream(dev)), "bgx_rollout_advance")
+            if trace:
+                tr["done"][steps] = done
+                tr["info"][steps] = info
+            steps += 1
+            self.steps += 1
+            if steps % every == 0 or steps == max_steps:
+                active = int(self.active.item())
+        left = torch.where(grp >= 0, G - self.games_done, 0).to(torch.int64)
+        unfinished = torch.zeros(P, dtype=torch.int64, device=dev).index_add_(0, grp.clamp(min=0).long(), left)
+        if trace:
+            tr = {n: v[:steps] for n, v in tr.items()}
+            tr.update(games_done=self.games_done.clone(), active=int(self.active.item()))
+        return tally, unfinished, tr
+
+    def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
+            trace: bool = False):
+        """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
+        bytes come from the layout) `trials` times with `player` (any arena player object)
+        on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
+        (the rest is reported as `unfinished`); standard openings again afterwards.  Returns
+        the list of the positions' results (summarize); with trace=True also the last
+        pass's trace with its group, starts and games_per_lane."""
+        pos = _records(positions)
+        P = pos.shape[0]
+        group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
+        total = unfinished = tr = None
+        for k in range(passes):
+            grp = torch.from_numpy(group[k])
+            starts = pos[grp.clamp(min=0).long()].clone()          # idle lanes: a valid record, never counted
+            starts[:, R_ROLL0:R_ROLL1 + 1] = torch.from_numpy(roll[k])
+            tally, unf, tr = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace)
+            total = tally if total is None else total + tally
+            unfinished = unf if unfinished is None else unfinished + unf
+            if trace:
+                tr.update(group=grp, starts=starts, games_per_lane=G)
+        self.eng.set_starts(None)
+        rows, unf = total.cpu().tolist(), unfinished.cpu().tolist()
+        res = [summarize(rows[p], unf[p]) for p in range(P)]
+        return (res, tr) if trace else res
+
+
+def exact_score(after52, mover: int) -> int:
+    """0 when `mover` has not borne off all 15 checkers in the afterstate (int8[52]); else the
+    game's points by the env's rule: 2 when the opponent has none off, 3 when in addition
+    the opponent has a checker in the mover's home board or on the bar, else 1."""
+    b = np.asarray(after52).astype(np.int64)
+    if b[50 + mover] < 15:
+        return 0
+    opp = 1 - mover
+    if b[50 + opp] > 0:
+        return 1
+    home = 18 if mover == 0 else 0
+    return 3 if b[opp * 24 + home:opp * 24 + home + 6].sum() > 0 or b[48 + opp] > 0 else 2
+
+
+def decode_move(v: int):
+    """uint64 move -> [(src, dst, hit), ...] (16 bits per sub-move)."""
+    subs = []
+    for i in range(4):
+        s = (int(v) >> (16 * i)) & 0xFFFF
+        if not s & 0x8000:
+            break
+        subs.append((s & 31, (s >> 5) & 31, (s >> 10) & 1))
+    return subs
+
+
+def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str = "stratified",
+                  max_steps: int = 4000) -> list:
+    """A decision: `record` (uint8[64]) holds the board, the mover and the roll to play.  Every
+    legal move's afterstate is rolled out with the opponent on roll and the move's equity is
+    minus that rollout's; moves that reach the same afterstate share one rollout.  A move
+    that ends the game is scored exactly and spends no lanes (`games` 0, `exact` True).
+    Returns one dict per move, best first: move (the encoded uint64), submoves, equity,
+    equity_stderr, games, exact.  No legal move: one entry with move None (the pass)."""
+    rec = torch.as_tensor(record).reshape(-1)
+    if rec.numel() != 64 or rec.dtype != torch.uint8:
+        raise ValueError("rollout_moves: record must be 64 bytes (uint8)")
+    rec = rec.cpu().clone()
+    rec[55:] = 0
+    validate_starts(rec[None])
+    mover, dice = int(rec[R_CUR]), (int(rec[R_ROLL0]), int(rec[R_ROLL1]))
+    if dice[0] == 0:
+        raise ValueError("rollout_moves: the record has no roll to play (bytes 53, 54)")
+    eng = rollout.eng
+    # the legal moves and their afterstates: the position posed on lane 0 (the rollout resets it)
+    eng.set_lanes(rec[None], lane0=0)
+    lane, mv, _ = eng.lanes(0, 1)
+    n = int(lane[0, 60]) | (int(lane[0, 61]) << 8)
+    if n == 0:
+        moves, afters = [None], rec[None, :52].numpy().view(np.int8)
+    else:
+        moves = [int(m) for m in mv[0, :n].cpu().numpy().view(np.uint64)]
+        afters = eng.afterstates(0, 1)[0, :n].cpu().numpy()
+    scores = [exact_score(a, mover) for a in afters]
+    open_idx = [i for i, s in enumerate(scores) if s == 0]
+    results = {}
+    if open_idx:
+        uniq, inverse = np.unique(afters[open_idx], axis=0, return_inverse=True)
+        pos = np.zeros((len(uniq), 64), np.uint8)
+        pos[:, :52] = uniq.view(np.uint8)
+        pos[:, R_CUR] = 1 - mover
+        res = rollout.run(player, torch.from_numpy(pos), trials, first_roll=first_roll, max_steps=max_steps)
+        for i, u in zip(open_idx, np.asarray(inverse).reshape(-1)):
+            results[i] = res[int(u)]
+    out = []
+    for i, m in enumerate(moves):
+        if scores[i]:
+            out.append(dict(move=m, submoves=decode_move(m), equity=float(scores[i]), equity_stderr=0.0, games=0,
+                            exact=True, unfinished=0))
+        else:
+            r = results[i]
+            out.append(dict(move=m, submoves=decode_move(m) if m is not None else [], equity=-r["equity"],
+                            equity_stderr=r["equity_stderr"], games=r["games"], exact=False,
+                            unfinished=r["unfinished"]))
+    out.sort(key=lambda d: -d["equity"])
+    return out
+
+
+# ------------------------------------------------------------- command line --
+def opening_record() -> torch.Tensor:
+    """The standard opening position, PLAYER1 on roll."""
+    r = torch.zeros(64, dtype=torch.uint8)
+    for p, c in ((0, 2), (11, 5), (16, 3), (18, 5), (24 + 23, 2), (24 + 12, 5), (24 + 7, 3), (24 + 5, 5)):
+        r[p] = c
+    return r
+
+
+def load_positions(path: str) -> torch.Tensor:
+    """"opening", or a JSON file: a list of {"board": [52 ints], "player": 0 | 1}."""
+    if path == "opening":
+        return opening_record()[None]
+    with open(path) as f:
+        items = json.load(f)
+    if not isinstance(items, list) or not items:
+        raise ValueError(f"{path}: expected a non-empty JSON list of positions")
+    out = torch.zeros(len(items), 64, dtype=torch.uint8)
+    for i, it in enumerate(items):
+        board = it["board"]
+        if len(board) != 52 or any(not 0 <= int(v) <= 15 for v in board):
+            raise ValueError(f"{path}: position {i}: board must be 52 counts in 0..15")
+        out[i, :52] = torch.tensor([int(v) for v in board], dtype=torch.uint8)
+        out[i, R_CUR] = int(it.get("player", 0))
+    return out
+
+
+class _Parser(argparse.ArgumentParser):
+    """--top-k is an error for any player but a 2ply one with weights."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        if ns.top_k is not None:
+            if ns.player != "2ply" or ns.net == "random":
+                self.error("--top-k needs --player 2ply with weights")
+            if ns.top_k < 1:
+                self.error("--top-k must be >= 1")
+        if ns.trials < 1 or ns.batch < 1:
+            self.error("--trials and --batch must be >= 1")
+        return ns
+
+
+def build_parser() -> argparse.ArgumentParser:
+    ap = _Parser(prog="python -m bgx.rollout", description="Roll positions out with one player on both sides.")
+    ap.add_argument("--net", required=True, help="a state_dict file (PPOTrainer.save) or 'random'")
+    ap.add_argument("--player", default="policy", choices=PLAYER_KINDS)
+    ap.add_argument("--top-k", type=int, default=None, help="2ply only: search only the top-k 1-ply moves")
+    ap.add_argument("--positions", required=True,
+                    help="'opening' or a JSON file: a list of {\"board\": [52 ints], \"player\": 0|1}")
+    ap.add_argument("--trials", type=int, default=1296, help="games per position (stratified: a multiple of 36)")
+    ap.add_argument("--first-roll", default="stratified", choices=FIRST_ROLLS)
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--max-steps", type=int, default=4000,
+                    help="env steps per pass after which it stops (unfinished games are reported)")
+    ap.add_argument("--seed", type=int, default=0)
+    return ap
+
+
+def main(argv=None):
+    import time
+    args = build_parser().parse_args(argv)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    net = None if args.net == "random" else load_net(args.net, dev)
+    max_moves = min(net.action_head.out_features, 500) if net is not None else 500
+    player = make_player(args.player, net, seed=args.seed * 2 + 1, top_k=args.top_k)
+    positions = load_positions(args.positions)
+    ro = Rollout(args.batch, seed=args.seed, max_moves=max_moves, device=dev)
+    torch.cuda.synchronize(dev)
+    t0 = time.perf_counter()
+    res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps)
+    dt = time.perf_counter() - t0
+    for i, r in enumerate(res):
+        print(json.dumps(dict(position=i, **r)), flush=True)
+    games = sum(r["games"] for r in res)
+    summary = dict(summary=True, positions=len(res), games=games, unfinished=sum(r["unfinished"] for r in res),
+                   steps=ro.steps, net=args.net, player="random" if net is None else args.player, top_k=args.top_k,
+                   trials=args.trials, first_roll=args.first_roll, batch=args.batch, max_steps=args.max_steps,
+                   seed=args.seed, seconds=dt, games_per_s=games / dt if dt > 0 else 0.0,
+                   env_steps_per_s=ro.steps * args.batch / dt if dt > 0 else 0.0)
+    print(json.dumps(summary), flush=True)
+    return res, summary
+
+
+if __name__ == "__main__":
+    main()

@@ -173,7 +173,12 @@ struct Args {
     uint8_t* cls;             // [B] predicted cost class (written by k_order_count), or null
     uint8_t* pre;             // [B] pre-class byte (pre_class), written by k_step / k_reset; null with cls
     int xcd;                  // B % 128 == 0: XCD-aware dispatch (16-lane runs per XCD, bg_engine.hip k_order_*)
+    // start table (bgx_engine_set_starts): [B][64] start records in the lane-record layout,
+    // the engine's own copy, byte kStartOk = 1 on the records k_check_starts found valid;
+    // null = every reset gives the standard opening
+    const uint8_t* starts;
 };
+constexpr int kStartOk = 63;
 
 // blockIdx -> lane when there is no dispatch order: blocks b, b + 8, ... (one XCD
 // under round-robin placement) take the 16 consecutive lanes of one run, so a
@@ -200,7 +205,8 @@ constexpr uint64_t kCtrMask = (1ull << 48) - 1ull;
 // wave's part of the prediction (one ballot); the roll is predict_class's.
 constexpr int kPreOver = 0x80;
 __device__ __forceinline__ int pre_class(int bv) {
-    if (rd(bv, R_OVER)) return kPreOver;                  // next: reset -> opening roll (never doubles)
+    if (rd(bv, R_OVER)) return kPreOver;                  // next: reset -> opening roll (never doubles; a start
+                                                          // table's roll may be: the light launch defers it)
     const int nxt = 1 - rd(bv, R_CUR);
     const int l = lane_id();
     const int off = nxt * 24;
@@ -278,17 +284,28 @@ __device__ __forceinline__ bool roll_lane(int& bv, int gi, const Args& A, uint32
     if (cached) {
     } else if (need == NEED_RESET) {
         if (rd(bv, R_MATCH)) { bv = wr(bv, R_S0, 0); bv = wr(bv, R_S1, 0); bv = wr(bv, R_MATCH, 0); }
-        if (lane_id() < 52) bv = initial_byte(lane_id());
         bv = wr(bv, R_OVER, 0);
+        // start table (never with SHARED dice): the lane's own start record instead of the
+        // opening -- its board and mover, and its roll, or two dice as for a mid-game roll
+        // (doubles allowed, no starter draw) when the record's roll is (0, 0)
+        const int sv = A.starts ? (int)A.starts[(size_t)gi * 64 + lane_id()] : 0;
         int starter;
-        if (A.dice_mode == BGX_DICE_MT_SHARED) {
-            const uint8_t* sr = A.shared_rolls + (size_t)gi * 4;
-            r0 = (int)ufl(sr[0]); r1 = (int)ufl(sr[1]); starter = (int)ufl(sr[2]);
+        if (A.starts && rd(sv, kStartOk)) {
+            if (lane_id() < 52) bv = sv;
+            starter = rd(sv, R_CUR);
+            r0 = rd(sv, R_ROLL0); r1 = rd(sv, R_ROLL1);
+            if (r0 == 0) { r0 = rng.die(); r1 = rng.die(); }
         } else {
-            int a, b;
-            do { a = rng.die(); b = rng.die(); } while (a == b);
-            starter = a < b ? 1 : 0;
-            do { r0 = rng.die(); r1 = rng.die(); } while (r0 == r1);
+            if (lane_id() < 52) bv = initial_byte(lane_id());
+            if (A.dice_mode == BGX_DICE_MT_SHARED) {
+                const uint8_t* sr = A.shared_rolls + (size_t)gi * 4;
+                r0 = (int)ufl(sr[0]); r1 = (int)ufl(sr[1]); starter = (int)ufl(sr[2]);
+            } else {
+                int a, b;
+                do { a = rng.die(); b = rng.die(); } while (a == b);
+                starter = a < b ? 1 : 0;
+                do { r0 = rng.die(); r1 = rng.die(); } while (r0 == r1);
+            }
         }
         bv = wr(bv, R_CUR, starter);
     } else {
@@ -452,6 +469,7 @@ struct bgx_engine {
     int ovf_parity;
     bool ovf_next_zeroed;
     uint64_t seed;
+    uint8_t* starts;      // the start table's storage, [B][64] (Args::starts points here while a table is set)
     // bg_search.hip workspace (grown on demand)
     void* search_ws;
     size_t search_ws_bytes;

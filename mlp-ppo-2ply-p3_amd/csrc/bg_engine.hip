@@ -9,6 +9,8 @@
 //   n_total [B]      i32  untruncated count
 //   mt      [B][640] u32  per-lane numpy-legacy MT19937 state (+ index at [624])
 //   ctr     [B]      u64  per-lane Philox draw counters
+//   starts  [B][64]  u8   start table (bgx_engine_set_starts): the record a lane resets to
+//                         instead of the opening while a table is set; byte 63 = record valid
 // Kernels are launched one 64-thread workgroup (= one wave) per game.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -591,6 +593,115 @@ __global__ __launch_bounds__(256) void k_arena_advance(const uint8_t* recs, cons
     tally_add(tally, BGX_ARENA_ACTIVE, -count(retired));
 }
 
+// ---- start table (bgx_engine_set_starts) ----
+// One thread per record: copy it into the engine's table and mark it in byte kStartOk as
+// valid (1) or not (0; error bit 2, the lane keeps the standard opening).  Valid: each
+// side's points + bar + off == 15, no point held by both sides, both off counts < 15, mover
+// 0 or 1, roll (0, 0) or both dice in 1..6.
+__global__ __launch_bounds__(256) void k_check_starts(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int B,
+                                                      int32_t* err) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B) return;
+    uint4 q[4];
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = ((const uint4*)src)[(size_t)i * 4 + k];
+    uint8_t* r = (uint8_t*)q;
+    int sum0 = r[48] + r[50], sum1 = r[49] + r[51];
+    bool shared = false;
+    #pragma unroll
+    for (int p = 0; p < 24; ++p) {
+        sum0 += r[p];
+        sum1 += r[24 + p];
+        shared |= r[p] != 0 && r[24 + p] != 0;
+    }
+    const int d0 = r[R_ROLL0], d1 = r[R_ROLL1];
+    const bool roll_ok = (d0 == 0 && d1 == 0) || (d0 >= 1 && d0 <= 6 && d1 >= 1 && d1 <= 6);
+    const bool ok = sum0 == 15 && sum1 == 15 && !shared && r[50] < 15 && r[51] < 15 && r[R_CUR] <= 1 && roll_ok;
+    r[kStartOk] = ok ? 1 : 0;
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) ((uint4*)dst)[(size_t)i * 4 + k] = q[k];
+    if (!ok) atomicOr(err, 4);
+}
+
+// ---- position rollouts (DESIGN.md "Start positions and rollouts"; bgx/rollout.py drives it) ----
+// Bookkeeping of rollouts on an engine whose start table holds the positions: lane i plays
+// G games of position group[i] (one player acts for both sides), every game from the
+// lane's start record again (the engine's auto-reset refills it in the step that ends the
+// game).  State, plain arrays of the caller:
+//   group int32[n]        position of the lane in [0, n_groups); anything else = idle lane
+//   games_done int32[n]   finished, counted games of the lane (active while < G)
+//   plies int32[n]        steps of the lane's current game
+//   sel uint8[n]          the lane is active (lane selection of bgx_one_ply_sel / bgx_two_ply_sel)
+//   tally int64[n_groups][8]  bgx_rollout_field; win = won by the start record's mover
+//   active int64[1]       active lanes remaining
+// PLIES is added at the game's end with the game, so the atomics are per finished game.
+// Lanes of one group are usually neighbours: a wave adds once per (group, field) it holds
+// finishers of.  Integer adds commute: the tallies are the same from run to run.
+__device__ __forceinline__ int rollout_group(const int32_t* group, int i, int n_groups) {
+    const int g = group[i];
+    return g >= 0 && g < n_groups ? g : -1;
+}
+
+// tally and active are zero already (the entry point's memsets, ordered before this kernel)
+__global__ __launch_bounds__(256) void k_rollout_begin(const int32_t* group, int n, int n_groups, int G,
+                                                       int32_t* games_done, int32_t* plies, uint8_t* sel,
+                                                       int64_t* active) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < n;
+    const bool on = in && G > 0 && rollout_group(group, i, n_groups) >= 0;
+    if (in) {
+        games_done[i] = 0;
+        plies[i] = 0;
+        sel[i] = (uint8_t)on;
+    }
+    tally_add(active, 0, count(on));
+}
+
+__global__ __launch_bounds__(256) void k_rollout_advance(const uint8_t* starts, const int32_t* group,
+                                                         const uint8_t* done, const int32_t* info, int n, int n_groups,
+                                                         int G, int32_t* games_done, int32_t* plies, uint8_t* sel,
+                                                         int64_t* tally, int64_t* active) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool in = i < n;
+    const int g = in ? rollout_group(group, i, n_groups) : -1;
+    int gd = g >= 0 ? games_done[i] : G;
+    const bool on = g >= 0 && gd < G;
+    const int inf = on ? info[i] : 0;
+    const int winner = ((inf >> 8) & 0xFF) - 1, score = min(max((inf >> 16) & 0xFF, 1), 3);
+    const bool fin = on && done[i] != 0 && winner >= 0;
+    const int p = on ? plies[i] + 1 : 0;
+    int field = 0;
+    bool retired = false;
+    if (on) {
+        plies[i] = fin ? 0 : p;
+        if (fin) {
+            const bool won = winner == (int)(starts[(size_t)i * 64 + R_CUR] & 1);
+            field = (won ? BGX_ROLLOUT_WIN1 : BGX_ROLLOUT_LOSS1) + score - 1;
+            games_done[i] = ++gd;
+            retired = gd >= G;
+            if (retired) sel[i] = 0;
+        }
+    }
+    // the wave's finishers, one group at a time (every thread of the wave reaches the ballots)
+    uint64_t rest = __ballot(fin);
+    while (rest) {
+        const int lead = __ffsll((unsigned long long)rest) - 1;
+        const int gl = __shfl(g, lead, 64);
+        const bool mine = fin && g == gl;
+        const uint64_t m = __ballot(mine);
+        int ps = mine ? p : 0;
+        #pragma unroll
+        for (int o = 32; o > 0; o >>= 1) ps += __shfl_xor(ps, o, 64);
+        int64_t* row = tally + (size_t)gl * 8;
+        tally_add(row, BGX_ROLLOUT_GAMES, (long long)__popcll(m));
+        tally_add(row, BGX_ROLLOUT_PLIES, (long long)ps);
+        #pragma unroll
+        for (int f = BGX_ROLLOUT_WIN1; f <= BGX_ROLLOUT_LOSS3; ++f) tally_add(row, f, count(mine && field == f));
+        rest &= ~m;
+    }
+    tally_add(active, 0, -count(retired));
+}
+
 // murmur3's 64-bit finalizer
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
@@ -723,6 +834,7 @@ int bgx_engine_create(int device, int32_t batch, int32_t max_moves, uint64_t see
     A.ovf_count = e->ovf_base;
     alloc((void**)&A.ovf_queue, B * 4);
     alloc((void**)&A.err, 16);
+    if (dice_mode != BGX_DICE_MT_SHARED) alloc((void**)&e->starts, B * 64);     // bgx_engine_set_starts
     alloc((void**)&e->slow_tables, (size_t)kSlowWaves * ((size_t)16 << kLogSlotsSlow));
     if (!bgx_dbg("BGX_STAMPS").empty()) alloc((void**)&A.stamps, B * 16);
     if (dice_mode == BGX_DICE_PHILOX && bgx_dbg_int("BGX_ORDER", 1) != 0) {
@@ -803,7 +915,7 @@ int bgx_engine_destroy(bgx_engine* e) {
     Args& A = e->a;
     void* ptrs[] = {A.lanes, A.moves, A.n_total, A.mt, A.ctr, A.shared_rolls, e->ovf_base, A.ovf_queue, A.err,
                     e->slow_tables, e->search_ws, e->search_pool, e->oneply_ws, A.stamps, e->perm, A.cls, A.pre,
-                    e->order_cnt};
+                    e->order_cnt, e->starts};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t ev : e->search_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->step_ev) if (ev) (void)hipEventDestroy(ev);
@@ -1206,6 +1318,52 @@ int bgx_arena_advance(const uint8_t* records_dev, const uint8_t* done_dev, const
         return BGX_EINVAL;
     hipLaunchKernelGGL(k_arena_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, records_dev,
                        done_dev, info_dev, n, games_per_lane, games_done_dev, sel_a_dev, sel_b_dev, tally_dev);
+    CKL();
+    return BGX_OK;
+}
+
+int bgx_engine_set_starts(bgx_engine* e, const uint8_t* starts_dev, void* stream) {
+    if (!e || e->a.dice_mode == BGX_DICE_MT_SHARED || ((uintptr_t)starts_dev & 15)) return BGX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    Args& A = e->a;
+    CK(hipSetDevice(e->device));
+    EngineUse use(e, s);
+    CK(use.err);
+    if (!starts_dev) {
+        A.starts = nullptr;
+        return BGX_OK;
+    }
+    hipLaunchKernelGGL(k_check_starts, dim3((A.B + 255) / 256), dim3(256), 0, s, starts_dev, e->starts, A.B, A.err);
+    CKL();
+    A.starts = e->starts;
+    return BGX_OK;
+}
+
+int bgx_rollout_begin(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev, int32_t n,
+                      int32_t n_groups, int32_t games_per_lane, int32_t* games_done_dev, int32_t* plies_dev,
+                      uint8_t* sel_dev, int64_t* tally_dev, int64_t* active_dev, void* stream) {
+    if (!records_dev || !starts_dev || !group_dev || n <= 0 || n_groups <= 0 || games_per_lane < 0 ||
+        !games_done_dev || !plies_dev || !sel_dev || !tally_dev || !active_dev)
+        return BGX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    CK(hipMemsetAsync(tally_dev, 0, (size_t)n_groups * 8 * sizeof(int64_t), s));
+    CK(hipMemsetAsync(active_dev, 0, sizeof(int64_t), s));
+    hipLaunchKernelGGL(k_rollout_begin, dim3((n + 255) / 256), dim3(256), 0, s, group_dev, n, n_groups, games_per_lane,
+                       games_done_dev, plies_dev, sel_dev, active_dev);
+    CKL();
+    return BGX_OK;
+}
+
+int bgx_rollout_advance(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev,
+                        const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
+                        int32_t games_per_lane, int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev,
+                        int64_t* tally_dev, int64_t* active_dev, void* stream) {
+    if (!records_dev || !starts_dev || !group_dev || !done_dev || !info_dev || n <= 0 || n_groups <= 0 ||
+        games_per_lane < 0 || !games_done_dev || !plies_dev || !sel_dev || !tally_dev || !active_dev)
+        return BGX_EINVAL;
+    hipLaunchKernelGGL(k_rollout_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, starts_dev,
+                       group_dev, done_dev, info_dev, n, n_groups, games_per_lane, games_done_dev, plies_dev, sel_dev,
+                       tally_dev, active_dev);
     CKL();
     return BGX_OK;
 }
