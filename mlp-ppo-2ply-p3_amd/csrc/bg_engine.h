@@ -448,6 +448,33 @@ __device__ __forceinline__ void store_rec(const Args& A, int gi, int bv) { A.lan
 
 }  // namespace bg
 
+// A device buffer that grows on demand: the pointer and its capacity in bytes.
+struct DeviceBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    // Room for `bytes`.  A buffer that is too small is replaced by one of bytes plus
+    // slack_num per cent: `stream` is synchronised first (nothing in flight uses the old
+    // buffer), the first keep_bytes of the old buffer are copied over, the old buffer is
+    // freed.  When the allocation or the copy fails, the old buffer and capacity stay.
+    hipError_t reserve(size_t bytes, int slack_num, hipStream_t stream, size_t keep_bytes) {
+        if (cap >= bytes) return hipSuccess;
+        hipError_t err = hipStreamSynchronize(stream);
+        if (err != hipSuccess) return err;
+        const size_t ncap = bytes + bytes * (size_t)slack_num / 100;
+        void* np = nullptr;
+        if ((err = hipMalloc(&np, ncap)) != hipSuccess) return err;
+        if (p && keep_bytes) {
+            err = hipMemcpyAsync(np, p, keep_bytes, hipMemcpyDeviceToDevice, stream);
+            if (err == hipSuccess) err = hipStreamSynchronize(stream);
+            if (err != hipSuccess) { (void)hipFree(np); return err; }
+        }
+        void* old = p;
+        p = np;
+        cap = ncap;
+        return old ? hipFree(old) : hipSuccess;
+    }
+};
+
 // Engine object behind the C ABI's opaque bgx_engine*.
 struct bgx_engine {
     bool step_debug = false;        // BGX_STEP_DEBUG (bgx_debug_option) at creation: per-step tier sizes
@@ -470,16 +497,13 @@ struct bgx_engine {
     bool ovf_next_zeroed;
     uint64_t seed;
     uint8_t* starts;      // the start table's storage, [B][64] (Args::starts points here while a table is set)
-    // bg_search.hip workspace (grown on demand)
-    void* search_ws;
-    size_t search_ws_bytes;
-    void* search_pool;        // 2-ply leaf pool: keys [cap] x 16 B, then tags [cap] x 4 B
-    size_t search_pool_cap;
+    // bg_search.hip workspaces (grown on demand; bg_workspace.h has their layouts)
+    DeviceBuf search_ws;
+    DeviceBuf search_pool;    // 2-ply leaf pool: keys [slots] x 16 B, then tags [slots] x 4 B
     hipStream_t search_side;  // 2-ply: second stream for the concurrent enumerator (created on demand)
     hipEvent_t search_ev[5];  // 2-ply phase marks: start, enumerated, evaluated, fork, join
     float search_ms[2];       // last bgx_two_ply call, round 0: enumeration ms, evaluation ms
-    void* oneply_ws;          // bgx_one_ply workspace (rows sized for B x max_moves)
-    size_t oneply_ws_bytes;
+    DeviceBuf oneply_ws;      // bgx_one_ply workspace (rows sized for B x max_moves)
     // Cross-stream ordering of the engine's own calls (bgx.h "Stream ordering"): the end of
     // the last eager call that touched the engine's device state (lanes, moves, overflow
     // queues and tables, search workspace) and the stream it ran on.  A call on another

@@ -914,7 +914,7 @@ int bgx_engine_destroy(bgx_engine* e) {
     if (e->use_ev) (void)hipEventDestroy(e->use_ev);
     Args& A = e->a;
     void* ptrs[] = {A.lanes, A.moves, A.n_total, A.mt, A.ctr, A.shared_rolls, e->ovf_base, A.ovf_queue, A.err,
-                    e->slow_tables, e->search_ws, e->search_pool, e->oneply_ws, A.stamps, e->perm, A.cls, A.pre,
+                    e->slow_tables, e->search_ws.p, e->search_pool.p, e->oneply_ws.p, A.stamps, e->perm, A.cls, A.pre,
                     e->order_cnt, e->starts};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (hipEvent_t ev : e->search_ev) if (ev) (void)hipEventDestroy(ev);

@@ -44,10 +44,15 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <string>
+#include <vector>
+
 #include "bg_engine.h"
 #include "bg_debug.h"
+#include "bg_workspace.h"
 
 using namespace bg;
+using namespace bgws;
 
 namespace {
 
@@ -69,7 +74,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 constexpr int kEvalWideWaves = 8, kEvalNarrowWaves = 4;   // waves per LDS-weight evaluator workgroup
 constexpr int kKB = 13;            // 208 / 16 k-steps of v_mfma_f32_32x32x16_f16
-constexpr int kSlowQueue = 1 << 20;
 // Leaf-pool allocation block (slots): a wave claims kBlk slots with one atomic on the
 // pool's single cursor.  That cursor is one address hit from all eight XCDs: at 256 slots
 // (1.9 M claims per 65,536-root batch) the claims serialised the enumerators (23.7 ms
@@ -118,8 +122,7 @@ __device__ __forceinline__ int nd_roll(int k) {     // k-th non-doubles roll ind
 // The features are then exact small integers / halves in f16, so one hi and one
 // lo MFMA product give fp32-grade accuracy: narrow, hi + lo of a unit are summed
 // from two accumulator registers of the same lane; wide, the accumulator sums them.
-__host__ __device__ constexpr bool wide_tiles(int NT) { return NT > 4; }
-__host__ __device__ constexpr int slices(int NT) { return wide_tiles(NT) ? (NT + 1) & ~1 : NT; }
+// (wide_tiles(NT), slices(NT): bg_workspace.h)
 __host__ __device__ inline int sz_f16(int NT) { return 4 + kKB * slices(NT) * 64 * 4 + slices(NT) * 8 * 64; }
 
 constexpr int kFeatBias = -2;
@@ -1647,58 +1650,39 @@ extern void bgx_set_error(const char* msg);
 static int value_tiles16(int H) { return (H + 15) / 16; }   // 16 hidden units (hi + lo rows) per MFMA tile
 constexpr int kMaxHidden = 128;                              // 8 tiles: 120 KiB of weights in LDS
 
+// The kernels specialised by NT (16-unit slices of the value net) and the evaluators'
+// workgroup size, which must be the kernels' EvalShape<NT>::kWaves (their tile stride).
+typedef void (*EvalFn)(EvalArgs);
+typedef void (*RowPartFn)(const uint4*, const int64_t*, const uint4*, float*);
+typedef void (*EvalRowsFn)(EvalRowsArgs);
+struct TileKernels {
+    EvalFn eval[8];
+    RowPartFn rowpart[8];
+    EvalRowsFn eval_rows[8];
+    int threads[8];
+};
+#define BGX_BY_NT(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>}
+static const TileKernels kTileKernels = {
+    BGX_BY_NT(k_eval), BGX_BY_NT(k_rowpart), BGX_BY_NT(k_eval_rows),
+    {64 * EvalShape<1>::kWaves, 64 * EvalShape<2>::kWaves, 64 * EvalShape<3>::kWaves, 64 * EvalShape<4>::kWaves,
+     64 * EvalShape<5>::kWaves, 64 * EvalShape<6>::kWaves, 64 * EvalShape<7>::kWaves, 64 * EvalShape<8>::kWaves}};
+#undef BGX_BY_NT
+static int tile_index(int NT) { return NT >= 1 && NT <= 7 ? NT - 1 : 7; }
+
+// Workgroups of `kernel` (`threads` each) resident over the whole device, at most
+// per_cu_cap per CU.  When a query fails: 256 CUs; 8 one-wave workgroups or one larger
+// workgroup per CU.
+constexpr int kNoCap = 1 << 30;
 template <typename K>
-static int persistent_grid(const bgx_engine* e, K kernel, int per_cu_cap) {
+static int resident_grid(const bgx_engine* e, K kernel, int threads, int per_cu_cap) {
     int cus = 0, occ = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus <= 0)
         cus = 256;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 64, 0) != hipSuccess || occ <= 0) occ = 8;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, 0) != hipSuccess || occ <= 0)
+        occ = threads <= 64 ? 8 : 1;
     if (occ > per_cu_cap) occ = per_cu_cap;
     return cus * occ;
 }
-
-typedef void (*EvalFn)(EvalArgs);
-typedef void (*EvalRowsFn)(EvalRowsArgs);
-static int eval_waves(int NT) { return NT <= 4 ? kEvalNarrowWaves : kEvalWideWaves; }
-// the 2-ply evaluator for NT 16-unit slices and its workgroup size; the row-part kernel
-struct EvalPick { EvalFn fn; int threads; };
-static EvalPick eval_kernel(int NT) {
-    switch (NT) {
-        case 1: return {k_eval<1>, 64 * eval_waves(1)}; case 2: return {k_eval<2>, 64 * eval_waves(2)};
-        case 3: return {k_eval<3>, 64 * eval_waves(3)}; case 4: return {k_eval<4>, 64 * eval_waves(4)};
-        case 5: return {k_eval<5>, 64 * eval_waves(5)}; case 6: return {k_eval<6>, 64 * eval_waves(6)};
-        case 7: return {k_eval<7>, 64 * eval_waves(7)}; default: return {k_eval<8>, 64 * eval_waves(8)};
-    }
-}
-typedef void (*RowPartFn)(const uint4*, const int64_t*, const uint4*, float*);
-static RowPartFn rowpart_kernel(int NT) {
-    switch (NT) {
-        case 1: return k_rowpart<1>; case 2: return k_rowpart<2>; case 3: return k_rowpart<3>;
-        case 4: return k_rowpart<4>; case 5: return k_rowpart<5>; case 6: return k_rowpart<6>;
-        case 7: return k_rowpart<7>; default: return k_rowpart<8>;
-    }
-}
-static EvalRowsFn eval_rows_kernel(int NT) {
-    switch (NT) {
-        case 1: return k_eval_rows<1>; case 2: return k_eval_rows<2>; case 3: return k_eval_rows<3>;
-        case 4: return k_eval_rows<4>; case 5: return k_eval_rows<5>; case 6: return k_eval_rows<6>;
-        case 7: return k_eval_rows<7>; default: return k_eval_rows<8>;
-    }
-}
-// the launch's workgroup size must be the kernels' EvalShape<NT>::kWaves (their tile stride)
-
-// resident workgroups of an evaluator over the whole device
-template <typename K>
-static int eval_grid(const bgx_engine* e, K kernel, int NT) {
-    int occ = 0, ncu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 64 * eval_waves(NT), 0) != hipSuccess || occ <= 0)
-        occ = 1;
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || ncu <= 0)
-        ncu = 256;
-    return occ * ncu;
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The 1-ply row pipeline on stream s, inside the caller's EngineUse: V of every legal
 // afterstate of the selected lanes, lane i's at vrow[lane_off[i] ..] in move order.
@@ -1714,42 +1698,30 @@ struct OnePlyRows {
 static int one_ply_rows(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
                         bool with_kept, hipStream_t s, OnePlyRows& out) {
     Args& A = e->a;
-    const size_t B = (size_t)A.B, R = B * (size_t)A.max_moves;
-    // [lane_off B i32][row total i64][row_lane R i32][rowside R][rowkey R][vrow R f32]: sized for
-    // the worst case, so the pass runs without a host sync (the row count stays on the device);
-    // the move filter's [kept B i32][kept_move R i32] after them
-    const size_t o_tot = align256(B * 4), o_rl = o_tot + 256, o_side = align256(o_rl + R * 4),
-                 o_key = align256(o_side + R * 16), o_v = align256(o_key + R * 16), o_kept = align256(o_v + R * 4),
-                 o_km = align256(o_kept + B * 4), need = with_kept ? align256(o_km + R * 4) : o_kept;
-    if (e->oneply_ws_bytes < need) {
-        SCK(hipStreamSynchronize(s));
-        if (e->oneply_ws) SCK(hipFree(e->oneply_ws));
-        e->oneply_ws = nullptr;
-        e->oneply_ws_bytes = 0;
-        SCK(hipMalloc(&e->oneply_ws, need));
-        e->oneply_ws_bytes = need;
-    }
-    char* ws = (char*)e->oneply_ws;
-    int32_t* lane_off = (int32_t*)ws;
-    int64_t* total = (int64_t*)(ws + o_tot);
-    int32_t* row_lane = (int32_t*)(ws + o_rl);
-    uint4* rowside = (uint4*)(ws + o_side);
-    uint4* rowkey = (uint4*)(ws + o_key);
-    float* vrow = (float*)(ws + o_v);
-    const int NT = value_tiles16(hidden);
+    const size_t B = (size_t)A.B;
+    const OnePlyLayout L(B, (size_t)A.max_moves, with_kept);
+    SCK(e->oneply_ws.reserve(L.bytes(), 0, s, 0));
+    void* ws = e->oneply_ws.p;
+    int32_t* lane_off = L.lane_off.at(ws);
+    int64_t* total = L.total.at(ws);
+    int32_t* row_lane = L.row_lane.at(ws);
+    uint4* rowside = L.rowside.at<uint4>(ws);
+    uint4* rowkey = L.rowkey.at<uint4>(ws);
+    float* vrow = L.vrow.at(ws);
+    const int NT = value_tiles16(hidden), ti = tile_index(NT);
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, sel, lane_off, total, 0, (const int32_t*)nullptr);
     hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, total, row_lane);
     // ~20 legal moves per lane on average: one wave per ~5 rows at B = 4,096
     const size_t gr = B * 6 < 16384 ? (B * 6 > 64 ? B * 6 : 64) : 16384;
     hipLaunchKernelGGL(k_rows, dim3((unsigned)gr), dim3(256), 0, s, A, row_lane, lane_off, (const int32_t*)nullptr, total,
                        (uint8_t*)nullptr, rowside, rowkey, A.err);
-    const EvalRowsFn kr = eval_rows_kernel(NT);
+    const EvalRowsFn kr = kTileKernels.eval_rows[ti];
+    const int threads = kTileKernels.threads[ti];
     const EvalRowsArgs E{rowkey, rowside, total, vrow, (const uint4*)(vpacked + 4), vpacked + 4 + kKB * slices(NT) * 64 * 4,
                          value_bias};
-    hipLaunchKernelGGL(kr, dim3(eval_grid(e, kr, NT)), dim3(64 * eval_waves(NT)), 0, s, E);
+    hipLaunchKernelGGL(kr, dim3(resident_grid(e, kr, threads, kNoCap)), dim3(threads), 0, s, E);
     SCK(hipGetLastError());
-    out = OnePlyRows{lane_off, total, vrow, with_kept ? (int32_t*)(ws + o_kept) : nullptr,
-                     with_kept ? (int32_t*)(ws + o_km) : nullptr};
+    out = OnePlyRows{lane_off, total, vrow, with_kept ? L.kept.at(ws) : nullptr, with_kept ? L.kept_move.at(ws) : nullptr};
     return BGX_OK;
 }
 
@@ -1801,6 +1773,275 @@ struct MoveFilter {
     float* v1_out;
 };
 
+// What every stage of one two_ply_search call works on.
+struct SearchCall {
+    bgx_engine* e;
+    hipStream_t s;
+    const float* vpacked;
+    int32_t hidden;
+    int NT;
+    float value_bias;
+    const uint8_t* sel;
+};
+
+// Stage 1 (bgx_two_ply_topk only): the 1-ply values, k_filter's kept counts and move lists;
+// the candidate count lands in *cand_host at the scan's sync.
+static int filter_candidates(const SearchCall& c, const MoveFilter& f, float* q_out, OnePlyRows& cand,
+                             int64_t* cand_host) {
+    const int rc = one_ply_rows(c.e, c.vpacked, c.hidden, c.value_bias, c.sel, true, c.s, cand);
+    if (rc != BGX_OK) return rc;
+    Args& A = c.e->a;
+    hipLaunchKernelGGL(k_filter, dim3((A.B + 3) / 4), dim3(256), 0, c.s, A, c.sel, cand.lane_off, cand.total, cand.vrow,
+                       f.top_k, f.margin, cand.kept, cand.kept_move, q_out, f.v1_out);
+    SCK(hipGetLastError());
+    SCK(hipMemcpyAsync(cand_host, cand.total, 8, hipMemcpyDeviceToHost, c.s));
+    return BGX_OK;
+}
+
+// Stage 2: zero the counters, lay the rows out per lane (from the kept counts with a
+// filter) and read the row count on the host: the body of the workspace is sized by it.
+static int scan_rows(const SearchCall& c, const TwoPlyLayout& L, const int32_t* kept, int64_t* rows_host) {
+    SCK(c.e->search_ws.reserve(L.head_bytes(), 25, c.s, 0));
+    void* ws = c.e->search_ws.p;
+    Ctr* ctr = L.ctr.at(ws);
+    SCK(hipMemsetAsync(ctr, 0, 256, c.s));
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, c.s, c.e->a, c.sel, L.lane_off.at(ws), &ctr->rows, 1, kept);
+    SCK(hipGetLastError());
+    SCK(hipMemcpyAsync(rows_host, &ctr->rows, 8, hipMemcpyDeviceToHost, c.s));
+    SCK(hipStreamSynchronize(c.s));
+    if (*rows_host * 21 >= (int64_t)0x1FFFFFFF) return BGX_EINVAL;     // job ids are 29-bit pool tags
+    return BGX_OK;
+}
+
+// Stage 3: row -> lane (and row -> move with a filter), the jobs' min / max-length cells,
+// the afterstate records and the mover's sides.
+static int build_rows(const SearchCall& c, const TwoPlyLayout& L, const OnePlyRows& cand, int rows, int jobs) {
+    Args& A = c.e->a;
+    void* ws = c.e->search_ws.p;
+    Ctr* ctr = L.ctr.at(ws);
+    int32_t *lane_off = L.lane_off.at(ws), *row_lane = L.row_lane.at(ws);
+    int32_t* row_move = L.filtered ? L.row_move.at(ws) : nullptr;
+    if (L.filtered)
+        hipLaunchKernelGGL(k_expand_kept, dim3((A.B + 3) / 4), dim3(256), 0, c.s, A, c.sel, lane_off, &ctr->rows,
+                           cand.kept, cand.lane_off, cand.kept_move, row_lane, row_move);
+    else
+        hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, c.s, A, c.sel, lane_off, &ctr->rows, row_lane);
+    SCK(hipMemsetAsync(L.minv.at(ws), 0x7F, (size_t)jobs * 4, c.s));
+    SCK(hipMemsetAsync(L.maxlen.at(ws), 0xFF, (size_t)jobs, c.s));
+    hipLaunchKernelGGL(k_rows, dim3((rows + 3) / 4 < 16384 ? (rows + 3) / 4 : 16384), dim3(256), 0, c.s, A, row_lane,
+                       lane_off, (const int32_t*)row_move, &ctr->rows, L.rowrec.at(ws), L.rowside.at<uint4>(ws),
+                       (uint4*)nullptr, &ctr->bad);
+    SCK(hipGetLastError());
+    return BGX_OK;
+}
+
+// Everything the enumeration reads from debug options and occupancy, resolved once per
+// call: the options and kernels by the constructor, which makes no HIP call; the grids and
+// the pool size by size_grids, whose occupancy queries run on the host while the GPU is
+// busy with the rows.
+struct EnumPlan {
+    // doubles enumerator: 512-slot dedup table with the revisit memo inside it, held to
+    // 128 VGPRs (4 waves/SIMD, +1.5 %).  Tests (BGX_2PLY_HEAVY = 9:0 / 10:0) run the
+    // exact alternatives without the memo (9:0) or with a 1,024-slot table (10:0): the
+    // same leaves, Q and choices (tests/test_gpu_search.py)
+    void (*kheavy)(S2) = k_enum<9, 2, 1, 4>;
+    void (*klist)(S2) = k_enum<9, 2, 2, 4>;
+    // the non-doubles enumerator: the row-level walk held to 80 VGPRs (6 waves/SIMD,
+    // +1.2 % over its natural 91)
+    void (*klight)(S2);
+    EvalFn keval;
+    RowPartFn krowpart;
+    int eval_threads;
+    int cap_light = cap_fast<kLogLight>(), cap_heavy, cap_mid = cap_fast<kLogMid>();   // LDS tables' unique entries
+    bool barrow, factored, dbg;
+    std::string dump;                  // BGX_2PLY_DUMP: the test hook's file prefix
+    int g_light, g_heavy, g_list, g_t0, g_mid, g_eval;
+    size_t pool_slots;                 // the leaf pool this call asks for
+    explicit EnumPlan(int NT);
+    void size_grids(const bgx_engine* e, int jobs);
+};
+
+EnumPlan::EnumPlan(int NT) {
+    barrow = bgx_dbg_int("BGX_2PLY_BARROW", 1) != 0;      // tests: 0 = the bar rows per job
+    int hlog = 9, hmk = 2;
+    if (const std::string hv = bgx_dbg("BGX_2PLY_HEAVY"); !hv.empty()) {
+        hlog = atoi(hv.c_str());
+        const char* c = strchr(hv.c_str(), ':');
+        hmk = c ? atoi(c + 1) : 2;
+    }
+    if (hlog == 9 && hmk == 0) { kheavy = k_enum<9, 0, 1>; klist = k_enum<9, 0, 2>; }
+    else if (hlog == 10 && hmk == 0) { kheavy = k_enum<10, 0, 1>; klist = k_enum<10, 0, 2>; }
+    else { hlog = 9; hmk = 2; }
+    klight = k_enum<kLogLight, -1, 3, 6>;
+    cap_heavy = (7 << hlog) / 8;
+    if (const std::string fs = bgx_dbg("BGX_2PLY_LDS_CAP"); !fs.empty()) {    // tests: force the overflow tiers ("first[:mid]")
+        cap_light = cap_heavy = cap_mid = atoi(fs.c_str());
+        if (const char* c = strchr(fs.c_str(), ':')) cap_mid = atoi(c + 1);
+    }
+    dbg = !bgx_dbg("BGX_2PLY_DEBUG").empty();
+    // the root mover's part of X1 per row (the factored evaluator); BGX_2PLY_UNFACTORED
+    // (tests) evaluates every leaf over all 13 k-blocks instead
+    factored = bgx_dbg("BGX_2PLY_UNFACTORED").empty();
+    dump = bgx_dbg("BGX_2PLY_DUMP");
+    const int ti = tile_index(NT);
+    keval = kTileKernels.eval[ti];
+    krowpart = kTileKernels.rowpart[ti];
+    eval_threads = kTileKernels.threads[ti];
+}
+
+void EnumPlan::size_grids(const bgx_engine* e, int jobs) {
+    g_light = resident_grid(e, klight, 64, 32);
+    g_heavy = resident_grid(e, kheavy, 64, 32);
+    g_list = resident_grid(e, klist, 64, 32);
+    g_t0 = resident_grid(e, k_enum_tier<10, 0>, 64, 32);
+    g_mid = resident_grid(e, k_enum_tier<kLogMid, 1>, 64, 32);
+    g_eval = resident_grid(e, keval, eval_threads, kNoCap);
+    // leaf pool: ~32 slots per job (mean ~19 survivors at mid-game positions);
+    // BGX_2PLY_POOL overrides (tests force retry rounds with a tiny pool)
+    // every resident wave may hold a partly filled block in each tier
+    size_t cap = (size_t)jobs * 32 + (size_t)(g_light + g_heavy + g_list + g_t0 + g_mid + e->slow_waves) * kBlk * 2;
+    if (const long long ps = bgx_dbg_int("BGX_2PLY_POOL", 0); ps > 0) cap = (size_t)ps;
+    cap = (cap + kBlk - 1) / kBlk * kBlk;
+    if (cap < (size_t)kBlk * 4) cap = (size_t)kBlk * 4;
+    if (cap > ((size_t)1 << 31)) cap = (size_t)1 << 31;
+    pool_slots = cap;
+}
+
+// Stage 4: the enumeration and evaluation rounds.  Round 0 runs the non-doubles
+// enumerator beside the doubles one, then the overflow tiers and the evaluator; a job
+// that found the pool full is re-run from an explicit list in the next round, with the
+// pool started over.  *hc is the counter block as the last round left it.
+static int run_rounds(const SearchCall& c, const EnumPlan& plan, const TwoPlyLayout& L, const S2& S, const EvalArgs& E,
+                      Ctr* hc) {
+    bgx_engine* e = c.e;
+    hipStream_t s = c.s;
+    void* ws = e->search_ws.p;
+    Ctr* ctr = L.ctr.at(ws);
+    if (!e->search_ev[0])
+        for (hipEvent_t& ev : e->search_ev) SCK(hipEventCreate(&ev));
+    if (!e->search_side) SCK(hipStreamCreateWithFlags(&e->search_side, hipStreamNonBlocking));
+    SCK(hipEventRecord(e->search_ev[0], s));
+    // retry rounds run few waves: every wave holding a block wastes its unused
+    // part, and a round must leave pool for its jobs to finish (progress with any pool)
+    int gcap = 1 << 30;
+    auto g = [&](int grid) { return grid < gcap ? grid : gcap; };
+    auto tiers = [&]() {
+        hipLaunchKernelGGL((k_enum_tier<10, 0>), dim3(g(plan.g_t0)), dim3(64), 0, s, S);
+        hipLaunchKernelGGL((k_enum_tier<kLogMid, 1>), dim3(g(plan.g_mid)), dim3(64), 0, s, S);
+        hipLaunchKernelGGL(k_enum_slow, dim3(g(e->slow_waves)), dim3(64), 0, s, S, e->slow_tables);
+    };
+    for (int round = 0;; ++round) {
+        if (round == 0) {       // the non-doubles enumerator beside the doubles one
+            SCK(hipEventRecord(e->search_ev[3], s));
+            SCK(hipStreamWaitEvent(e->search_side, e->search_ev[3], 0));
+            hipLaunchKernelGGL(plan.kheavy, dim3(plan.g_heavy), dim3(64), 0, s, S);
+            hipLaunchKernelGGL(plan.klight, dim3(plan.g_light), dim3(64), 0, e->search_side, S);
+            SCK(hipEventRecord(e->search_ev[4], e->search_side));
+            SCK(hipStreamWaitEvent(s, e->search_ev[4], 0));
+            tiers();
+            SCK(hipEventRecord(e->search_ev[1], s));
+        } else {
+            const long long blocks = (long long)(S.cap / kBlk);
+            gcap = (int)(blocks / 16 > 1 ? (blocks / 16 < (1 << 30) ? blocks / 16 : (1 << 30)) : 1);
+            hipLaunchKernelGGL(plan.klist, dim3(g(plan.g_list)), dim3(64), 0, s, S);
+            tiers();
+        }
+        hipLaunchKernelGGL(plan.keval, dim3(plan.g_eval), dim3(plan.eval_threads), 0, s, E);
+        SCK(hipGetLastError());
+        if (round == 0) SCK(hipEventRecord(e->search_ev[2], s));
+        SCK(hipMemcpyAsync(hc, ctr, sizeof *hc, hipMemcpyDeviceToHost, s));
+        SCK(hipStreamSynchronize(s));
+        if (hc->bad) {                      // the lanes changed under the call (bgx.h stream ordering)
+            bgx_set_error("bgx_two_ply: the lanes' move lists changed under the call (stream ordering)");
+            return BGX_ESTATE;
+        }
+        if (round == 0) {
+            SCK(hipEventElapsedTime(&e->search_ms[0], e->search_ev[0], e->search_ev[1]));
+            SCK(hipEventElapsedTime(&e->search_ms[1], e->search_ev[1], e->search_ev[2]));
+        }
+        if (plan.dbg)
+            fprintf(stderr, "[bgx 2-ply] round %d: pool %llu/%zu, tier1 %d, tier2 %d, retry %d, leaves %llu\n", round,
+                    hc->cursor, (size_t)S.cap, hc->qcount[0] + hc->qcount[1], hc->qcount[2], hc->retry_count, hc->leaves);
+        if (hc->retry_count == 0) return BGX_OK;
+        if (round + 1 >= kMaxRounds) return BGX_ENOMEM;
+        // next round: the lost jobs become the explicit list, the pool starts over
+        SCK(hipMemcpyAsync(L.list.at(ws), L.retry.at(ws), (size_t)hc->retry_count * 4, hipMemcpyDeviceToDevice, s));
+        SCK(hipMemcpyAsync(&ctr->list_count, &ctr->retry_count, 4, hipMemcpyDeviceToDevice, s));
+        SCK(hipMemsetAsync(&ctr->cursor, 0, 8, s));
+        SCK(hipMemsetAsync(ctr->qcount, 0, 16, s));          // qcount[3], retry_count
+    }
+}
+
+// Test hook (BGX_2PLY_DUMP; tests/test_gpu_search.py): per-job minv at the prefix itself,
+// then .rp the row parts, .keys / .tags / .v the used pool and V per slot, .side the rows'
+// mover sides, .ml the jobs' final sub-move counts.
+static int dump_search_state(const std::string& prefix, const S2& S, const EvalArgs& E, size_t used, int rows, int jobs,
+                             size_t rowpart_floats, const float* rowpart) {
+    std::vector<char> host;
+    auto dump = [&](const void* dev, size_t bytes, const char* ext) -> hipError_t {
+        host.resize(bytes);
+        if (bytes)
+            if (const hipError_t err = hipMemcpy(host.data(), dev, bytes, hipMemcpyDeviceToHost); err != hipSuccess)
+                return err;
+        if (FILE* f = fopen((prefix + ext).c_str(), "wb")) { fwrite(host.data(), 1, bytes, f); fclose(f); }
+        return hipSuccess;
+    };
+    SCK(dump(E.minv, (size_t)jobs * 4, ""));
+    SCK(dump(rowpart, rowpart_floats * 4, ".rp"));
+    (void)dump(S.keys, used * 16, ".keys");
+    (void)dump(S.tags, used * 4, ".tags");
+    (void)dump(E.vdbg, used * 4, ".v");
+    (void)dump(E.rowside, (size_t)rows * 16, ".side");
+    (void)dump(E.maxlen, (size_t)jobs, ".ml");
+    return BGX_OK;
+}
+
+// frees a device allocation on every exit path
+struct DeviceFree {
+    void* p = nullptr;
+    ~DeviceFree() { if (p) (void)hipFree(p); }
+};
+
+// Stages 3-5 on a non-empty row set: the rows, the plan, the row parts, the pool, the
+// rounds and (tests) the dump.  On return minv holds every job's min.
+static int search_rows(const SearchCall& c, const TwoPlyLayout& L, const OnePlyRows& cand, int rows, int jobs) {
+    bgx_engine* e = c.e;
+    int rc = build_rows(c, L, cand, rows, jobs);
+    if (rc != BGX_OK) return rc;
+    EnumPlan plan(c.NT);
+    void* ws = e->search_ws.p;
+    Ctr* ctr = L.ctr.at(ws);
+    uint4* rowside = L.rowside.at<uint4>(ws);
+    float* rowpart = L.rowpart.at(ws);
+    const uint4* w1q = (const uint4*)(c.vpacked + 4);
+    if (plan.factored)
+        hipLaunchKernelGGL(plan.krowpart, dim3((rows + 127) / 128 < 8192 ? (rows + 127) / 128 : 8192), dim3(256), 0, c.s,
+                           rowside, &ctr->rows, w1q, rowpart);
+    plan.size_grids(e, jobs);
+    // the pool is counted in slots of 20 bytes (key + tag); it may be larger than asked
+    // for (kept from a bigger call), the call uses its own pool_slots of it
+    SCK(e->search_pool.reserve(plan.pool_slots * 20, 0, c.s, 0));
+    const size_t pcap = plan.pool_slots;
+    uint4* keys = (uint4*)e->search_pool.p;
+    uint32_t* tags = (uint32_t*)(keys + pcap);
+    const S2 S{L.rowrec.at(ws), 0, rows, keys, tags, &ctr->cursor, (unsigned long long)pcap, L.maxlen.at(ws),
+               &ctr->leaves, ctr->qcount, L.queues.at(ws), &ctr->retry_count, L.retry.at(ws), L.list.at(ws),
+               &ctr->list_count, e->a.err, plan.cap_light, plan.cap_heavy, plan.cap_mid, 3, 3, plan.barrow ? 1 : 0};
+    DeviceFree vdbg;
+    if (!plan.dump.empty()) {
+        SCK(hipMalloc(&vdbg.p, pcap * 4));
+        SCK(hipMemsetAsync(vdbg.p, 0, pcap * 4, c.s));
+    }
+    const EvalArgs E{keys, tags, &ctr->zero, &ctr->cursor, (unsigned long long)pcap, rowside, L.maxlen.at(ws),
+                     L.minv.at(ws), w1q, c.vpacked + 4 + kKB * slices(c.NT) * 64 * 4, c.value_bias,
+                     plan.factored ? rowpart : nullptr, (float*)vdbg.p};
+    Ctr hc;
+    rc = run_rounds(c, plan, L, S, E, &hc);
+    if (rc != BGX_OK || plan.dump.empty()) return rc;
+    return dump_search_state(plan.dump, S, E, hc.cursor < pcap ? (size_t)hc.cursor : pcap, rows, jobs, L.rowpart.count,
+                             rowpart);
+}
+
 // The 2-ply pipeline of bgx_two_ply_sel and bgx_two_ply_topk.  With a filter the rows are
 // the kept moves only: the 1-ply values (one_ply_rows), k_filter's kept counts and move
 // lists, the row layout scanned from the kept counts, and the row -> move map (row_move)
@@ -1811,275 +2052,34 @@ static int two_ply_search(bgx_engine* e, const float* vpacked, int32_t hidden, f
                           uint64_t* stats_host, void* stream) {
     if (!e || !vpacked || !best_out || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
     SCK(hipSetDevice(e->device));
-    hipStream_t s = (hipStream_t)stream;
-    EngineUse use(e, s);
+    const SearchCall c{e, (hipStream_t)stream, vpacked, hidden, value_tiles16(hidden), value_bias, sel};
+    EngineUse use(e, c.s);
     SCK(use.err);
-    Args& A = e->a;
-    const size_t B = (size_t)A.B;
     OnePlyRows cand{};
-    int64_t cand64 = 0;                               // candidate afterstates (stats)
-    if (filter) {
-        const int rc1 = one_ply_rows(e, vpacked, hidden, value_bias, sel, true, s, cand);
-        if (rc1 != BGX_OK) return rc1;
-        hipLaunchKernelGGL(k_filter, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, cand.lane_off, cand.total, cand.vrow,
-                           filter->top_k, filter->margin, cand.kept, cand.kept_move, q_out, filter->v1_out);
-        SCK(hipGetLastError());
-        SCK(hipMemcpyAsync(&cand64, cand.total, 8, hipMemcpyDeviceToHost, s));     // read after the scan's sync
-    }
-    // workspace head: [lane_off B i32][counters 256 B][overflow queues]
-    struct Ctr {
-        int64_t rows;
-        unsigned long long leaves, cursor;
-        int32_t qcount[3], retry_count, list_count, bad;    // bad: k_rows found a changed lane
-        unsigned long long zero;                      // start of the evaluated pool range
-    };
-    static_assert(sizeof(Ctr) <= 256, "counters");
-    const size_t o_ctr = align256(B * 4), o_q = o_ctr + 256, head = align256(o_q + (size_t)3 * kSlowQueue * 4);
-    auto grow = [&](size_t need) -> int {
-        if (e->search_ws_bytes >= need) return BGX_OK;
-        void* nw = nullptr;
-        SCK(hipStreamSynchronize(s));
-        SCK(hipMalloc(&nw, need + need / 4));
-        if (e->search_ws) SCK(hipFree(e->search_ws));
-        e->search_ws = nw;
-        e->search_ws_bytes = need + need / 4;
-        return BGX_OK;
-    };
-    int rc = grow(head);
+    int64_t cand64 = 0, rows64 = 0;                   // candidate afterstates (stats), rows
+    int rc = filter ? filter_candidates(c, *filter, q_out, cand, &cand64) : BGX_OK;
     if (rc != BGX_OK) return rc;
-    char* ws = (char*)e->search_ws;
-    SCK(hipMemsetAsync(ws + o_ctr, 0, 256, s));
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, A, sel, (int32_t*)ws, (int64_t*)(ws + o_ctr), 1,
-                       (const int32_t*)cand.kept);
-    SCK(hipGetLastError());
-    int64_t rows64 = 0;
-    SCK(hipMemcpyAsync(&rows64, ws + o_ctr, 8, hipMemcpyDeviceToHost, s));
-    SCK(hipStreamSynchronize(s));
+    TwoPlyLayout L((size_t)e->a.B);
+    rc = scan_rows(c, L, cand.kept, &rows64);
+    if (rc != BGX_OK) return rc;
     const int64_t jobs64 = rows64 * 21;
-    if (jobs64 >= (int64_t)0x1FFFFFFF) return BGX_EINVAL;     // job ids are 29-bit pool tags
     const int rows = (int)rows64, jobs = (int)jobs64;
-    // [row_lane rows][rowrec rows*64][rowside rows*16][minv jobs*4][maxlen jobs][list jobs*4][retry jobs*4]
-    // [rowpart rows*16*slices f32][row_move rows i32, with a filter]
-    const int NT = value_tiles16(hidden);
-    const size_t o_rl = head, o_rec = align256(o_rl + (size_t)rows * 4), o_side = align256(o_rec + (size_t)rows * 64),
-                 o_minv = align256(o_side + (size_t)rows * 16), o_ml = align256(o_minv + (size_t)jobs * 4),
-                 o_list = align256(o_ml + (size_t)jobs), o_retry = align256(o_list + (size_t)jobs * 4),
-                 o_rp = align256(o_retry + (size_t)jobs * 4),
-                 o_rm = align256(o_rp + (size_t)rows * 16 * slices(NT) * 4),
-                 need = filter ? align256(o_rm + (size_t)rows * 4) : o_rm;
-    if (e->search_ws_bytes < need) {
-        // keep the head (lane_off, counters) across the regrow
-        void* nw = nullptr;
-        SCK(hipMalloc(&nw, need + need / 4));
-        SCK(hipMemcpyAsync(nw, e->search_ws, head, hipMemcpyDeviceToDevice, s));
-        SCK(hipStreamSynchronize(s));
-        SCK(hipFree(e->search_ws));
-        e->search_ws = nw;
-        e->search_ws_bytes = need + need / 4;
-        ws = (char*)nw;
-    }
-    int32_t* lane_off = (int32_t*)ws;
-    Ctr* ctr = (Ctr*)(ws + o_ctr);
-    int32_t* row_lane = (int32_t*)(ws + o_rl);
-    uint8_t* rowrec = (uint8_t*)(ws + o_rec);
-    uint4* rowside = (uint4*)(ws + o_side);
-    int32_t* minv = (int32_t*)(ws + o_minv);
-    uint8_t* maxlen = (uint8_t*)(ws + o_ml);
-    int32_t* list = (int32_t*)(ws + o_list);
-    int32_t* retry = (int32_t*)(ws + o_retry);
-    float* rowpart = (float*)(ws + o_rp);
-    int32_t* row_move = filter ? (int32_t*)(ws + o_rm) : nullptr;
-
+    L.body((size_t)rows, (size_t)jobs, c.NT, filter != nullptr);
+    SCK(e->search_ws.reserve(L.bytes(), 25, c.s, L.head_bytes()));     // the head (lane_off, counters) is live
     if (rows > 0) {
-        if (filter)
-            hipLaunchKernelGGL(k_expand_kept, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows,
-                               cand.kept, cand.lane_off, cand.kept_move, row_lane, row_move);
-        else
-            hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows, row_lane);
-        SCK(hipMemsetAsync(minv, 0x7F, (size_t)jobs * 4, s));
-        SCK(hipMemsetAsync(maxlen, 0xFF, (size_t)jobs, s));
-        hipLaunchKernelGGL(k_rows, dim3((rows + 3) / 4 < 16384 ? (rows + 3) / 4 : 16384), dim3(256), 0, s, A, row_lane,
-                           lane_off, (const int32_t*)row_move, &ctr->rows, rowrec, rowside, (uint4*)nullptr, &ctr->bad);
-        SCK(hipGetLastError());
-        const bool barrow = bgx_dbg_int("BGX_2PLY_BARROW", 1) != 0;      // tests: 0 = the bar rows per job
-        S2 S{rowrec, 0, rows, nullptr, nullptr, &ctr->cursor, 0ull, maxlen, &ctr->leaves,
-             ctr->qcount, (int32_t*)(ws + o_q), &ctr->retry_count,
-             retry, list, &ctr->list_count, A.err, cap_fast<kLogLight>(), 0, cap_fast<kLogMid>(), 3, 3,
-             barrow ? 1 : 0};
-        // doubles enumerator: 512-slot dedup table with the revisit memo inside it, held to
-        // 128 VGPRs (4 waves/SIMD, +1.5 %).  Tests (BGX_2PLY_HEAVY = 9:0 / 10:0) run the
-        // exact alternatives without the memo (9:0) or with a 1,024-slot table (10:0): the
-        // same leaves, Q and choices (tests/test_gpu_search.py)
-        int hlog = 9, hmk = 2;
-        if (const std::string hv = bgx_dbg("BGX_2PLY_HEAVY"); !hv.empty()) {
-            hlog = atoi(hv.c_str());
-            const char* c = strchr(hv.c_str(), ':');
-            hmk = c ? atoi(c + 1) : 2;
-        }
-        void (*kheavy)(S2) = k_enum<9, 2, 1, 4>;
-        void (*klist)(S2) = k_enum<9, 2, 2, 4>;
-        if (hlog == 9 && hmk == 0) { kheavy = k_enum<9, 0, 1>; klist = k_enum<9, 0, 2>; }
-        else if (hlog == 10 && hmk == 0) { kheavy = k_enum<10, 0, 1>; klist = k_enum<10, 0, 2>; }
-        else { hlog = 9; hmk = 2; }
-        S.cap_heavy = (7 << hlog) / 8;
-        if (const std::string fs = bgx_dbg("BGX_2PLY_LDS_CAP"); !fs.empty()) {    // tests: force the overflow tiers ("first[:mid]")
-            S.cap_light = S.cap_heavy = S.cap_mid = atoi(fs.c_str());
-            if (const char* c = strchr(fs.c_str(), ':')) S.cap_mid = atoi(c + 1);
-        }
-        const bool dbg = !bgx_dbg("BGX_2PLY_DEBUG").empty();
-        const float* f16s = vpacked;
-        const uint4* w1q = (const uint4*)(f16s + 4);
-        // the root mover's part of X1 per row (the factored evaluator); BGX_2PLY_UNFACTORED
-        // (tests) evaluates every leaf over all 13 k-blocks instead
-        const bool factored = bgx_dbg("BGX_2PLY_UNFACTORED").empty();
-        if (factored)
-            hipLaunchKernelGGL(rowpart_kernel(NT), dim3((rows + 127) / 128 < 8192 ? (rows + 127) / 128 : 8192), dim3(256),
-                               0, s, rowside, &ctr->rows, w1q, rowpart);
-        EvalArgs E{nullptr, nullptr, &ctr->zero, &ctr->cursor, 0ull, rowside, maxlen, minv,
-                   w1q, f16s + 4 + kKB * slices(NT) * 64 * 4, value_bias, factored ? rowpart : nullptr, nullptr};
-        // the non-doubles enumerator: the row-level walk held to 80 VGPRs (6 waves/SIMD,
-        // +1.2 % over its natural 91)
-        void (*klight)(S2) = k_enum<kLogLight, -1, 3, 6>;
-        const int g_light = persistent_grid(e, klight, 32);
-        const int g_heavy = persistent_grid(e, kheavy, 32);
-        const int g_list = persistent_grid(e, klist, 32);
-        const int g_t0 = persistent_grid(e, k_enum_tier<10, 0>, 32);
-        const int g_mid = persistent_grid(e, k_enum_tier<kLogMid, 1>, 32);
-        // leaf pool: ~32 slots per job (mean ~19 survivors at mid-game positions);
-        // BGX_2PLY_POOL overrides (tests force retry rounds with a tiny pool)
-        // every resident wave may hold a partly filled block in each tier
-        size_t cap = (size_t)jobs * 32 + (size_t)(g_light + g_heavy + g_list + g_t0 + g_mid + e->slow_waves) * kBlk * 2;
-        if (const long long ps = bgx_dbg_int("BGX_2PLY_POOL", 0); ps > 0) cap = (size_t)ps;
-        cap = (cap + kBlk - 1) / kBlk * kBlk;
-        if (cap < (size_t)kBlk * 4) cap = (size_t)kBlk * 4;
-        if (cap > ((size_t)1 << 31)) cap = (size_t)1 << 31;
-        if (e->search_pool_cap < cap) {
-            SCK(hipStreamSynchronize(s));
-            if (e->search_pool) SCK(hipFree(e->search_pool));
-            e->search_pool = nullptr; e->search_pool_cap = 0;
-            SCK(hipMalloc(&e->search_pool, cap * 20));
-            e->search_pool_cap = cap;
-        }
-        const size_t pcap = cap;           // the pool may be larger (kept from a bigger call)
-        S.keys = (uint4*)e->search_pool;
-        S.tags = (uint32_t*)(S.keys + pcap);
-        E.keys = S.keys;
-        E.tags = S.tags;
-        S.cap = E.cap = (unsigned long long)pcap;
-        float* vdbg = nullptr;
-        const std::string dump = bgx_dbg("BGX_2PLY_DUMP");
-        if (!dump.empty()) {
-            SCK(hipMalloc(&vdbg, pcap * 4));
-            SCK(hipMemsetAsync(vdbg, 0, pcap * 4, s));
-            E.vdbg = vdbg;
-        }
-        const EvalPick keval = eval_kernel(NT);
-        int occ_eval = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_eval, keval.fn, keval.threads, 0) != hipSuccess ||
-            occ_eval <= 0)
-            occ_eval = 1;
-        const int g_eval = occ_eval * persistent_grid(e, keval.fn, 1);     // resident workgroups
-        if (!e->search_ev[0])
-            for (hipEvent_t& ev : e->search_ev) SCK(hipEventCreate(&ev));
-        if (!e->search_side) SCK(hipStreamCreateWithFlags(&e->search_side, hipStreamNonBlocking));
-        SCK(hipEventRecord(e->search_ev[0], s));
-        auto eval = [&](hipStream_t st) {
-            hipLaunchKernelGGL(keval.fn, dim3(g_eval), dim3(keval.threads), 0, st, E);
-        };
-        // retry rounds run few waves: every wave holding a block wastes its unused
-        // part, and a round must leave pool for its jobs to finish (progress with any pool)
-        int gcap = 1 << 30;
-        auto g = [&](int grid) { return grid < gcap ? grid : gcap; };
-        auto tiers = [&]() {
-            hipLaunchKernelGGL((k_enum_tier<10, 0>), dim3(g(g_t0)), dim3(64), 0, s, S);
-            hipLaunchKernelGGL((k_enum_tier<kLogMid, 1>), dim3(g(g_mid)), dim3(64), 0, s, S);
-            hipLaunchKernelGGL(k_enum_slow, dim3(g(e->slow_waves)), dim3(64), 0, s, S, e->slow_tables);
-        };
-        for (int round = 0;; ++round) {
-            if (round == 0) {       // the non-doubles enumerator beside the doubles one
-                SCK(hipEventRecord(e->search_ev[3], s));
-                SCK(hipStreamWaitEvent(e->search_side, e->search_ev[3], 0));
-                hipLaunchKernelGGL(kheavy, dim3(g_heavy), dim3(64), 0, s, S);
-                hipLaunchKernelGGL(klight, dim3(g_light), dim3(64), 0, e->search_side, S);
-                SCK(hipEventRecord(e->search_ev[4], e->search_side));
-                SCK(hipStreamWaitEvent(s, e->search_ev[4], 0));
-                tiers();
-                SCK(hipEventRecord(e->search_ev[1], s));
-                eval(s);
-            } else {
-                const long long blocks = (long long)(pcap / kBlk);
-                gcap = (int)(blocks / 16 > 1 ? (blocks / 16 < (1 << 30) ? blocks / 16 : (1 << 30)) : 1);
-                hipLaunchKernelGGL(klist, dim3(g(g_list)), dim3(64), 0, s, S);
-                tiers();
-                eval(s);
-            }
-            SCK(hipGetLastError());
-            if (round == 0) SCK(hipEventRecord(e->search_ev[2], s));
-            Ctr hc;
-            SCK(hipMemcpyAsync(&hc, ctr, sizeof hc, hipMemcpyDeviceToHost, s));
-            SCK(hipStreamSynchronize(s));
-            const int32_t nretry = hc.retry_count;
-            if (hc.bad) {                      // the lanes changed under the call (bgx.h stream ordering)
-                bgx_set_error("bgx_two_ply: the lanes' move lists changed under the call (stream ordering)");
-                return BGX_ESTATE;
-            }
-            if (round == 0) {
-                SCK(hipEventElapsedTime(&e->search_ms[0], e->search_ev[0], e->search_ev[1]));
-                SCK(hipEventElapsedTime(&e->search_ms[1], e->search_ev[1], e->search_ev[2]));
-            }
-            if (dbg)
-                fprintf(stderr, "[bgx 2-ply] round %d: pool %llu/%zu, tier1 %d, tier2 %d, retry %d, leaves %llu\n", round,
-                        hc.cursor, pcap, hc.qcount[0] + hc.qcount[1], hc.qcount[2], hc.retry_count, hc.leaves);
-            if (nretry == 0) {
-                // test hook (tests/test_gpu_search.py): per-job minv, row parts, the pool, V per slot
-                if (!dump.empty()) {
-                    const char* dp = dump.c_str();
-                    int32_t* hm = (int32_t*)malloc((size_t)jobs * 4);
-                    SCK(hipMemcpy(hm, minv, (size_t)jobs * 4, hipMemcpyDeviceToHost));
-                    FILE* f = fopen(dp, "wb");
-                    if (f) { fwrite(hm, 4, (size_t)jobs, f); fclose(f); }
-                    free(hm);
-                    const size_t nrp = (size_t)rows * 16 * slices(NT);
-                    float* hr = (float*)malloc(nrp * 4);
-                    SCK(hipMemcpy(hr, rowpart, nrp * 4, hipMemcpyDeviceToHost));
-                    char nm[512];
-                    snprintf(nm, sizeof nm, "%s.rp", dp);
-                    f = fopen(nm, "wb");
-                    if (f) { fwrite(hr, 4, nrp, f); fclose(f); }
-                    free(hr);
-                    const size_t used = hc.cursor < pcap ? hc.cursor : pcap;
-                    auto dumpd = [&](const void* d, size_t bytes, const char* ext) {
-                        void* hb = malloc(bytes);
-                        if (hipMemcpy(hb, d, bytes, hipMemcpyDeviceToHost) == hipSuccess) {
-                            snprintf(nm, sizeof nm, "%s.%s", dp, ext);
-                            if (FILE* g = fopen(nm, "wb")) { fwrite(hb, 1, bytes, g); fclose(g); }
-                        }
-                        free(hb);
-                    };
-                    dumpd(S.keys, used * 16, "keys");
-                    dumpd(S.tags, used * 4, "tags");
-                    dumpd(vdbg, used * 4, "v");
-                    dumpd(rowside, (size_t)rows * 16, "side");
-                    dumpd(maxlen, (size_t)jobs, "ml");
-                    (void)hipFree(vdbg);
-                }
-                break;
-            }
-            if (round + 1 >= kMaxRounds) return BGX_ENOMEM;
-            // next round: the lost jobs become the explicit list, the pool starts over
-            SCK(hipMemcpyAsync(list, retry, (size_t)nretry * 4, hipMemcpyDeviceToDevice, s));
-            SCK(hipMemcpyAsync(&ctr->list_count, &ctr->retry_count, 4, hipMemcpyDeviceToDevice, s));
-            SCK(hipMemsetAsync(&ctr->cursor, 0, 8, s));
-            SCK(hipMemsetAsync(ctr->qcount, 0, 16, s));          // qcount[3], retry_count
-        }
+        rc = search_rows(c, L, cand, rows, jobs);
+        if (rc != BGX_OK) return rc;
     }
-    hipLaunchKernelGGL(k_two_ply_reduce, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, lane_off, &ctr->rows, minv,
-                       (const int32_t*)cand.kept, (const int32_t*)row_move, best_out, bestq_out, q_out);
+    void* ws = e->search_ws.p;
+    Ctr* ctr = L.ctr.at(ws);
+    hipLaunchKernelGGL(k_two_ply_reduce, dim3((e->a.B + 3) / 4), dim3(256), 0, c.s, e->a, sel, L.lane_off.at(ws),
+                       &ctr->rows, L.minv.at(ws), (const int32_t*)cand.kept,
+                       (const int32_t*)(filter ? L.row_move.at(ws) : nullptr), best_out, bestq_out, q_out);
     SCK(hipGetLastError());
     if (stats_host) {
         unsigned long long lv = 0;
-        SCK(hipMemcpyAsync(&lv, &ctr->leaves, 8, hipMemcpyDeviceToHost, s));
-        SCK(hipStreamSynchronize(s));
+        SCK(hipMemcpyAsync(&lv, &ctr->leaves, 8, hipMemcpyDeviceToHost, c.s));
+        SCK(hipStreamSynchronize(c.s));
         stats_host[0] = lv;
         stats_host[1] = (uint64_t)jobs64;
         stats_host[2] = (uint64_t)rows64;

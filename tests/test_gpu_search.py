@@ -385,3 +385,56 @@ def test_one_ply_selfplay_c2_batch():
             assert np.abs(vn[i, :k] - ref).max() < TOL, (t, i)
         eng.step(best, want_obs=False, want_info=False)
     assert eng.error() == 0
+
+
+def test_two_ply_workspace_reuse():
+    """One engine's search buffers across calls of changing size: 1-ply, 2-ply on 8 selected
+    lanes, 2-ply on all lanes (both workspace regrows, the second with a live head), the
+    filtered 2-ply, the 8 lanes again (buffers now larger than needed), 1-ply again.  Every
+    call gives, bit for bit on the lanes it wrote, what the same call gives on a fresh
+    engine holding the same records: the choice, its value, V or Q over the legal moves
+    (lanes without a legal move included) and the statistics."""
+    import bgx
+    from bgx.policy import PolicyNet
+    from bgx.search import ValueHead, one_ply, two_ply
+    torch.manual_seed(4)
+    vh = ValueHead(PolicyNet(hidden_size=40).cuda())
+    B, M = 256, 500
+    eng = bgx.Engine(batch=B, max_moves=M, seed=31, dice="philox", auto_reset=True)
+    eng.reset(want_obs=False)
+    rng = np.random.RandomState(6)
+    for _ in range(30):
+        nm = eng.n_moves().cpu().numpy()
+        eng.step(torch.from_numpy(np.array([rng.randint(k) if k else 0 for k in nm], np.int32)).cuda(),
+                 want_obs=False, want_info=False)
+    rec = eng.records()
+    n = eng.n_moves().long()
+    legal = torch.arange(M, device="cuda")[None, :] < n[:, None]
+    sel8 = torch.zeros(B, dtype=torch.uint8, device="cuda")
+    sel8[torch.from_numpy(rng.choice(B, 8, replace=False)).cuda()] = 1
+
+    def outs():      # defined entries on the lanes a selected call does not write
+        return (torch.full((B,), -7, dtype=torch.int32, device="cuda"), torch.full((B,), -7.0, device="cuda"),
+                torch.full((B, M), -7.0, device="cuda"))
+
+    calls = [("one_ply", lambda e: one_ply(e, vh, out=outs()), None),
+             ("two_ply sel", lambda e: two_ply(e, vh, sel=sel8, out=outs()), sel8),
+             ("two_ply", lambda e: two_ply(e, vh, out=outs()), None),
+             ("two_ply top_k", lambda e: two_ply(e, vh, out=outs(), top_k=2), None),
+             ("two_ply sel again", lambda e: two_ply(e, vh, sel=sel8, out=outs()), sel8),
+             ("one_ply again", lambda e: one_ply(e, vh, out=outs()), None)]
+    for name, call, sel in calls:
+        got = call(eng)
+        fresh = bgx.Engine(batch=B, max_moves=M, seed=99, dice="philox", auto_reset=True)
+        fresh.set_lanes(rec)
+        assert torch.equal(fresh.n_moves().long(), n), name
+        want = call(fresh)
+        wrote = torch.ones(B, dtype=torch.bool, device="cuda") if sel is None else sel.bool()
+        assert torch.equal(got[0][wrote], want[0][wrote]), name
+        assert torch.equal(got[1].view(torch.int32)[wrote], want[1].view(torch.int32)[wrote]), name
+        m = legal & wrote[:, None]
+        assert torch.equal(got[2].view(torch.int32)[m], want[2].view(torch.int32)[m]), name
+        if len(got) > 3:
+            assert got[3] == want[3], (name, got[3], want[3])
+            assert got[3]["jobs"] == 21 * got[3]["afterstates"] and got[3]["leaves"] > 0, name
+        assert eng.error() == 0 and fresh.error() == 0, name
