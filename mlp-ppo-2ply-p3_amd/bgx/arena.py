@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .engine import Engine, R_CUR, R_NM0, R_NM1, _ptr
+from .engine import Engine, R_CUR, R_NM0, R_NM1, _ptr, _stream
 
 # tally int64[16] (include/bgx.h bgx_arena_field); entries 14, 15 stay zero
 FIELDS = ("games", "wins_a", "wins_b", "points_a", "points_b", "gammons_a", "gammons_b", "backgammons_a",
@@ -48,10 +48,6 @@ def summarize(tally, steps: int, unfinished: int) -> dict:
              ppg_a=(r["points_a"] - r["points_b"]) / g if g > 0 else 0.0,
              win_rate_stderr=math.sqrt(max(p * (1.0 - p), 0.0) / g) if g > 0 else 0.0)
     return r
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 # ------------------------------------------------------------------ players --

@@ -24,6 +24,11 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+def _stream(dev):
+    """The current torch stream of `dev` as the C ABI's hipStream_t argument."""
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
 def validate_starts(records: torch.Tensor) -> None:
     """Raise ValueError naming the first bad lane of a start table (uint8[n, 64] records in the
     lane-record layout, any device) and the reason: the rules of bgx_engine_set_starts."""

@@ -12,11 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .engine import Engine, _ptr
-
-
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+from .engine import Engine, _ptr, _stream
 
 
 class ValueHead:

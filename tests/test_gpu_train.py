@@ -346,20 +346,21 @@ def test_update_redone_after_skipped_step(monkeypatch):
     device, the host copy then differs after the update, and the update is redone
     from its snapshot with per-epoch get_scale() -- the same weights, Adam state and
     scale as the exact path run directly."""
+    import bgx.ppo_epoch as E
     import bgx.train as T
     res = []
     for hinted in (True, False):
         tr = T.PPOTrainer(batch=2048, horizon=4, seed=3, chunk=8192)
         tr.rollout()
         calls = {"n": 0}
-        orig = T.adam_step
+        orig = E.adam_step
 
         def inj(opt, sc, orig=orig, calls=calls):
             calls["n"] += 1
             if calls["n"] % 4 == 2:                    # epoch 2 of every pass
                 opt.param_groups[0]["params"][0].grad[0, 0] = float("inf")
             return orig(opt, sc)
-        monkeypatch.setattr(T, "adam_step", inj)
+        monkeypatch.setattr(E, "adam_step", inj)        # the module whose epoch calls it
         if not hinted:
             monkeypatch.setattr(T.PPOTrainer, "_scale_state", lambda self: None)
         tr.update()

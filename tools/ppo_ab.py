@@ -1,5 +1,5 @@
 """A/B of PPO iteration variants in one process (experiments): for each variant (a
-comma-separated list of bgx.train module attributes set to 0/1), a fresh PPOTrainer
+comma-separated list of bgx.ppo_epoch / bgx.train module attributes set to 0/1), a fresh PPOTrainer
 (B = 65,536, T = 32) runs 1 warm + N timed iterations; prints the mean rollout / update
 seconds and env steps/s.  Variants alternate over ROUNDS rounds.
 
@@ -15,13 +15,15 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "mlp-ppo-2ply-p3_amd")]
+import bgx.ppo_epoch as E  # noqa: E402
 import bgx.train as T  # noqa: E402
 
 
 def run(spec, n):
     for kv in filter(None, spec.split(",")):
         k, v = kv.split("=")
-        setattr(T, k, type(getattr(T, k))(int(v)))
+        mod = E if hasattr(E, k) else T           # the module whose code reads the attribute
+        setattr(mod, k, type(getattr(mod, k))(int(v)))
     tr = T.PPOTrainer(batch=65536, horizon=32, seed=11)
     tr.iteration()
     torch.cuda.synchronize()

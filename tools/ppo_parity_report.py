@@ -1,6 +1,6 @@
 """Print the measured margins of the PPO-update parity tests (GPU): the trainer's
 update vs golden G6b (fp32) / G6c (fp16), and the fused fp16 epoch vs the fp32
-torch epoch at 2^21 rows with the per-row gradient scale of bgx.train (REF_ROWS)
+torch epoch at 2^21 rows with the per-row gradient scale of bgx.ppo_epoch (REF_ROWS)
 and with the old scale / n (REF_ROWS = inf)."""
 import copy
 import json
@@ -13,6 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mlp-ppo-2ply-p3_amd"), os.path.join(ROOT, "tests")]
 
+import bgx.ppo_epoch as E  # noqa: E402
 import bgx.train as T  # noqa: E402
 from bgx.engine import encode  # noqa: E402
 from bgx.ppo import global_normalize  # noqa: E402
@@ -41,7 +42,7 @@ def golden_margins():
 
 
 def large_batch(ref_rows):
-    T.REF_ROWS = ref_rows
+    E.REF_ROWS = ref_rows              # the module whose epochs read it
     torch.manual_seed(0)
     tr = T.PPOTrainer(batch=65536, horizon=32, seed=9)
     tr.rollout()
