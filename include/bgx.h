@@ -516,7 +516,7 @@ int64_t bgx_ppo_gw1_workspace(int32_t m);
 int bgx_ppo_gw1(const void* dh_dev, const uint8_t* records_dev, int32_t m, int32_t hidden, float* workspace_dev,
                 float* gw1_dev, void* stream);
 
-/* Discounted returns of a [T][B] rollout per game lane (the reference's
+/* csrc/bg_returns.hip.  Discounted returns of a [T][B] rollout per game lane (the reference's
  * compute_returns, ppo_agent.py:206-216, restated per lane: R_t = r_t + gamma R_{t+1},
  * reset where done): out [T][B] fp32, the same fp32 roundings as r + gamma * R. */
 int bgx_lane_returns(const float* rewards_dev, const uint8_t* dones_dev, int32_t T, int32_t B, float gamma,
@@ -586,7 +586,7 @@ int bgx_episode_stats(const float* rewards_dev, const uint8_t* dones_dev, const 
  * ppo_agent.py:235-266): row i of each output = row perm[i] of its input, for the
  * 64-byte records and the four per-row fields (action, old log-prob, return,
  * advantage).  One kernel (16-byte copies of the records). */
-/* The PPO optimizer step: torch.optim.Adam(fused=True) (ADAM_MODE::ORIGINAL; no weight
+/* csrc/bg_adam.hip.  The PPO optimizer step: torch.optim.Adam(fused=True) (ADAM_MODE::ORIGINAL; no weight
  * decay, amsgrad or maximize) as GradScaler.step + GradScaler.update drive it
  * (ppo_agent.py:302-305 `scaler.step(self.optimizer); scaler.update()`), for up to 8
  * fp32 tensors: params/grads/exp_avg/exp_avg_sq device pointers, steps = each tensor's

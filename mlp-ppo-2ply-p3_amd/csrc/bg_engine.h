@@ -477,58 +477,74 @@ struct DeviceBuf {
 
 // Engine object behind the C ABI's opaque bgx_engine*.
 struct bgx_engine {
-    bool step_debug = false;        // BGX_STEP_DEBUG (bgx_debug_option) at creation: per-step tier sizes
-    int device;
-    bg::Args a;
-    uint4* slow_tables;
-    int slow_waves;
-    int32_t* perm;        // dispatch order for k_step (Philox mode), built by k_order
-    bool perm_valid;
-    int32_t* order_cnt;   // k_order_count -> k_order_scatter, [B/256+1][8 sub-lists][kClasses]
+    bool step_debug{false};        // BGX_STEP_DEBUG (bgx_debug_option) at creation: per-step tier sizes
+    int device{0};
+    bg::Args a{};
+    uint4* slow_tables{nullptr};
+    int slow_waves{bg::kSlowWaves};
+    int32_t* perm{nullptr};        // dispatch order for k_step (Philox mode), built by k_order
+    bool perm_valid{false};
+    int32_t* order_cnt{nullptr};   // k_order_count -> k_order_scatter, [B/256+1][8 sub-lists][kClasses]
+    hipStream_t step_side{nullptr};    // the light launch beside the heavy one, and the next dispatch order
+    hipEvent_t step_ev[4]{};         // fork, light done, heavy done, dispatch order done
+    bool order_pending{false};         // the next step's launches wait for step_ev[3] (join_order)
+    bool step_fork{true};              // bgx_engine_set_fork: light launch + dispatch order on step_side
     // overflow counters, two 16-byte sets: a Philox step uses set `ovf_parity`
     // (Args::ovf_count) and its k_order_count zeroes the other set for the next
     // step, so the step needs no separate memset launch
-    hipStream_t step_side;      // the light launch beside the heavy one, and the next dispatch order
-    hipEvent_t step_ev[4];      // fork, light done, heavy done, dispatch order done
-    bool order_pending;         // the next step's launches wait for step_ev[3]
-    bool step_fork;             // bgx_engine_set_fork: light launch + dispatch order on step_side
-    int32_t* ovf_base;
-    int ovf_parity;
-    bool ovf_next_zeroed;
-    uint64_t seed;
-    uint8_t* starts;      // the start table's storage, [B][64] (Args::starts points here while a table is set)
+    int32_t* ovf_base{nullptr};
+    int ovf_parity{0};
+    bool ovf_next_zeroed{false};
+    uint64_t seed{0};
+    uint8_t* starts{nullptr};      // the start table's storage, [B][64] (Args::starts points here while a table is set)
     // bg_search.hip workspaces (grown on demand; bg_workspace.h has their layouts)
     DeviceBuf search_ws;
-    DeviceBuf search_pool;    // 2-ply leaf pool: keys [slots] x 16 B, then tags [slots] x 4 B
-    hipStream_t search_side;  // 2-ply: second stream for the concurrent enumerator (created on demand)
-    hipEvent_t search_ev[5];  // 2-ply phase marks: start, enumerated, evaluated, fork, join
-    float search_ms[2];       // last bgx_two_ply call, round 0: enumeration ms, evaluation ms
-    DeviceBuf oneply_ws;      // bgx_one_ply workspace (rows sized for B x max_moves)
+    DeviceBuf search_pool;              // 2-ply leaf pool: keys [slots] x 16 B, then tags [slots] x 4 B
+    hipStream_t search_side{nullptr};  // 2-ply: second stream for the concurrent enumerator (created on demand)
+    hipEvent_t search_ev[5]{};       // 2-ply phase marks: start, enumerated, evaluated, fork, join
+    float search_ms[2]{};            // last bgx_two_ply call, round 0: enumeration ms, evaluation ms
+    DeviceBuf oneply_ws;                // bgx_one_ply workspace (rows sized for B x max_moves)
     // Cross-stream ordering of the engine's own calls (bgx.h "Stream ordering"): the end of
     // the last eager call that touched the engine's device state (lanes, moves, overflow
     // queues and tables, search workspace) and the stream it ran on.  A call on another
     // stream waits for it first.
-    hipEvent_t use_ev;
-    hipStream_t use_stream;
-    bool use_valid;           // use_ev marks the last call (false: none yet, or it was captured)
+    hipEvent_t use_ev{nullptr};
+    hipStream_t use_stream{nullptr};
+    bool use_valid{false};             // use_ev marks the last call (false: none yet, or it was captured)
 };
 
-// RAII guard of one engine call on stream s: the constructor makes s wait for the engine's
-// previous call when that ran on another stream; the destructor marks this call's end.  A
-// call made while s is being captured into a HIP graph neither waits nor marks (its work
-// runs when the graph is launched; the launch stream orders it): the guard then forgets the
-// last mark, so the next eager call on any stream does not wait on a stale event.
-struct EngineUse {
+// Stream s waits for a dispatch order still running on the side stream (the order pass of
+// the last forked step: it writes perm, cls, the counters' roll cache and the other set of
+// overflow counters).  Only the calls that read or rewrite those join; the rest run beside it.
+inline hipError_t join_order(bgx_engine* e, hipStream_t s) {
+    if (!e->order_pending) return hipSuccess;
+    const hipError_t err = hipStreamWaitEvent(s, e->step_ev[3], 0);
+    if (err == hipSuccess) e->order_pending = false;
+    return err;
+}
+
+// RAII guard of one engine call on stream s; the entry point returns `err` when it is set.
+// The constructor selects the engine's device, makes s wait for the engine's previous call
+// when that ran on another stream and, with `join`, for a pending dispatch order
+// (join_order); the destructor marks this call's end.  A call made while s is being captured
+// into a HIP graph neither waits for the previous call nor marks (its work runs when the
+// graph is launched; the launch stream orders it): the guard then forgets the last mark, so
+// the next eager call on any stream does not wait on a stale event.
+struct EngineCall {
     bgx_engine* e;
     hipStream_t s;
-    bool captured;
+    bool entered = false, captured = false;
     hipError_t err;
-    EngineUse(bgx_engine* e_, hipStream_t s_) : e(e_), s(s_), captured(false), err(hipSuccess) {
+    EngineCall(bgx_engine* e_, hipStream_t s_, bool join = false) : e(e_), s(s_), err(hipSetDevice(e_->device)) {
+        if (err != hipSuccess) return;
+        entered = true;
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) captured = true;
         if (!captured && e->use_valid && e->use_stream != s) err = hipStreamWaitEvent(s, e->use_ev, 0);
+        if (err == hipSuccess && join) err = join_order(e, s);
     }
-    ~EngineUse() {
+    ~EngineCall() {
+        if (!entered) return;
         if (captured) { e->use_valid = false; return; }
         if (!e->use_ev && hipEventCreateWithFlags(&e->use_ev, hipEventDisableTiming) != hipSuccess) {
             e->use_ev = nullptr;

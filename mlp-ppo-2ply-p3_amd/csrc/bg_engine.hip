@@ -25,6 +25,7 @@
 
 #include "bg_engine.h"
 #include "bg_debug.h"
+#include "bg_host.h"
 #include <map>
 
 using namespace bg;
@@ -720,18 +721,15 @@ __global__ __launch_bounds__(256) void k_random_act(const uint8_t* recs, int n, 
     act[i] = (int32_t)(((h >> 32) * (uint64_t)cnt) >> 32);      // 0 when the lane has no legal move
 }
 
-thread_local std::string g_err;
-
-int fail(hipError_t e, int code = BGX_EDEVICE) {
-    g_err = hipGetErrorString(e);
-    return code;
-}
+thread_local std::string g_err;      // bgx_last_error()
 
 }  // namespace
 
-
-// error hooks for the other translation units (bg_search.hip, bg_ppo*.hip)
-int bgx_internal_fail(hipError_t e) { return fail(e); }
+// the error hooks of every translation unit (bg_host.h)
+int bgx_internal_fail(hipError_t e, int code) {
+    g_err = hipGetErrorString(e);
+    return code;
+}
 void bgx_set_error(const char* msg) { g_err = msg; }
 // the explicit debug options (bg_debug.h, bgx_debug_option)
 static std::mutex g_dbg_mu;
@@ -746,11 +744,9 @@ long long bgx_dbg_int(const char* name, long long dflt) {
     return v.empty() ? dflt : strtoll(v.c_str(), nullptr, 10);
 }
 
-#define CK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return fail(_e); } while (0)
 // the per-position kernels (reset, standalone movegen, regeneration) with the
 // 512-slot dedup table
-#define LAUNCH_LOG(e, K, grid, s, ...) hipLaunchKernelGGL(K<9>, grid, dim3(64), 0, s, __VA_ARGS__)
-#define CKL() do { hipError_t _e = hipGetLastError(); if (_e != hipSuccess) return fail(_e); } while (0)
+#define LAUNCH_LOG(K, grid, s, ...) hipLaunchKernelGGL(K<9>, grid, dim3(64), 0, s, __VA_ARGS__)
 
 static void launch_order(bgx_engine* e, hipStream_t s) {
     const int nblk = (e->a.B + 1023) / 1024, ncnt = (e->a.B + kCountThreads - 1) / kCountThreads;
@@ -762,14 +758,30 @@ static void launch_order(bgx_engine* e, hipStream_t s) {
     e->perm_valid = true;
 }
 
-static void launch_step(hipStream_t s, const Args& a, int grid, const int32_t* actions, float* obs, float* reward,
-                        uint8_t* done, int32_t* info, int base = 0) {
+// bgx_step's device arguments
+struct StepIo {
+    const int32_t* actions;
+    float *obs, *reward;
+    uint8_t* done;
+    int32_t* info;
+};
+
+// The first `grid` positions of the dispatch order (every lane when there is no order).
+static void launch_heavy(hipStream_t s, const Args& a, int grid, const StepIo& io) {
     if (grid <= 0) return;
     // the split's doubles prefix: a 512-slot table and no revisit memo (8 KB of LDS):
     // the doubles walks that cannot bear off use no table at all, so occupancy
     // (VGPR-bound, 4 waves/SIMD) beats a bigger table (C3: 1,024 slots + memo 242 M/s,
     // 512 slots + memo inside 284 M/s, no memo 288 M/s; measured round 2)
-    hipLaunchKernelGGL((k_step<0, 9, 0>), dim3(grid), dim3(64), 0, s, a, actions, obs, reward, done, info, base);
+    hipLaunchKernelGGL((k_step<0, 9, 0>), dim3(grid), dim3(64), 0, s, a, io.actions, io.obs, io.reward, io.done,
+                       io.info, 0);
+}
+
+// The order's positions from `heavy` on: a 256-slot table, no memo, no doubles code (4 KB,
+// 49 VGPRs: the hardware wave limit, ~5x the resident waves; doubles go to the overflow tiers).
+static void launch_light(hipStream_t s, const Args& a, int heavy, const StepIo& io) {
+    hipLaunchKernelGGL((k_step<0, 8, 0, true>), dim3(a.B - heavy), dim3(64), 0, s, a, io.actions, io.obs, io.reward,
+                       io.done, io.info, heavy);
 }
 
 // Doubles share of the dispatch order (Philox mode): the expected doubles
@@ -792,7 +804,129 @@ static int slow_path(bgx_engine* e, hipStream_t s, int src, const int8_t* boards
     else
         hipLaunchKernelGGL(k_movegen_over<1>, dim3(e->slow_waves), dim3(64), 0, s, e->a, boards, players, dice, cap,
                            nm, nt, moves, e->slow_tables);
-    CKL();
+    return bgx_launch_status();
+}
+
+// The engine's fixed device buffers: bgx_engine_create allocates them in this order (bytes
+// 0: not in this configuration) and zeroes the marked ones, bgx_engine_destroy frees them.
+struct EngineBuf {
+    void** p;
+    size_t bytes;
+    bool zero;
+};
+static std::vector<EngineBuf> engine_bufs(bgx_engine* e, bool stamps, bool order) {
+    Args& A = e->a;
+    const size_t B = (size_t)A.B;
+    const bool shared = A.dice_mode == BGX_DICE_MT_SHARED;
+    return {
+        {(void**)&A.lanes, B * 64, true},
+        {(void**)&A.moves, B * (size_t)A.max_moves * 8, false},
+        {(void**)&A.n_total, B * 4, true},
+        {(void**)&A.mt, (A.dice_mode == BGX_DICE_MT_LANE ? B : 1) * kMtWords * 4, false},
+        {(void**)&A.ctr, B * 8, true},
+        {(void**)&A.shared_rolls, B * 4, false},
+        {(void**)&e->ovf_base, 32, true},
+        {(void**)&A.ovf_queue, B * 4, false},
+        {(void**)&A.err, 16, true},
+        {(void**)&e->starts, shared ? 0 : B * 64, false},                   // bgx_engine_set_starts
+        {(void**)&e->slow_tables, (size_t)kSlowWaves * ((size_t)16 << kLogSlotsSlow), false},
+        {(void**)&A.stamps, stamps ? B * 16 : 0, false},
+        {(void**)&e->perm, order ? B * 4 : 0, false},
+        {(void**)&A.cls, order ? B : 0, true},
+        {(void**)&A.pre, order ? B : 0, true},
+        {(void**)&e->order_cnt, order ? (B / kCountThreads + 1) * kXcd * kClasses * 4 : 0, false},
+    };
+}
+
+// This call's overflow counters (Args::ovf_count), zero on stream s before its launches.
+// With `rotate` (bgx_reset, bgx_step: the calls an order pass follows) the set that the
+// last order pass zeroed is taken when there is one; every other case zeroes the current set.
+static hipError_t fresh_ovf_counters(bgx_engine* e, hipStream_t s, bool rotate) {
+    if (rotate && e->ovf_next_zeroed) {
+        e->ovf_parity ^= 1;
+        e->a.ovf_count = e->ovf_base + 4 * e->ovf_parity;
+        e->ovf_next_zeroed = false;
+        return hipSuccess;
+    }
+    return hipMemsetAsync(e->a.ovf_count, 0, 16, s);
+}
+
+// SHARED dice: apply, the one stream's dice for every lane that needs a roll, advance.
+static void step_shared_dice(const Args& A, const StepIo& io, hipStream_t s) {
+    hipLaunchKernelGGL((k_step<1, 9>), dim3(A.B), dim3(64), 0, s, A, io.actions, io.obs, io.reward, io.done, io.info, 0);
+    hipLaunchKernelGGL(k_shared_dice, dim3(1), dim3(64), 0, s, A);
+    hipLaunchKernelGGL((k_step<2, 9>), dim3(A.B), dim3(64), 0, s, A, io.actions, io.obs, io.reward, io.done, io.info, 0);
+}
+
+// The next dispatch order on the side stream once both launches of a forked step have
+// written their pre-class bytes and counters: it runs beside stream s's overflow tiers and
+// the caller's next policy kernel instead of before them (neither touches pre, cls, perm or
+// the counters); the order pass writes the counters' roll cache, so the next bgx_step and
+// every other call that reads or rewrites counters joins it (join_order) before its own
+// launches.
+static int order_on_side(bgx_engine* e, hipStream_t s) {
+    BGX_CK(hipEventRecord(e->step_ev[2], s));
+    BGX_CK(hipStreamWaitEvent(e->step_side, e->step_ev[2], 0));
+    launch_order(e, e->step_side);
+    BGX_CK(hipEventRecord(e->step_ev[3], e->step_side));
+    e->order_pending = true;
+    return BGX_OK;
+}
+
+// Per-lane dice.  Split dispatch (Philox mode, once there is a dispatch order): the
+// predicted-doubles prefix of the order in the heavy launch, the rest in the light one,
+// then the next order.  Forked (bgx_engine_set_fork), the light launch and the order pass
+// run on the side stream beside the heavy launch (filling the CUs its tail leaves idle),
+// fork-join on events; linear, everything is in plain stream order -- no cross-stream wait
+// that a serializing tool (profiler) or a shared hardware queue could deadlock.
+static int step_lane_dice(bgx_engine* e, const StepIo& io, hipStream_t s) {
+    Args a = e->a;
+    a.perm = e->perm_valid ? e->perm : nullptr;
+    const int heavy = a.perm ? heavy_grid(a.B, a.xcd != 0) : a.B;
+    if (heavy < a.B && e->step_fork) {
+        if (!e->step_side) {
+            BGX_CK(hipStreamCreateWithFlags(&e->step_side, hipStreamNonBlocking));
+            for (hipEvent_t& ev : e->step_ev) BGX_CK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        }
+        BGX_CK(hipEventRecord(e->step_ev[0], s));
+        BGX_CK(hipStreamWaitEvent(e->step_side, e->step_ev[0], 0));
+        launch_heavy(s, a, heavy, io);
+        launch_light(e->step_side, a, heavy, io);
+        BGX_CK(hipEventRecord(e->step_ev[1], e->step_side));
+        if (a.cls) {
+            const int rc = order_on_side(e, s);
+            if (rc != BGX_OK) return rc;
+        }
+        BGX_CK(hipStreamWaitEvent(s, e->step_ev[1], 0));
+    } else {
+        launch_heavy(s, a, heavy, io);
+        if (heavy < a.B) launch_light(s, a, heavy, io);
+        if (a.cls) launch_order(e, s);
+    }
+    return BGX_OK;
+}
+
+// BGX_STEP_DEBUG: the overflow-tier queue size of this step and its first lanes, to stderr.
+static int step_debug_dump(bgx_engine* e, hipStream_t s) {
+    const Args& A = e->a;
+    int32_t q[2] = {0, 0};
+    BGX_CK(hipMemcpyAsync(q, A.ovf_count, 8, hipMemcpyDeviceToHost, s));
+    BGX_CK(hipStreamSynchronize(s));
+    fprintf(stderr, "[bgx step] overflow queue %d of %d lanes\n", q[0], A.B);
+    for (int i = 0; i < q[0] && i < 4; ++i) {
+        int32_t gi = 0;
+        uint8_t rec[64];
+        BGX_CK(hipMemcpy(&gi, A.ovf_queue + i, 4, hipMemcpyDeviceToHost));
+        BGX_CK(hipMemcpy(rec, A.lanes + (size_t)gi * 64, 64, hipMemcpyDeviceToHost));
+        int own = 0, outside = 0;
+        const int pl = rec[52];
+        for (int p = 0; p < 24; ++p) {
+            own += rec[pl * 24 + p] > 0;
+            if (!(pl == 0 ? p >= 18 : p < 6)) outside += rec[pl * 24 + p];
+        }
+        fprintf(stderr, "   lane %d pl %d roll %d-%d points %d outside %d bar %d off %d n %d\n", gi, pl, rec[53],
+                rec[54], own, outside, rec[48 + pl], rec[50 + pl], rec[60] | (rec[61] << 8));
+    }
     return BGX_OK;
 }
 
@@ -802,13 +936,10 @@ int bgx_engine_create(int device, int32_t batch, int32_t max_moves, uint64_t see
                       int32_t auto_reset, int32_t match_length, bgx_engine** out) {
     if (!out || batch <= 0 || max_moves <= 0 || max_moves > 32767 || dice_mode < 0 || dice_mode > 2)
         return BGX_EINVAL;
-    CK(hipSetDevice(device));
+    BGX_CK(hipSetDevice(device));
     bgx_engine* e = new bgx_engine();
-    memset(&e->a, 0, sizeof e->a);
     e->device = device;
     e->seed = seed;
-    e->order_pending = false;
-    e->step_fork = true;
     Args& A = e->a;
     A.B = batch; A.max_moves = max_moves; A.dice_mode = dice_mode; A.auto_reset = auto_reset ? 1 : 0;
     A.match_length = match_length;
@@ -820,40 +951,22 @@ int bgx_engine_create(int device, int32_t batch, int32_t max_moves, uint64_t see
                                          cap_fast<kLogMid>());
     A.cap_main = (int)std::min<long long>(std::max<long long>(bgx_dbg_int("BGX_MOVEGEN_CAP", cap_fast<9>()), 1),
                                           cap_fast<9>());
-    e->slow_waves = kSlowWaves;
-    const size_t B = (size_t)batch;
+    const bool stamps = !bgx_dbg("BGX_STAMPS").empty();
+    const bool order = dice_mode == BGX_DICE_PHILOX && bgx_dbg_int("BGX_ORDER", 1) != 0;
     hipError_t err = hipSuccess;
-    auto alloc = [&](void** p, size_t bytes) { if (err == hipSuccess) err = hipMalloc(p, bytes); };
-    alloc((void**)&A.lanes, B * 64);
-    alloc((void**)&A.moves, B * (size_t)max_moves * 8);
-    alloc((void**)&A.n_total, B * 4);
-    alloc((void**)&A.mt, (dice_mode == BGX_DICE_MT_SHARED ? 1 : (dice_mode == BGX_DICE_MT_LANE ? B : 1)) * kMtWords * 4);
-    alloc((void**)&A.ctr, B * 8);
-    alloc((void**)&A.shared_rolls, B * 4);
-    alloc((void**)&e->ovf_base, 32);
+    for (const EngineBuf& b : engine_bufs(e, stamps, order))
+        if (err == hipSuccess && b.bytes) err = hipMalloc(b.p, b.bytes);
     A.ovf_count = e->ovf_base;
-    alloc((void**)&A.ovf_queue, B * 4);
-    alloc((void**)&A.err, 16);
-    if (dice_mode != BGX_DICE_MT_SHARED) alloc((void**)&e->starts, B * 64);     // bgx_engine_set_starts
-    alloc((void**)&e->slow_tables, (size_t)kSlowWaves * ((size_t)16 << kLogSlotsSlow));
-    if (!bgx_dbg("BGX_STAMPS").empty()) alloc((void**)&A.stamps, B * 16);
-    if (dice_mode == BGX_DICE_PHILOX && bgx_dbg_int("BGX_ORDER", 1) != 0) {
-        alloc((void**)&e->perm, B * 4);
-        alloc((void**)&A.cls, B);
-        alloc((void**)&A.pre, B);
-        alloc((void**)&e->order_cnt, (B / kCountThreads + 1) * kXcd * kClasses * 4);
-    }
-    if (err != hipSuccess) { bgx_engine_destroy(e); return fail(err, BGX_ENOMEM); }
-    if (hipMemset(A.lanes, 0, B * 64) != hipSuccess || hipMemset(A.ctr, 0, B * 8) != hipSuccess ||
-        hipMemset(e->ovf_base, 0, 32) != hipSuccess || hipMemset(A.err, 0, 16) != hipSuccess ||
-        hipMemset(A.n_total, 0, B * 4) != hipSuccess || (A.cls && hipMemset(A.cls, 0, B) != hipSuccess) ||
-        (A.pre && hipMemset(A.pre, 0, B) != hipSuccess)) {
-        bgx_engine_destroy(e);
-        return fail(hipGetLastError());
+    if (err != hipSuccess) { bgx_engine_destroy(e); return bgx_internal_fail(err, BGX_ENOMEM); }
+    for (const EngineBuf& b : engine_bufs(e, stamps, order)) {
+        if (b.zero && b.bytes && hipMemset(*b.p, 0, b.bytes) != hipSuccess) {
+            bgx_engine_destroy(e);
+            return bgx_internal_fail(hipGetLastError());
+        }
     }
     // default seeds: lane i -> seed + i
-    std::vector<uint32_t> seeds(B);
-    for (size_t i = 0; i < B; ++i) seeds[i] = (uint32_t)(seed + i);
+    std::vector<uint32_t> seeds((size_t)batch);
+    for (size_t i = 0; i < seeds.size(); ++i) seeds[i] = (uint32_t)(seed + i);
     int rc = bgx_engine_seed(e, seeds.data(), seed);
     if (rc != BGX_OK) { bgx_engine_destroy(e); return rc; }
     *out = e;
@@ -862,13 +975,8 @@ int bgx_engine_create(int device, int32_t batch, int32_t max_moves, uint64_t see
 
 int bgx_engine_join(bgx_engine* e, void* stream) {
     if (!e) return BGX_EINVAL;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, (hipStream_t)stream);
-    CK(use.err);
-    if (e->order_pending) {                  // the next step's dispatch order, on the side stream
-        CK(hipStreamWaitEvent((hipStream_t)stream, e->step_ev[3], 0));
-        e->order_pending = false;
-    }
+    EngineCall call(e, (hipStream_t)stream, true);   // the next step's dispatch order, on the side stream
+    BGX_CK(call.err);
     return BGX_OK;
 }
 
@@ -878,31 +986,21 @@ int bgx_engine_order(bgx_engine* e, int32_t* perm_host, uint8_t* cls_host, uint6
     if ((perm_host || cls_host) && (!e->a.cls || !e->perm_valid)) return BGX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const size_t B = (size_t)e->a.B;
-    CK(hipSetDevice(e->device));
     {
-        EngineUse use(e, s);
-        CK(use.err);
-        if (e->order_pending) {              // the last step's dispatch order, on the side stream
-            CK(hipStreamWaitEvent(s, e->step_ev[3], 0));
-            e->order_pending = false;
-        }
-        if (perm_host) CK(hipMemcpyAsync(perm_host, e->perm, B * 4, hipMemcpyDeviceToHost, s));
-        if (cls_host) CK(hipMemcpyAsync(cls_host, e->a.cls, B, hipMemcpyDeviceToHost, s));
-        if (ctr_host) CK(hipMemcpyAsync(ctr_host, e->a.ctr, B * 8, hipMemcpyDeviceToHost, s));
+        EngineCall call(e, s, true);         // the last step's dispatch order, on the side stream
+        BGX_CK(call.err);
+        if (perm_host) BGX_CK(hipMemcpyAsync(perm_host, e->perm, B * 4, hipMemcpyDeviceToHost, s));
+        if (cls_host) BGX_CK(hipMemcpyAsync(cls_host, e->a.cls, B, hipMemcpyDeviceToHost, s));
+        if (ctr_host) BGX_CK(hipMemcpyAsync(ctr_host, e->a.ctr, B * 8, hipMemcpyDeviceToHost, s));
     }
-    CK(hipStreamSynchronize(s));
+    BGX_CK(hipStreamSynchronize(s));
     return BGX_OK;
 }
 
 int bgx_engine_set_fork(bgx_engine* e, int32_t fork, void* stream) {
     if (!e) return BGX_EINVAL;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, (hipStream_t)stream);
-    CK(use.err);
-    if (!fork && e->order_pending) {         // a pending dispatch order joins `stream` first
-        CK(hipStreamWaitEvent((hipStream_t)stream, e->step_ev[3], 0));
-        e->order_pending = false;
-    }
+    EngineCall call(e, (hipStream_t)stream, !fork);  // going linear: a pending dispatch order joins `stream` first
+    BGX_CK(call.err);
     e->step_fork = fork != 0;
     return BGX_OK;
 }
@@ -912,11 +1010,8 @@ int bgx_engine_destroy(bgx_engine* e) {
     (void)hipSetDevice(e->device);
     if (e->use_valid) (void)hipEventSynchronize(e->use_ev);   // the last call's work is done
     if (e->use_ev) (void)hipEventDestroy(e->use_ev);
-    Args& A = e->a;
-    void* ptrs[] = {A.lanes, A.moves, A.n_total, A.mt, A.ctr, A.shared_rolls, e->ovf_base, A.ovf_queue, A.err,
-                    e->slow_tables, e->search_ws.p, e->search_pool.p, e->oneply_ws.p, A.stamps, e->perm, A.cls, A.pre,
-                    e->order_cnt, e->starts};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (const EngineBuf& b : engine_bufs(e, true, true)) if (*b.p) (void)hipFree(*b.p);
+    for (const DeviceBuf* b : {&e->search_ws, &e->search_pool, &e->oneply_ws}) if (b->p) (void)hipFree(b->p);
     for (hipEvent_t ev : e->search_ev) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->step_ev) if (ev) (void)hipEventDestroy(ev);
     if (e->step_side) (void)hipStreamDestroy(e->step_side);
@@ -927,20 +1022,20 @@ int bgx_engine_destroy(bgx_engine* e) {
 
 int bgx_engine_seed(bgx_engine* e, const uint32_t* seeds_host, uint64_t philox_seed) {
     if (!e || !seeds_host) return BGX_EINVAL;
-    CK(hipSetDevice(e->device));
+    BGX_CK(hipSetDevice(e->device));
     Args& A = e->a;
     // device-wide order (bgx.h "Stream ordering"): every earlier call on any stream has
     // finished before the dice state changes, and the new state is in place on return
-    CK(hipDeviceSynchronize());
+    BGX_CK(hipDeviceSynchronize());
     A.key0 = (uint32_t)philox_seed; A.key1 = (uint32_t)(philox_seed >> 32);
-    CK(hipMemset(A.ctr, 0, (size_t)A.B * 8));
+    BGX_CK(hipMemset(A.ctr, 0, (size_t)A.B * 8));
     if (A.dice_mode == BGX_DICE_PHILOX) {
-        CK(hipDeviceSynchronize());
+        BGX_CK(hipDeviceSynchronize());
         return BGX_OK;
     }
     const int n = A.dice_mode == BGX_DICE_MT_LANE ? A.B : 1;
     uint32_t* dseeds = nullptr;
-    CK(hipMalloc(&dseeds, (size_t)n * 4));
+    BGX_CK(hipMalloc(&dseeds, (size_t)n * 4));
     hipError_t err = hipMemcpy(dseeds, seeds_host, (size_t)n * 4, hipMemcpyHostToDevice);
     if (err == hipSuccess) {
         hipLaunchKernelGGL(k_mt_seed, dim3((n + 255) / 256), dim3(256), 0, 0, A.mt, dseeds, n);
@@ -948,7 +1043,7 @@ int bgx_engine_seed(bgx_engine* e, const uint32_t* seeds_host, uint64_t philox_s
     }
     if (err == hipSuccess) err = hipDeviceSynchronize();
     (void)hipFree(dseeds);
-    if (err != hipSuccess) return fail(err);
+    BGX_CK(err);
     return BGX_OK;
 }
 
@@ -958,25 +1053,25 @@ int bgx_engine_mt_state(bgx_engine* e, int32_t lane, uint32_t* state_host, int32
     if (A.dice_mode == BGX_DICE_PHILOX) return BGX_EINVAL;
     if (A.dice_mode == BGX_DICE_MT_SHARED) lane = 0;
     if (lane < 0 || lane >= A.B) return BGX_EINVAL;
-    CK(hipSetDevice(e->device));
-    CK(hipDeviceSynchronize());
+    BGX_CK(hipSetDevice(e->device));
+    BGX_CK(hipDeviceSynchronize());
     uint32_t* dev = A.mt + (size_t)lane * kMtWords;
-    if (set) CK(hipMemcpy(dev, state_host, 625 * 4, hipMemcpyHostToDevice));
-    else CK(hipMemcpy(state_host, dev, 625 * 4, hipMemcpyDeviceToHost));
+    if (set) BGX_CK(hipMemcpy(dev, state_host, 625 * 4, hipMemcpyHostToDevice));
+    else BGX_CK(hipMemcpy(state_host, dev, 625 * 4, hipMemcpyDeviceToHost));
     return BGX_OK;
 }
 
 #ifdef BGX_COUNTERS
 extern "C" int bgx_debug_counters(unsigned long long* out16) {
-    CK(hipDeviceSynchronize());
+    BGX_CK(hipDeviceSynchronize());
     constexpr size_t n = 16 * (size_t)bg::kCntSlots;
     std::vector<unsigned long long> h(n), z(n, 0ull);
-    CK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(bg::g_cnt), n * 8));
+    BGX_CK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(bg::g_cnt), n * 8));
     for (int i = 0; i < 16; ++i) {
         out16[i] = 0;
         for (int k = 0; k < bg::kCntSlots; ++k) out16[i] += h[(size_t)i * bg::kCntSlots + k];
     }
-    CK(hipMemcpyToSymbol(HIP_SYMBOL(bg::g_cnt), z.data(), n * 8));
+    BGX_CK(hipMemcpyToSymbol(HIP_SYMBOL(bg::g_cnt), z.data(), n * 8));
     return BGX_OK;
 }
 #endif
@@ -984,8 +1079,8 @@ extern "C" int bgx_debug_counters(unsigned long long* out16) {
 // diagnostics: copy the per-lane [start, end] s_memrealtime stamps of the last step
 extern "C" int bgx_debug_stamps(bgx_engine* e, uint64_t* host_out) {
     if (!e || !host_out || !e->a.stamps) return BGX_EINVAL;
-    CK(hipDeviceSynchronize());
-    CK(hipMemcpy(host_out, e->a.stamps, (size_t)e->a.B * 16, hipMemcpyDeviceToHost));
+    BGX_CK(hipDeviceSynchronize());
+    BGX_CK(hipMemcpy(host_out, e->a.stamps, (size_t)e->a.B * 16, hipMemcpyDeviceToHost));
     return BGX_OK;
 }
 
@@ -1000,28 +1095,17 @@ int bgx_reset(bgx_engine* e, const uint8_t* lane_mask_dev, float* obs_dev, void*
     if (!e) return BGX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     Args& A = e->a;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, s);
-    CK(use.err);
-    if (e->order_pending) {                  // a step's dispatch order still on the side stream
-        CK(hipStreamWaitEvent(s, e->step_ev[3], 0));
-        e->order_pending = false;
-    }
-    if (e->ovf_next_zeroed) {             // the previous step's k_order_count zeroed the other set
-        e->ovf_parity ^= 1;
-        A.ovf_count = e->ovf_base + 4 * e->ovf_parity;
-        e->ovf_next_zeroed = false;
-    } else {
-        CK(hipMemsetAsync(A.ovf_count, 0, 16, s));
-    }
+    EngineCall call(e, s, true);             // joins a step's dispatch order still on the side stream
+    BGX_CK(call.err);
+    BGX_CK(fresh_ovf_counters(e, s, true));
     if (A.dice_mode == BGX_DICE_MT_SHARED) {
-        LAUNCH_LOG(e, k_reset, dim3(A.B), s, A, lane_mask_dev, obs_dev, 1);
+        LAUNCH_LOG(k_reset, dim3(A.B), s, A, lane_mask_dev, obs_dev, 1);
         hipLaunchKernelGGL(k_shared_dice, dim3(1), dim3(64), 0, s, A);
-        LAUNCH_LOG(e, k_reset, dim3(A.B), s, A, nullptr, obs_dev, 0);
+        LAUNCH_LOG(k_reset, dim3(A.B), s, A, nullptr, obs_dev, 0);
     } else {
-        LAUNCH_LOG(e, k_reset, dim3(A.B), s, A, lane_mask_dev, obs_dev, 0);
+        LAUNCH_LOG(k_reset, dim3(A.B), s, A, lane_mask_dev, obs_dev, 0);
     }
-    CKL();
+    BGX_CK_LAUNCH();
     if (A.cls) {
         launch_order(e, s);
     }
@@ -1032,97 +1116,24 @@ int bgx_step(bgx_engine* e, const int32_t* actions_dev, float* obs_dev, float* r
              int32_t* info_dev, void* stream) {
     if (!e || !actions_dev || !reward_dev || !done_dev) return BGX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    Args& A = e->a;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, s);
-    CK(use.err);
-    if (e->ovf_next_zeroed) {             // the previous step's k_order_count zeroed the other set
-        e->ovf_parity ^= 1;
-        A.ovf_count = e->ovf_base + 4 * e->ovf_parity;
-        e->ovf_next_zeroed = false;
+    const StepIo io{actions_dev, obs_dev, reward_dev, done_dev, info_dev};
+    // joins the previous step's dispatch order (side stream).  A pending order has zeroed
+    // the other counter set, so fresh_ovf_counters below then rotates and issues no memset:
+    // the wait is this call's first operation on s either way.
+    EngineCall call(e, s, true);
+    BGX_CK(call.err);
+    BGX_CK(fresh_ovf_counters(e, s, true));
+    if (e->a.dice_mode == BGX_DICE_MT_SHARED) {
+        step_shared_dice(e->a, io, s);
     } else {
-        CK(hipMemsetAsync(A.ovf_count, 0, 16, s));
+        const int rc = step_lane_dice(e, io, s);
+        if (rc != BGX_OK) return rc;
     }
-    if (A.dice_mode == BGX_DICE_MT_SHARED) {
-        hipLaunchKernelGGL((k_step<1, 9>), dim3(A.B), dim3(64), 0, s, A, actions_dev, obs_dev, reward_dev, done_dev,
-                           info_dev, 0);
-        hipLaunchKernelGGL(k_shared_dice, dim3(1), dim3(64), 0, s, A);
-        hipLaunchKernelGGL((k_step<2, 9>), dim3(A.B), dim3(64), 0, s, A, actions_dev, obs_dev, reward_dev, done_dev,
-                           info_dev, 0);
-    } else {
-        if (e->order_pending) {              // the previous step's dispatch order (side stream)
-            CK(hipStreamWaitEvent(s, e->step_ev[3], 0));
-            e->order_pending = false;
-        }
-        Args a = A;
-        a.perm = e->perm_valid ? e->perm : nullptr;
-        const int heavy = a.perm ? heavy_grid(A.B, A.xcd != 0) : A.B;
-        // Split dispatch (Philox mode): the predicted-doubles prefix of the order
-        // with the big dedup table + revisit memo (26 KB of LDS per wave), then the
-        // rest with a 256-slot table, no memo, no doubles code (4 KB, 49 VGPRs: the
-        // hardware wave limit, ~5x the resident waves; doubles go to the overflow tiers).
-        // Plain stream order -- no cross-stream wait that a serializing tool
-        // (profiler) or a shared hardware queue could deadlock.
-        if (heavy < A.B && e->step_fork) {
-            // fork-join on events: the light launch runs on a side stream beside
-            // the heavy one (filling the CUs its tail leaves idle)
-            if (!e->step_side) {
-                CK(hipStreamCreateWithFlags(&e->step_side, hipStreamNonBlocking));
-                for (hipEvent_t& ev : e->step_ev) CK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-            }
-            CK(hipEventRecord(e->step_ev[0], s));
-            CK(hipStreamWaitEvent(e->step_side, e->step_ev[0], 0));
-            auto light = [&] {
-                hipLaunchKernelGGL((k_step<0, 8, 0, true>), dim3(A.B - heavy), dim3(64), 0, e->step_side, a,
-                                   actions_dev, obs_dev, reward_dev, done_dev, info_dev, heavy);
-            };
-            launch_step(s, a, heavy, actions_dev, obs_dev, reward_dev, done_dev, info_dev);
-            light();
-            CK(hipEventRecord(e->step_ev[1], e->step_side));
-            if (A.cls) {
-                // the next dispatch order on the side stream once both launches have
-                // written their pre-class bytes and counters: it runs beside this
-                // stream's overflow tiers and the caller's next policy kernel instead
-                // of before them (neither touches pre, cls, perm or the counters); the
-                // order pass writes the counters' roll cache, so the next bgx_step and
-                // every other call that reads or rewrites counters waits for it
-                // (step_ev[3], order_pending) before its own launches
-                CK(hipEventRecord(e->step_ev[2], s));
-                CK(hipStreamWaitEvent(e->step_side, e->step_ev[2], 0));
-                launch_order(e, e->step_side);
-                CK(hipEventRecord(e->step_ev[3], e->step_side));
-                e->order_pending = true;
-            }
-            CK(hipStreamWaitEvent(s, e->step_ev[1], 0));
-        } else {
-            launch_step(s, a, heavy, actions_dev, obs_dev, reward_dev, done_dev, info_dev);
-            if (heavy < A.B)
-                hipLaunchKernelGGL((k_step<0, 8, 0, true>), dim3(A.B - heavy), dim3(64), 0, s, a, actions_dev,
-                                   obs_dev, reward_dev, done_dev, info_dev, heavy);
-        }
-        if (A.cls && !e->order_pending) launch_order(e, s);
-    }
-    CKL();
+    BGX_CK_LAUNCH();
     const int rc = slow_path(e, s, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
-    if (e->step_debug) {                     // overflow-tier queue sizes of this step
-        int32_t q[2] = {0, 0};
-        CK(hipMemcpyAsync(q, A.ovf_count, 8, hipMemcpyDeviceToHost, s));
-        CK(hipStreamSynchronize(s));
-        fprintf(stderr, "[bgx step] overflow queue %d of %d lanes\n", q[0], A.B);
-        for (int i = 0; i < q[0] && i < 4; ++i) {
-            int32_t gi = 0;
-            uint8_t rec[64];
-            CK(hipMemcpy(&gi, A.ovf_queue + i, 4, hipMemcpyDeviceToHost));
-            CK(hipMemcpy(rec, A.lanes + (size_t)gi * 64, 64, hipMemcpyDeviceToHost));
-            int own = 0, outside = 0;
-            const int pl = rec[52];
-            for (int p = 0; p < 24; ++p) {
-                own += rec[pl * 24 + p] > 0;
-                if (!(pl == 0 ? p >= 18 : p < 6)) outside += rec[pl * 24 + p];
-            }
-            fprintf(stderr, "   lane %d pl %d roll %d-%d points %d outside %d bar %d off %d n %d\n", gi, pl, rec[53],
-                    rec[54], own, outside, rec[48 + pl], rec[50 + pl], rec[60] | (rec[61] << 8));
-        }
+    if (e->step_debug) {
+        const int drc = step_debug_dump(e, s);
+        if (drc != BGX_OK) return drc;
     }
     return rc;
 }
@@ -1135,13 +1146,12 @@ int bgx_movegen(bgx_engine* e, const int8_t* boards52_dev, const uint8_t* player
     if (n > e->a.B) return BGX_EINVAL;   // overflow queue is sized by the engine batch
     if (n == 0) return BGX_OK;
     hipStream_t s = (hipStream_t)stream;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, s);
-    CK(use.err);
-    CK(hipMemsetAsync(e->a.ovf_count, 0, 16, s));
-    LAUNCH_LOG(e, k_movegen, dim3(n), s, boards52_dev, players_dev, dice_dev, n, max_moves, n_moves_dev, n_total_dev,
+    EngineCall call(e, s);
+    BGX_CK(call.err);
+    BGX_CK(fresh_ovf_counters(e, s, false));
+    LAUNCH_LOG(k_movegen, dim3(n), s, boards52_dev, players_dev, dice_dev, n, max_moves, n_moves_dev, n_total_dev,
                moves_dev, e->a.ovf_count, e->a.ovf_queue, e->a.cap_main);
-    CKL();
+    BGX_CK_LAUNCH();
     return slow_path(e, s, 1, boards52_dev, players_dev, dice_dev, max_moves, n_moves_dev, n_total_dev, moves_dev);
 }
 
@@ -1149,7 +1159,7 @@ int bgx_encode(const int8_t* boards52_dev, const uint8_t* players_dev, int32_t n
     if (n < 0 || (n > 0 && (!boards52_dev || !players_dev || !out_dev))) return BGX_EINVAL;
     if (n == 0) return BGX_OK;
     hipLaunchKernelGGL(k_encode, dim3(n), dim3(64), 0, (hipStream_t)stream, boards52_dev, players_dev, n, out_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1170,7 +1180,7 @@ int bgx_encode_records_ex(const uint8_t* records_dev, int32_t n, int32_t dtype, 
     else
         hipLaunchKernelGGL((k_encode_rec<_Float16, 208>), dim3(blocks), dim3(256), 0, s, records_dev, n,
                            (_Float16*)out_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1181,34 +1191,31 @@ int bgx_encode_records(const uint8_t* records_dev, int32_t n, int32_t dtype, voi
 int bgx_afterstates(bgx_engine* e, int32_t lane0, int32_t nlanes, int8_t* boards52_dev, void* stream) {
     if (!e || !boards52_dev || lane0 < 0 || nlanes < 0 || lane0 + nlanes > e->a.B) return BGX_EINVAL;
     if (nlanes == 0) return BGX_OK;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, (hipStream_t)stream);
-    CK(use.err);
+    EngineCall call(e, (hipStream_t)stream);
+    BGX_CK(call.err);
     hipLaunchKernelGGL(k_legal<0>, dim3(nlanes), dim3(64), 0, (hipStream_t)stream, e->a, lane0, (void*)boards52_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
 int bgx_legal_features(bgx_engine* e, int32_t lane0, int32_t nlanes, float* out_dev, void* stream) {
     if (!e || !out_dev || lane0 < 0 || nlanes < 0 || lane0 + nlanes > e->a.B) return BGX_EINVAL;
     if (nlanes == 0) return BGX_OK;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, (hipStream_t)stream);
-    CK(use.err);
+    EngineCall call(e, (hipStream_t)stream);
+    BGX_CK(call.err);
     hipLaunchKernelGGL(k_legal<1>, dim3(nlanes), dim3(64), 0, (hipStream_t)stream, e->a, lane0, (void*)out_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
 int bgx_action_masks(bgx_engine* e, int16_t* counts_dev, float* masks_dev, void* stream) {
     if (!e) return BGX_EINVAL;
     if (!counts_dev && !masks_dev) return BGX_OK;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, (hipStream_t)stream);
-    CK(use.err);
+    EngineCall call(e, (hipStream_t)stream);
+    BGX_CK(call.err);
     hipLaunchKernelGGL(k_action_masks, dim3(e->a.B), dim3(masks_dev ? 256 : 64), 0, (hipStream_t)stream, e->a,
                        counts_dev, masks_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1218,14 +1225,13 @@ int bgx_copy_lanes(bgx_engine* e, int32_t lane0, int32_t n, uint8_t* lanes_dst, 
     if (n == 0) return BGX_OK;
     hipStream_t s = (hipStream_t)stream;
     const Args& A = e->a;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, s);
-    CK(use.err);
-    if (lanes_dst) CK(hipMemcpyAsync(lanes_dst, A.lanes + (size_t)lane0 * 64, (size_t)n * 64, hipMemcpyDeviceToDevice, s));
+    EngineCall call(e, s);
+    BGX_CK(call.err);
+    if (lanes_dst) BGX_CK(hipMemcpyAsync(lanes_dst, A.lanes + (size_t)lane0 * 64, (size_t)n * 64, hipMemcpyDeviceToDevice, s));
     if (moves_dst)
-        CK(hipMemcpyAsync(moves_dst, A.moves + (size_t)lane0 * A.max_moves, (size_t)n * A.max_moves * 8,
+        BGX_CK(hipMemcpyAsync(moves_dst, A.moves + (size_t)lane0 * A.max_moves, (size_t)n * A.max_moves * 8,
                           hipMemcpyDeviceToDevice, s));
-    if (n_total_dst) CK(hipMemcpyAsync(n_total_dst, A.n_total + lane0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
+    if (n_total_dst) BGX_CK(hipMemcpyAsync(n_total_dst, A.n_total + lane0, (size_t)n * 4, hipMemcpyDeviceToDevice, s));
     return BGX_OK;
 }
 
@@ -1238,28 +1244,27 @@ int bgx_set_lanes_ex(bgx_engine* e, int32_t lane0, int32_t n, const uint8_t* lan
     if (n == 0) return BGX_OK;
     hipStream_t s = (hipStream_t)stream;
     Args& A = e->a;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, s);
-    CK(use.err);
-    CK(hipMemcpyAsync(A.lanes + (size_t)lane0 * 64, lanes_src, (size_t)n * 64, hipMemcpyDeviceToDevice, s));
+    EngineCall call(e, s);
+    BGX_CK(call.err);
+    BGX_CK(hipMemcpyAsync(A.lanes + (size_t)lane0 * 64, lanes_src, (size_t)n * 64, hipMemcpyDeviceToDevice, s));
     if (!regen) return BGX_OK;
-    CK(hipMemsetAsync(A.ovf_count, 0, 16, s));
-    LAUNCH_LOG(e, k_regen, dim3(n), s, A, lane0);
-    CKL();
+    BGX_CK(fresh_ovf_counters(e, s, false));
+    LAUNCH_LOG(k_regen, dim3(n), s, A, lane0);
+    BGX_CK_LAUNCH();
     return slow_path(e, s, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
 }
 
 int bgx_engine_error(bgx_engine* e, int32_t* err_out) {
     if (!e || !err_out) return BGX_EINVAL;
-    CK(hipSetDevice(e->device));
-    CK(hipDeviceSynchronize());
-    CK(hipMemcpy(err_out, e->a.err, 4, hipMemcpyDeviceToHost));
+    BGX_CK(hipSetDevice(e->device));
+    BGX_CK(hipDeviceSynchronize());
+    BGX_CK(hipMemcpy(err_out, e->a.err, 4, hipMemcpyDeviceToHost));
     return BGX_OK;
 }
 
 int bgx_host_device_ptr(void* host_ptr, void** dev_ptr_out) {
     if (!host_ptr || !dev_ptr_out) return BGX_EINVAL;
-    CK(hipHostGetDevicePointer(dev_ptr_out, host_ptr, 0));
+    BGX_CK(hipHostGetDevicePointer(dev_ptr_out, host_ptr, 0));
     return BGX_OK;
 }
 
@@ -1285,7 +1290,7 @@ int bgx_copy_regions(const bgx_region* regions, int32_t n, int32_t workgroups, v
     const int64_t need = (acc + 255) / 256;
     const int wg = (int)(workgroups > 0 && workgroups < need ? workgroups : (need < 64 ? need : 64));
     hipLaunchKernelGGL(k_copy_regions, dim3(wg), dim3(256), 0, (hipStream_t)stream, R);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1294,10 +1299,10 @@ int bgx_arena_begin(const uint8_t* records_dev, int32_t n, int32_t games_per_lan
     if (!records_dev || n <= 0 || games_per_lane < 0 || !games_done_dev || !sel_a_dev || !sel_b_dev || !tally_dev)
         return BGX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    CK(hipMemsetAsync(tally_dev, 0, 16 * sizeof(int64_t), s));
+    BGX_CK(hipMemsetAsync(tally_dev, 0, 16 * sizeof(int64_t), s));
     hipLaunchKernelGGL(k_arena_begin, dim3((n + 255) / 256), dim3(256), 0, s, records_dev, n, games_per_lane,
                        games_done_dev, sel_a_dev, sel_b_dev, tally_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1306,7 +1311,7 @@ int bgx_arena_merge(const uint8_t* sel_a_dev, const uint8_t* sel_b_dev, const in
     if (!sel_a_dev || !sel_b_dev || !act_a_dev || !act_b_dev || n <= 0 || !actions_dev) return BGX_EINVAL;
     hipLaunchKernelGGL(k_arena_merge, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, sel_a_dev, sel_b_dev,
                        act_a_dev, act_b_dev, n, actions_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1318,7 +1323,7 @@ int bgx_arena_advance(const uint8_t* records_dev, const uint8_t* done_dev, const
         return BGX_EINVAL;
     hipLaunchKernelGGL(k_arena_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, records_dev,
                        done_dev, info_dev, n, games_per_lane, games_done_dev, sel_a_dev, sel_b_dev, tally_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1326,15 +1331,14 @@ int bgx_engine_set_starts(bgx_engine* e, const uint8_t* starts_dev, void* stream
     if (!e || e->a.dice_mode == BGX_DICE_MT_SHARED || ((uintptr_t)starts_dev & 15)) return BGX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     Args& A = e->a;
-    CK(hipSetDevice(e->device));
-    EngineUse use(e, s);
-    CK(use.err);
+    EngineCall call(e, s);
+    BGX_CK(call.err);
     if (!starts_dev) {
         A.starts = nullptr;
         return BGX_OK;
     }
     hipLaunchKernelGGL(k_check_starts, dim3((A.B + 255) / 256), dim3(256), 0, s, starts_dev, e->starts, A.B, A.err);
-    CKL();
+    BGX_CK_LAUNCH();
     A.starts = e->starts;
     return BGX_OK;
 }
@@ -1346,11 +1350,11 @@ int bgx_rollout_begin(const uint8_t* records_dev, const uint8_t* starts_dev, con
         !games_done_dev || !plies_dev || !sel_dev || !tally_dev || !active_dev)
         return BGX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    CK(hipMemsetAsync(tally_dev, 0, (size_t)n_groups * 8 * sizeof(int64_t), s));
-    CK(hipMemsetAsync(active_dev, 0, sizeof(int64_t), s));
+    BGX_CK(hipMemsetAsync(tally_dev, 0, (size_t)n_groups * 8 * sizeof(int64_t), s));
+    BGX_CK(hipMemsetAsync(active_dev, 0, sizeof(int64_t), s));
     hipLaunchKernelGGL(k_rollout_begin, dim3((n + 255) / 256), dim3(256), 0, s, group_dev, n, n_groups, games_per_lane,
                        games_done_dev, plies_dev, sel_dev, active_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1364,7 +1368,7 @@ int bgx_rollout_advance(const uint8_t* records_dev, const uint8_t* starts_dev, c
     hipLaunchKernelGGL(k_rollout_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, starts_dev,
                        group_dev, done_dev, info_dev, n, n_groups, games_per_lane, games_done_dev, plies_dev, sel_dev,
                        tally_dev, active_dev);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1373,7 +1377,7 @@ int bgx_random_act(const uint8_t* records_dev, int32_t n, uint64_t seed, uint32_
     if (!records_dev || n <= 0 || !act_out) return BGX_EINVAL;
     hipLaunchKernelGGL(k_random_act, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, records_dev, n, seed,
                        step, act_out);
-    CKL();
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 

@@ -23,7 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
-#include "../../include/bgx.h"
+#include "bg_host.h"
 #include "bg_debug.h"
 
 
@@ -819,7 +819,7 @@ int bgx_policy_pack(const float* W1, const float* b1, const float* Wa, const flo
     const int work = kKB1 * T * 64 * 8 + T * 16 * 64 + OT * T * 2 * 64 * 8 + OT * 16 * 64;
     hipLaunchKernelGGL(k_policy_pack, dim3((work + 255) / 256), dim3(256), 0, s, W1, b1, Wa, ba, wv, bv, hidden,
                        n_actions, T, OT, packed);
-    return hipGetLastError() == hipSuccess ? BGX_OK : BGX_EDEVICE;
+    return bgx_launch_status();
 }
 
 #ifdef BGX_POLICY_STAMPS
@@ -870,7 +870,7 @@ int bgx_policy_act_ctr(const uint8_t* records_dev, int32_t n, const float* packe
         default: BGX_ACT(4); break;
     }
 #undef BGX_ACT
-    return hipGetLastError() == hipSuccess ? BGX_OK : BGX_EDEVICE;
+    return bgx_launch_status();
 }
 
 int bgx_policy_act_rec(const uint8_t* records_dev, int32_t n, const float* packed, int32_t hidden, int32_t n_actions,
@@ -883,7 +883,7 @@ int bgx_policy_act_rec(const uint8_t* records_dev, int32_t n, const float* packe
 int bgx_counter_add(uint32_t* ctr_dev, uint32_t v, void* stream) {
     if (!ctr_dev) return BGX_EINVAL;
     hipLaunchKernelGGL(k_counter_add, dim3(1), dim3(64), 0, (hipStream_t)stream, ctr_dev, v);
-    return hipGetLastError() == hipSuccess ? BGX_OK : BGX_EDEVICE;
+    return bgx_launch_status();
 }
 
 int bgx_policy_act(const uint8_t* records_dev, int32_t n, const float* packed, int32_t hidden, int32_t n_actions,
@@ -904,7 +904,7 @@ int bgx_fc1_pack(const void* w1h_dev, int32_t hidden, void* packed_dev, void* st
     const int T = (hidden + 31) / 32, work = kKB1 * T * 64;
     hipLaunchKernelGGL(k_fc1_pack, dim3((work + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const _Float16*)w1h_dev, hidden, T, (uint4*)packed_dev);
-    return hipGetLastError() == hipSuccess ? BGX_OK : BGX_EDEVICE;
+    return bgx_launch_status();
 }
 
 int bgx_ppo_epoch_prep(const float* w1_dev, const float* b1_dev, const float* wa_dev, const float* ba_dev,
@@ -919,7 +919,7 @@ int bgx_ppo_epoch_prep(const float* w1_dev, const float* b1_dev, const float* wa
                 (uint4*)w1pack_dev, (_Float16*)b1h_dev, (_Float16*)w2h_dev, (_Float16*)b2h_dev, gw1_dev, gw2_dev,
                 gb2_dev, hmax2_dev_or_null, bound_dev_or_null, sums_dev_or_null};
     hipLaunchKernelGGL(k_ppo_epoch_prep, dim3(512), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? BGX_OK : BGX_EDEVICE;
+    return bgx_launch_status();
 }
 
 int bgx_fc1_records(const uint8_t* records_dev, int32_t n, const void* packed_dev, const void* b1h_dev,
@@ -946,7 +946,7 @@ int bgx_fc1_records_ex(const uint8_t* records_dev, int32_t n, const void* packed
         case 3: hipLaunchKernelGGL((k_fc1_rec<3>), grid, blk, 0, s, records_dev, n, w, b, hidden, o, hmax2_dev); break;
         default: hipLaunchKernelGGL((k_fc1_rec<4>), grid, blk, 0, s, records_dev, n, w, b, hidden, o, hmax2_dev); break;
     }
-    return hipGetLastError() == hipSuccess ? BGX_OK : BGX_EDEVICE;
+    return bgx_launch_status();
 }
 
 }  // extern "C"

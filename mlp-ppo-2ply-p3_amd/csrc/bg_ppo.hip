@@ -14,7 +14,7 @@
 #include <stdint.h>
 #include <math.h>
 
-#include "../../include/bgx.h"
+#include "bg_host.h"
 
 namespace {
 
@@ -276,8 +276,6 @@ __global__ __launch_bounds__(256) void k_relu_bwd(_Float16* __restrict__ dh, con
 
 }  // namespace
 
-extern int bgx_internal_fail(hipError_t e);
-
 extern "C" int bgx_ppo_head_ex(const void* logits, int32_t dtype, int64_t ld_logits, const void* values,
                                const uint8_t* records, const int32_t* actions, const float* old_logp,
                                const float* returns, const float* adv, int32_t n, int32_t n_actions, float eps_clip,
@@ -307,8 +305,7 @@ extern "C" int bgx_ppo_head_ex(const void* logits, int32_t dtype, int64_t ld_log
                            (const _Float16*)values, records, actions, old_logp, returns, adv, n, n_actions,
                            eps_clip, c_value, c_entropy, grad_scale, (_Float16*)dlogits, ld_dlogits,
                            (_Float16*)dvalues, sums, vec, pad, colsum);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
+    return bgx_launch_status();
 }
 
 extern "C" int bgx_ppo_head(const void* logits, int32_t dtype, int64_t ld_logits, const void* values,
@@ -329,6 +326,5 @@ extern "C" int bgx_relu_backward(void* dh, const void* h, int32_t n, int32_t hid
     if (((uintptr_t)dh | (uintptr_t)h) % 16) return BGX_EINVAL;
     hipLaunchKernelGGL(k_relu_bwd, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (_Float16*)dh,
                        (const _Float16*)h, n, hidden, colsum);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
+    return bgx_launch_status();
 }

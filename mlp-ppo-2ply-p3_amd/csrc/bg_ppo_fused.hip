@@ -33,11 +33,16 @@
 // tile count (host side, once per update), so a wave's 32 rows need the same tiles
 // and k_ppo_gw2 visits, for action tile a, only the rows that reach it.  Mean
 // legal count in self-play is ~19, so most rows need 2 of the 16 tiles.
+//
+// Also here, the rest of the fused epoch: k_ppo_gw1 (gW1 / gb1 straight from the records),
+// the row plan and the sorted rows (k_plan_*, k_gather_rollout), k_ppo_epoch_grads (the
+// gradients into the .grad tensors) and the workspaces' carves (Gw2Space, Gw1Space,
+// PlanSpace).  A rollout's returns are in bg_returns.hip, the optimizer step in bg_adam.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 
-#include "../../include/bgx.h"
+#include "bg_host.h"
 
 namespace {
 
@@ -885,222 +890,6 @@ __global__ __launch_bounds__(256) void k_ppo_gw1_sum2(const float* __restrict__ 
     gw1[u * kW1 + f] += s;
 }
 
-
-// One fp32 product / sum / difference, rounded on its own.  hipcc contracts a * b + c to an
-// fma by default, also through __fmul_rn / __fadd_rn (inline a * b and a + b of a header
-// compiled with contraction allowed); these carry no contraction flag, so they never fuse.
-__device__ __forceinline__ float mul_rn(float a, float b) {
-    #pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-    #pragma clang fp contract(off)
-    return a + b;
-}
-__device__ __forceinline__ float sub_rn(float a, float b) {
-    #pragma clang fp contract(off)
-    return a - b;
-}
-
-// ---- discounted returns per game lane (bgx.train.lane_returns; ppo_agent.py:206-216
-// restated per lane): R_t = r_t + gamma R_{t+1}, R reset at done -- one thread per lane
-// walking its T steps backwards, the same two fp32 roundings as the torch ops (no fma)
-__global__ __launch_bounds__(256) void k_lane_returns(const float* __restrict__ r, const uint8_t* __restrict__ d,
-                                                      int T, int B, float gamma, float* __restrict__ out) {
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    if (b >= B) return;
-    float R = 0.0f;
-    for (int t = T - 1; t >= 0; --t) {
-        const size_t i = (size_t)t * B + b;
-        if (d[i]) R = 0.0f;
-        R = add_rn(r[i], mul_rn(gamma, R));
-        out[i] = R;
-    }
-}
-
-// ---- the rollout's episode accounting per game lane (bgx_episode_stats;
-// bgx.train.episode_stats restated, train.py:55-99): one thread per lane walks its T
-// steps, accumulating the unfinished episode's reward from the carry, closing it at each
-// done; per-block sums of the six statistics (fp64: the rewards are multiples of 1/2, so
-// every sum is exact in any order), then one block adds the block sums in order.  The
-// mover byte (record byte 52) is read only at winning steps.
-constexpr int kEpStats = 6;
-__global__ __launch_bounds__(256) void k_episode_partials(const float* __restrict__ r, const uint8_t* __restrict__ d,
-                                                          const uint8_t* __restrict__ rec, double* __restrict__ carry,
-                                                          int T, int B, double* __restrict__ part) {
-    __shared__ double red[4][kEpStats];
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    double v[kEpStats] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (b < B) {
-        double acc = carry[b];
-        for (int t = 0; t < T; ++t) {
-            const size_t i = (size_t)t * B + b;
-            const double rw = (double)r[i];
-            acc += rw;
-            if (d[i]) {
-                v[0] += 1.0;                               // finished episodes
-                v[1] += acc;                               // their rewards (carry included)
-                acc = 0.0;
-                if (rw > 0.0) {
-                    v[2] += 1.0;                           // wins (the mover of a winning step)
-                    v[3] += rec[i * 64 + 52] == 0 ? 1.0 : 0.0;     // by PLAYER1
-                }
-                v[4] += rw == 1.5 ? 1.0 : 0.0;             // gammon wins
-                v[5] += rw == 2.0 ? 1.0 : 0.0;             // backgammon wins
-            }
-        }
-        carry[b] = acc;
-    }
-    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-    #pragma unroll
-    for (int k = 0; k < kEpStats; ++k) {
-        double x = v[k];
-        #pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o);
-        if (l == 0) red[w][k] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < kEpStats)
-        part[(size_t)blockIdx.x * kEpStats + threadIdx.x] =
-            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-__global__ __launch_bounds__(64) void k_episode_sum(const double* __restrict__ part, int nb, double* __restrict__ out) {
-    if (threadIdx.x >= kEpStats) return;
-    double s = 0.0;
-    for (int k = 0; k < nb; ++k) s += part[(size_t)k * kEpStats + threadIdx.x];
-    out[threadIdx.x] = s;
-}
-
-// ---- zero-sum GAE(lambda) per game lane (bgx_selfplay_gae; bgx.train._selfplay_gae_torch
-// restated, DESIGN.md §6 "Self-play returns"): one thread per lane walks its T steps
-// backwards carrying (A, v, mover) of step t + 1, sign-flipped where the mover changes and
-// dropped at a done; five fp32 roundings per step in the torch loop's order (no fma).
-// A step's four loads (reward, done, value, mover byte) do not depend on the recurrence:
-// they are issued kGaeU steps at a time, the next group's before the current group's
-// arithmetic, so 2 x 4 x kGaeU loads per lane are in flight (a 65,536-lane launch is one
-// wave per SIMD: the loads in flight per wave are all the memory parallelism there is).
-// The mover is one byte load per record: the lanes of a wave touch 64 different 64-byte
-// records either way, and a wider load would move bytes nobody reads.
-constexpr int kGaeU = 8;                     // steps per load group
-struct GaeGroup { float r[kGaeU], v[kGaeU]; int d[kGaeU], m[kGaeU]; };
-
-// steps top, top - 1, ..., top - kGaeU + 1; a step below 0 (the last group of a T that is
-// no multiple of kGaeU) loads step 0 again and is not used: no branch between the loads
-__device__ __forceinline__ void gae_load(GaeGroup& s, const float* __restrict__ r, const uint8_t* __restrict__ d,
-                                         const uint8_t* __restrict__ rec, const float* __restrict__ v, int top, int B,
-                                         int b) {
-    #pragma unroll
-    for (int j = 0; j < kGaeU; ++j) {
-        const int t = top - j > 0 ? top - j : 0;
-        const size_t i = (size_t)t * B + b;
-        s.r[j] = r[i];
-        s.v[j] = v[i];
-        s.d[j] = d[i];
-        s.m[j] = rec[i * 64 + 52];
-    }
-}
-
-__global__ __launch_bounds__(256) void k_selfplay_gae(const float* __restrict__ r, const uint8_t* __restrict__ d,
-                                                      const uint8_t* __restrict__ rec, const float* __restrict__ v,
-                                                      const float* __restrict__ boot_v,
-                                                      const uint8_t* __restrict__ boot_rec, int T, int B, float g,
-                                                      float gl, float* __restrict__ adv, float* __restrict__ ret,
-                                                      double* __restrict__ part) {
-    __shared__ double red[4][2];
-    const int b = blockIdx.x * 256 + threadIdx.x;
-    double sa = 0.0, sq = 0.0;
-    if (b < B) {
-        GaeGroup cur, nxt;
-        gae_load(cur, r, d, rec, v, T - 1, B, b);
-        // step T: the position the rollout stopped in, or nothing (the horizon is a cut)
-        const bool boot = boot_v != nullptr;
-        float v1 = boot ? boot_v[b] : 0.0f;
-        int m1 = boot ? (int)boot_rec[(size_t)b * 64 + 52] : 0;
-        float a1 = 0.0f;
-        bool cut_next = !boot;
-        for (int top = T - 1; top >= 0; top -= kGaeU) {
-            if (top >= kGaeU) gae_load(nxt, r, d, rec, v, top - kGaeU, B, b);
-            #pragma unroll
-            for (int j = 0; j < kGaeU; ++j) {
-                const int t = top - j;
-                if (t >= 0) {
-                    const float rv = cur.v[j];
-                    const bool cut = cur.d[j] != 0 || cut_next;
-                    const bool same = cur.m[j] == m1;
-                    const float nv = cut ? 0.0f : (same ? v1 : -v1);
-                    const float na = cut ? 0.0f : (same ? a1 : -a1);
-                    const float delta = sub_rn(add_rn(cur.r[j], mul_rn(g, nv)), rv);
-                    const float a = add_rn(delta, mul_rn(gl, na));
-                    const size_t i = (size_t)t * B + b;
-                    adv[i] = a;
-                    ret[i] = add_rn(a, rv);
-                    sa += (double)a;
-                    sq += (double)a * (double)a;
-                    a1 = a; v1 = rv; m1 = cur.m[j];
-                    cut_next = false;
-                }
-            }
-            cur = nxt;
-        }
-    }
-    if (part == nullptr) return;                             // uniform: no sums asked for
-    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-    #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        sa += __shfl_xor(sa, o);
-        sq += __shfl_xor(sq, o);
-    }
-    if (l == 0) { red[w][0] = sa; red[w][1] = sq; }
-    __syncthreads();
-    if (threadIdx.x < 2)
-        part[(size_t)blockIdx.x * 2 + threadIdx.x] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-// the block partials in a fixed order: lane l adds blocks l, l + 64, ..., then a xor tree
-__global__ __launch_bounds__(64) void k_selfplay_gae_sum(const double* __restrict__ part, int nb, double n,
-                                                         double* __restrict__ sums) {
-    double sa = 0.0, sq = 0.0;
-    for (int k = threadIdx.x; k < nb; k += 64) {
-        sa += part[(size_t)k * 2];
-        sq += part[(size_t)k * 2 + 1];
-    }
-    #pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        sa += __shfl_xor(sa, o);
-        sq += __shfl_xor(sq, o);
-    }
-    if (threadIdx.x == 0) { sums[0] = sa; sums[1] = sq; sums[2] = n; }
-}
-
-// ---- advantage normalisation from the three sums on the device (bgx_normalize_adv;
-// bgx.ppo.global_normalize's multi-rank branch): mean and unbiased variance in fp64, var
-// clamped at 0, then (a - fp32(mean)) / (fp32(std) + eps) in fp32, in place
-__device__ __forceinline__ void normalize_consts(const double* __restrict__ sums, float eps, float& mean, float& den) {
-    const double n = sums[2];
-    const double mu = sums[0] / n;
-    double var = (sums[1] - n * mu * mu) / (n - 1.0);
-    var = var > 0.0 ? var : (var == var ? 0.0 : var);       // clamp(min=0); NaN (n = 1) stays NaN
-    mean = (float)mu;
-    den = add_rn((float)sqrt(var), eps);
-}
-__global__ __launch_bounds__(256) void k_normalize_adv(float* __restrict__ a, int64_t n, int64_t n4,
-                                                       const double* __restrict__ sums, float eps) {
-    float mean, den;
-    normalize_consts(sums, eps, mean, den);
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    float4* a4 = reinterpret_cast<float4*>(a);
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        float4 x = a4[i];
-        x.x = __fdiv_rn(sub_rn(x.x, mean), den);
-        x.y = __fdiv_rn(sub_rn(x.y, mean), den);
-        x.z = __fdiv_rn(sub_rn(x.z, mean), den);
-        x.w = __fdiv_rn(sub_rn(x.w, mean), den);
-        a4[i] = x;
-    }
-    for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-        a[i] = __fdiv_rn(sub_rn(a[i], mean), den);
-}
-
 // ---- the update's rollout rows in plan order (bgx_gather_rollout): 4 threads per row,
 // each copying 16 bytes of the record; thread 0..3 of a row also copies one of the four
 // per-row fields
@@ -1275,133 +1064,28 @@ __global__ __launch_bounds__(kPlanRows) void k_plan_scatter(const uint8_t* __res
     }
 }
 
-// ---- the optimizer step (bgx_adam_step): torch.optim.Adam(fused=True) driven by
-// GradScaler.step + update, as three launches over the flat element range of every
-// tensor instead of torch's per-tensor multi-tensor chunks (a 90 k-parameter net ran
-// as ~4 workgroups each walking 65,536 elements: 69 us for the Adam kernel alone, plus
-// the inf check, the step increments and the scale update as separate launches)
-constexpr int kAdamMax = 8;
-struct AdamArgs {
-    float* p[kAdamMax];
-    float* g[kAdamMax];
-    float* m[kAdamMax];
-    float* v[kAdamMax];
-    float* step[kAdamMax];
-    int64_t end[kAdamMax];            // exclusive prefix sums of the element counts
-    int n;
-    int64_t total;
-    double lr, beta1, beta2, eps;     // torch passes them as doubles
-    const float* scale;               // GradScaler scale (null: no scaler)
-    int32_t* found;                   // non-finite flag (0 between calls)
-};
-
-__device__ __forceinline__ int adam_tensor(const AdamArgs& a, int64_t i) {
-    int t = 0;
-    #pragma unroll
-    for (int k = 0; k < kAdamMax - 1; ++k)
-        t += (k < a.n - 1 && i >= a.end[k]) ? 1 : 0;
-    return t;
+// ---- the workspaces' carves, each written once for its size function and its launcher
+// gW2 (floats): the task partials [tasks][kPart], then kRed group sums per action tile
+struct Gw2Space { int tasks; int64_t part2, floats; };
+Gw2Space gw2_space(int m) {
+    const int tasks = kNT * (((m + 31) / 32 + kTS - 1) / kTS);
+    return {tasks, (int64_t)tasks * kPart, ((int64_t)tasks + kNT * kRed) * kPart};
 }
-
-// GradScaler._check_inf_per_device: any non-finite scaled gradient
-__global__ __launch_bounds__(256) void k_adam_check(AdamArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool bad = false;
-    if (i < a.total) {
-        const int t = adam_tensor(a, i);
-        const float g = a.g[t][i - (t ? a.end[t - 1] : 0)];
-        bad = !isfinite(g);
-    }
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(a.found, 1);
+// gW1 (floats): a partial [kGw1Part] per workgroup, then the kRed group sums; `per` stages of
+// kGw1Rows rows per workgroup (m = 0 is sized as one workgroup and launches none)
+struct Gw1Space { int wgs, per; int64_t part2, floats; };
+Gw1Space gw1_space(int m) {
+    const int nst = (m + kGw1Rows - 1) / kGw1Rows, wgs = nst < kGw1Grid ? (nst > 0 ? nst : 1) : kGw1Grid;
+    return {wgs, (nst + wgs - 1) / wgs, (int64_t)wgs * kGw1Part, ((int64_t)wgs + kRed) * kGw1Part};
 }
-
-// _fused_adam_ (ADAM_MODE::ORIGINAL, no weight decay / amsgrad / maximize): the
-// gradient unscaled by the GradScaler scale (and stored back, as torch does), then the
-// moments and the parameter at step s + 1; nothing when the check found a non-finite.
-// The mixed fp32 / fp64 arithmetic follows torch's adam_math (fp32 state, double
-// hyper-parameters: the moment updates and the unscale round from fp64, the bias
-// corrections are fp64 rounded to fp32, the parameter update is fp32)
-__global__ __launch_bounds__(256) void k_adam_apply(AdamArgs a) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.total || (a.scale && *a.found)) return;
-    const int t = adam_tensor(a, i);
-    const int64_t j = i - (t ? a.end[t - 1] : 0);
-    float g = a.g[t][j];
-    if (a.scale) {
-        g = (float)((double)g / (double)*a.scale);
-        a.g[t][j] = g;
-    }
-    const double s = (double)(*a.step[t] + 1.0f);
-    float m = a.m[t][j], v = a.v[t][j];
-    m = (float)(a.beta1 * (double)m + (1.0 - a.beta1) * (double)g);
-    v = (float)(a.beta2 * (double)v + (1.0 - a.beta2) * (double)g * (double)g);
-    const float bc1 = (float)(1.0 - pow(a.beta1, s));
-    const float bc2s = (float)sqrt(1.0 - pow(a.beta2, s));
-    const float step_size = (float)(a.lr / (double)bc1);
-    const float denom = (float)((double)(sqrtf(v) / bc2s) + a.eps);
-    a.p[t][j] -= step_size * m / denom;
-    a.m[t][j] = m;
-    a.v[t][j] = v;
-}
-
-// the step counters (+1 unless skipped) and _amp_update_scale_; the flag back to 0
-__global__ void k_adam_finish(AdamArgs a, float* scale, int32_t* tracker, float growth, float backoff, int interval) {
-    const int l = threadIdx.x;
-    const int found = (a.scale && *a.found) ? 1 : 0;
-    if (l < a.n && !found) *a.step[l] += 1.0f;
-    if (l == 0 && scale) {
-        if (found) {
-            *scale = (float)((double)*scale * (double)backoff);
-            *tracker = 0;
-        } else {
-            const int succ = *tracker + 1;
-            if (succ == interval) {
-                const float ns = (float)((double)*scale * (double)growth);
-                if (isfinite(ns)) *scale = ns;
-                *tracker = 0;
-            } else {
-                *tracker = succ;
-            }
-        }
-        *a.found = 0;
-    }
+// the row plan (int32 words): bcnt [kPlanCls][nb], boff [kPlanCls][nb], gbase [kPlanCls]
+struct PlanSpace { int nb; int64_t boff, gbase, words; };
+PlanSpace plan_space(int m) {
+    const int64_t nb = ((int64_t)m + kPlanRows - 1) / kPlanRows;
+    return {(int)nb, nb * kPlanCls, 2 * nb * kPlanCls, 2 * nb * kPlanCls + kPlanCls};
 }
 
 }  // namespace
-
-extern int bgx_internal_fail(hipError_t e);
-
-extern "C" int bgx_adam_step(int32_t n, float* const* params, float* const* grads, float* const* exp_avg,
-                             float* const* exp_avg_sq, float* const* steps, const int64_t* numels, double lr,
-                             double beta1, double beta2, double eps, float* scale, int32_t* growth_tracker,
-                             float growth_factor, float backoff_factor, int32_t growth_interval, int32_t* found,
-                             void* stream) {
-    if (n <= 0 || n > kAdamMax || !params || !grads || !exp_avg || !exp_avg_sq || !steps || !numels || !found)
-        return BGX_EINVAL;
-    if (scale && !growth_tracker) return BGX_EINVAL;
-    AdamArgs a{};
-    int64_t tot = 0;
-    for (int t = 0; t < n; ++t) {
-        if (!params[t] || !grads[t] || !exp_avg[t] || !exp_avg_sq[t] || !steps[t] || numels[t] < 0) return BGX_EINVAL;
-        a.p[t] = params[t]; a.g[t] = grads[t]; a.m[t] = exp_avg[t]; a.v[t] = exp_avg_sq[t]; a.step[t] = steps[t];
-        tot += numels[t];
-        a.end[t] = tot;
-    }
-    for (int t = n; t < kAdamMax; ++t) a.end[t] = tot;
-    a.n = n; a.total = tot;
-    a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-    a.scale = scale; a.found = found;
-    hipStream_t s = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)((tot + 255) / 256);
-    if (tot > 0) {
-        if (scale) hipLaunchKernelGGL(k_adam_check, dim3(blocks), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_adam_apply, dim3(blocks), dim3(256), 0, s, a);
-    }
-    hipLaunchKernelGGL(k_adam_finish, dim3(1), dim3(64), 0, s, a, scale, growth_tracker, growth_factor, backoff_factor,
-                       growth_interval);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
-}
 
 extern "C" int bgx_ppo_rows(const void* h, const int32_t* perm, const uint8_t* records, const int32_t* actions,
                             const float* old_logp, const float* returns, const float* adv, int32_t m, int32_t hidden,
@@ -1434,15 +1118,12 @@ extern "C" int bgx_ppo_rows(const void* h, const int32_t* perm, const uint8_t* r
     hipLaunchKernelGGL(k_ppo_rows<2>, wgs(4, 1024), dim3(256), 0, s, a, row_plan + 2);
     hipLaunchKernelGGL(k_ppo_rows<4>, wgs(4, 1024), dim3(256), 0, s, a, row_plan + 4);
     hipLaunchKernelGGL(k_ppo_rows<kNT>, wgs(8, 256), dim3(512), 0, s, a, row_plan + 6);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
+    return bgx_launch_status();
 }
 
 extern "C" int64_t bgx_ppo_gw2_workspace(int32_t m) {
     if (m < 0) return BGX_EINVAL;
-    const int64_t ntiles = (m + 31) / 32;
-    // task partials, then kRed group sums per action tile
-    return ((int64_t)kNT * ((ntiles + kTS - 1) / kTS) + (int64_t)kNT * kRed) * kPart * (int64_t)sizeof(float);
+    return gw2_space(m).floats * (int64_t)sizeof(float);
 }
 
 extern "C" int bgx_ppo_gw2(const void* h, const int32_t* perm, const void* stats, const int32_t* info, int32_t m,
@@ -1452,25 +1133,21 @@ extern "C" int bgx_ppo_gw2(const void* h, const int32_t* perm, const void* stats
     if (m == 0) return BGX_OK;
     if (!h || !stats || !info || !w2h || !b2h || !plan || !workspace || !gw2 || !gb2) return BGX_EINVAL;
     if (((uintptr_t)h | (uintptr_t)w2h | (uintptr_t)stats) % 16) return BGX_EINVAL;
-    const int ntiles = (m + 31) / 32;
-    const int max_tasks = kNT * ((ntiles + kTS - 1) / kTS);
+    const Gw2Space ws = gw2_space(m);
     Gw2Args a{(const _Float16*)h, perm, (const float4*)stats, info, (const _Float16*)w2h, (const _Float16*)b2h, m, k1,
               plan, workspace};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ppo_gw2, dim3((max_tasks + 3) / 4), dim3(256), 0, s, a);
-    float* part2 = workspace + (size_t)max_tasks * kPart;
+    hipLaunchKernelGGL(k_ppo_gw2, dim3((ws.tasks + 3) / 4), dim3(256), 0, s, a);
+    float* part2 = workspace + ws.part2;
     hipLaunchKernelGGL(k_ppo_gw2_sum1, dim3((kPart + 255) / 256, kNT, kRed), dim3(256), 0, s, workspace, plan, part2);
     hipLaunchKernelGGL(k_ppo_gw2_sum2, dim3((kPart + 255) / 256, kNT), dim3(256), 0, s, part2, gw2, gb2);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
+    return bgx_launch_status();
 }
 
 
 extern "C" int64_t bgx_ppo_gw1_workspace(int32_t m) {
     if (m < 0) return BGX_EINVAL;
-    const int64_t nst = (m + kGw1Rows - 1) / kGw1Rows;
-    const int64_t wgs = nst < kGw1Grid ? (nst > 0 ? nst : 1) : kGw1Grid;
-    return (wgs + kRed) * kGw1Part * (int64_t)sizeof(float);
+    return gw1_space(m).floats * (int64_t)sizeof(float);
 }
 
 extern "C" int bgx_ppo_gw1(const void* dh, const uint8_t* records, int32_t m, int32_t hidden, float* workspace,
@@ -1479,17 +1156,14 @@ extern "C" int bgx_ppo_gw1(const void* dh, const uint8_t* records, int32_t m, in
     if (m == 0) return BGX_OK;
     if (!dh || !records || !workspace || !gw1) return BGX_EINVAL;
     if (((uintptr_t)dh | (uintptr_t)records) % 16 || (uintptr_t)workspace % 16) return BGX_EINVAL;
-    const int nst = (m + kGw1Rows - 1) / kGw1Rows;
-    const int wgs = nst < kGw1Grid ? nst : kGw1Grid;
-    const int per = (nst + wgs - 1) / wgs;
-    Gw1Args a{(const _Float16*)dh, records, m, per, workspace};
+    const Gw1Space ws = gw1_space(m);
+    Gw1Args a{(const _Float16*)dh, records, m, ws.per, workspace};
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_ppo_gw1, dim3(wgs), dim3(512), 0, s, a);
-    float* part2 = workspace + (size_t)wgs * kGw1Part;
-    hipLaunchKernelGGL(k_ppo_gw1_sum1, dim3((kGw1Part + 255) / 256, kRed), dim3(256), 0, s, workspace, wgs, part2);
+    hipLaunchKernelGGL(k_ppo_gw1, dim3(ws.wgs), dim3(512), 0, s, a);
+    float* part2 = workspace + ws.part2;
+    hipLaunchKernelGGL(k_ppo_gw1_sum1, dim3((kGw1Part + 255) / 256, kRed), dim3(256), 0, s, workspace, ws.wgs, part2);
     hipLaunchKernelGGL(k_ppo_gw1_sum2, dim3((kW1 * kH + 255) / 256), dim3(256), 0, s, part2, gw1);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
+    return bgx_launch_status();
 }
 
 extern "C" int bgx_gather_rollout(const int32_t* perm, int32_t n, const uint8_t* records, const int32_t* actions,
@@ -1506,30 +1180,28 @@ extern "C" int bgx_gather_rollout(const int32_t* perm, int32_t n, const uint8_t*
     hipLaunchKernelGGL(k_gather_rollout, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        perm, n, (const uint4*)records, actions, old_logp, returns, adv, (uint4*)records_out,
                        actions_out, old_logp_out, returns_out, adv_out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
+    return bgx_launch_status();
 }
 
 extern "C" int64_t bgx_ppo_plan_workspace(int32_t m) {
     if (m < 0) return BGX_EINVAL;
-    const int64_t nb = ((int64_t)m + kPlanRows - 1) / kPlanRows;
-    return (2 * nb * kPlanCls + kPlanCls) * 4;
+    return plan_space(m).words * (int64_t)sizeof(int32_t);
 }
 
 static int ppo_plan(const uint8_t* records, int32_t m, int32_t n_actions, int32_t* workspace, int32_t* perm,
                     const PlanRows& rows, int32_t* plan, int32_t* row_plan, void* stream) {
-    const int nb = (m + kPlanRows - 1) / kPlanRows;
+    const PlanSpace ws = plan_space(m);
+    const int nb = ws.nb;
     hipStream_t s = (hipStream_t)stream;
     int32_t* bcnt = workspace;
-    int32_t* boff = workspace + (size_t)nb * kPlanCls;
-    int32_t* gbase = boff + (size_t)nb * kPlanCls;
+    int32_t* boff = workspace + ws.boff;
+    int32_t* gbase = workspace + ws.gbase;
     if (nb > 0) hipLaunchKernelGGL(k_plan_count, dim3(nb), dim3(kPlanRows), 0, s, records, m, n_actions, bcnt);
     hipLaunchKernelGGL(k_plan_scan, dim3(1), dim3(1024), 0, s, bcnt, nb, m, boff, gbase, plan, row_plan);
     if (nb > 0)
         hipLaunchKernelGGL(k_plan_scatter, dim3(nb), dim3(kPlanRows), 0, s, records, m, n_actions, boff, gbase, perm,
                            rows);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
+    return bgx_launch_status();
 }
 
 extern "C" int bgx_ppo_plan(const uint8_t* records, int32_t m, int32_t n_actions, int32_t* workspace, int32_t* perm,
@@ -1651,67 +1323,5 @@ extern "C" int bgx_ppo_epoch_grads(const float* gw1_dev, const float* gw2_dev, c
                  parts_dev_or_null};
     hipLaunchKernelGGL(k_ppo_epoch_grads, dim3(256 + (guard_dev_or_null ? 1 : 0) + (parts_dev_or_null ? 1 : 0)),
                        dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
-}
-
-extern "C" int64_t bgx_episode_stats_workspace(int32_t B) {
-    if (B < 0) return BGX_EINVAL;
-    return (int64_t)((B + 255) / 256) * kEpStats * (int64_t)sizeof(double);
-}
-
-extern "C" int bgx_episode_stats(const float* rewards, const uint8_t* dones, const uint8_t* records, double* carry,
-                                 int32_t T, int32_t B, double* workspace, double* out, void* stream) {
-    if (T < 0 || B < 0 || !out || (B > 0 && (!carry || !workspace)) ||
-        (T > 0 && B > 0 && (!rewards || !dones || !records)))
-        return BGX_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const int nb = (B + 255) / 256;
-    if (nb > 0)
-        hipLaunchKernelGGL(k_episode_partials, dim3(nb), dim3(256), 0, s, rewards, dones, records, carry, T, B,
-                           workspace);
-    hipLaunchKernelGGL(k_episode_sum, dim3(1), dim3(64), 0, s, workspace, nb, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
-}
-
-extern "C" int bgx_lane_returns(const float* rewards, const uint8_t* dones, int32_t T, int32_t B, float gamma,
-                                float* out, void* stream) {
-    if (T < 0 || B < 0 || (T > 0 && B > 0 && (!rewards || !dones || !out))) return BGX_EINVAL;
-    if (T == 0 || B == 0) return BGX_OK;
-    hipLaunchKernelGGL(k_lane_returns, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, rewards, dones, T, B,
-                       gamma, out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
-}
-
-extern "C" int64_t bgx_selfplay_gae_workspace(int32_t B) {
-    if (B < 0) return BGX_EINVAL;
-    return (int64_t)((B + 255) / 256) * 2 * (int64_t)sizeof(double);
-}
-
-extern "C" int bgx_selfplay_gae(const float* rewards, const uint8_t* dones, const uint8_t* records, const float* values,
-                                const float* boot_values, const uint8_t* boot_records, int32_t T, int32_t B, float g,
-                                float gl, float* adv, float* ret, double* workspace, double* sums, void* stream) {
-    if (T <= 0 || B <= 0 || !rewards || !dones || !records || !values || !adv || !ret) return BGX_EINVAL;
-    if ((boot_values == nullptr) != (boot_records == nullptr)) return BGX_EINVAL;
-    if (sums && !workspace) return BGX_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const int nb = (B + 255) / 256;
-    hipLaunchKernelGGL(k_selfplay_gae, dim3(nb), dim3(256), 0, s, rewards, dones, records, values, boot_values,
-                       boot_records, T, B, g, gl, adv, ret, sums ? workspace : (double*)nullptr);
-    if (sums)
-        hipLaunchKernelGGL(k_selfplay_gae_sum, dim3(1), dim3(64), 0, s, workspace, nb, (double)T * (double)B, sums);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
-}
-
-extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, float eps, void* stream) {
-    if (n <= 0 || !adv || !sums) return BGX_EINVAL;
-    const int64_t n4 = ((uintptr_t)adv & 15) == 0 ? n / 4 : 0;
-    const int64_t work = n4 > 0 ? n4 + 3 : n;                 // threads that find an element
-    const int nb = (int)((work + 255) / 256 < 2048 ? (work + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_normalize_adv, dim3(nb), dim3(256), 0, (hipStream_t)stream, adv, n, n4, sums, eps);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? BGX_OK : bgx_internal_fail(e);
+    return bgx_launch_status();
 }

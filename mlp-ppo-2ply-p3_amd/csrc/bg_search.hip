@@ -49,6 +49,7 @@
 
 #include "bg_engine.h"
 #include "bg_debug.h"
+#include "bg_host.h"
 #include "bg_workspace.h"
 
 using namespace bg;
@@ -1643,10 +1644,6 @@ __global__ __launch_bounds__(256) void k_expand_kept(Args A, const uint8_t* sel,
 
 }  // namespace
 
-extern int bgx_internal_fail(hipError_t e);
-extern void bgx_set_error(const char* msg);
-#define SCK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return bgx_internal_fail(_e); } while (0)
-
 static int value_tiles16(int H) { return (H + 15) / 16; }   // 16 hidden units (hi + lo rows) per MFMA tile
 constexpr int kMaxHidden = 128;                              // 8 tiles: 120 KiB of weights in LDS
 
@@ -1684,7 +1681,7 @@ static int resident_grid(const bgx_engine* e, K kernel, int threads, int per_cu_
     return cus * occ;
 }
 
-// The 1-ply row pipeline on stream s, inside the caller's EngineUse: V of every legal
+// The 1-ply row pipeline on stream s, inside the caller's EngineCall: V of every legal
 // afterstate of the selected lanes, lane i's at vrow[lane_off[i] ..] in move order.
 // bgx_one_ply_sel reduces them to a choice; bgx_two_ply_topk filters its candidates by them
 // (with_kept: room for k_filter's kept counts and kept move lists).
@@ -1700,7 +1697,7 @@ static int one_ply_rows(bgx_engine* e, const float* vpacked, int32_t hidden, flo
     Args& A = e->a;
     const size_t B = (size_t)A.B;
     const OnePlyLayout L(B, (size_t)A.max_moves, with_kept);
-    SCK(e->oneply_ws.reserve(L.bytes(), 0, s, 0));
+    BGX_CK(e->oneply_ws.reserve(L.bytes(), 0, s, 0));
     void* ws = e->oneply_ws.p;
     int32_t* lane_off = L.lane_off.at(ws);
     int64_t* total = L.total.at(ws);
@@ -1720,7 +1717,7 @@ static int one_ply_rows(bgx_engine* e, const float* vpacked, int32_t hidden, flo
     const EvalRowsArgs E{rowkey, rowside, total, vrow, (const uint4*)(vpacked + 4), vpacked + 4 + kKB * slices(NT) * 64 * 4,
                          value_bias};
     hipLaunchKernelGGL(kr, dim3(resident_grid(e, kr, threads, kNoCap)), dim3(threads), 0, s, E);
-    SCK(hipGetLastError());
+    BGX_CK_LAUNCH();
     out = OnePlyRows{lane_off, total, vrow, with_kept ? L.kept.at(ws) : nullptr, with_kept ? L.kept_move.at(ws) : nullptr};
     return BGX_OK;
 }
@@ -1739,7 +1736,7 @@ int bgx_value_pack(const float* W1, const float* b1, const float* wv, const floa
     const int NT = value_tiles16(hidden);
     hipLaunchKernelGGL(k_value_pack16, dim3(1), dim3(1024), 0, (hipStream_t)stream, W1, b1, wv, hidden, NT,
                        (int*)packed, (_Float16*)(packed + 4), packed + 4 + kKB * slices(NT) * 64 * 4);
-    SCK(hipGetLastError());
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1751,16 +1748,15 @@ int bgx_one_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value
 int bgx_one_ply_sel(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
                     int32_t* best_out, float* bestv_out, float* values_out, void* stream) {
     if (!e || !vpacked || !best_out || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
-    SCK(hipSetDevice(e->device));
     hipStream_t s = (hipStream_t)stream;
-    EngineUse use(e, s);
-    SCK(use.err);
+    EngineCall call(e, s);
+    BGX_CK(call.err);
     OnePlyRows r;
     const int rc = one_ply_rows(e, vpacked, hidden, value_bias, sel, false, s, r);
     if (rc != BGX_OK) return rc;
     hipLaunchKernelGGL(k_one_ply_reduce, dim3((e->a.B + 3) / 4), dim3(256), 0, s, e->a, sel, r.lane_off, r.total,
                        r.vrow, best_out, bestv_out, values_out);
-    SCK(hipGetLastError());
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1793,22 +1789,22 @@ static int filter_candidates(const SearchCall& c, const MoveFilter& f, float* q_
     Args& A = c.e->a;
     hipLaunchKernelGGL(k_filter, dim3((A.B + 3) / 4), dim3(256), 0, c.s, A, c.sel, cand.lane_off, cand.total, cand.vrow,
                        f.top_k, f.margin, cand.kept, cand.kept_move, q_out, f.v1_out);
-    SCK(hipGetLastError());
-    SCK(hipMemcpyAsync(cand_host, cand.total, 8, hipMemcpyDeviceToHost, c.s));
+    BGX_CK_LAUNCH();
+    BGX_CK(hipMemcpyAsync(cand_host, cand.total, 8, hipMemcpyDeviceToHost, c.s));
     return BGX_OK;
 }
 
 // Stage 2: zero the counters, lay the rows out per lane (from the kept counts with a
 // filter) and read the row count on the host: the body of the workspace is sized by it.
 static int scan_rows(const SearchCall& c, const TwoPlyLayout& L, const int32_t* kept, int64_t* rows_host) {
-    SCK(c.e->search_ws.reserve(L.head_bytes(), 25, c.s, 0));
+    BGX_CK(c.e->search_ws.reserve(L.head_bytes(), 25, c.s, 0));
     void* ws = c.e->search_ws.p;
     Ctr* ctr = L.ctr.at(ws);
-    SCK(hipMemsetAsync(ctr, 0, 256, c.s));
+    BGX_CK(hipMemsetAsync(ctr, 0, 256, c.s));
     hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, c.s, c.e->a, c.sel, L.lane_off.at(ws), &ctr->rows, 1, kept);
-    SCK(hipGetLastError());
-    SCK(hipMemcpyAsync(rows_host, &ctr->rows, 8, hipMemcpyDeviceToHost, c.s));
-    SCK(hipStreamSynchronize(c.s));
+    BGX_CK_LAUNCH();
+    BGX_CK(hipMemcpyAsync(rows_host, &ctr->rows, 8, hipMemcpyDeviceToHost, c.s));
+    BGX_CK(hipStreamSynchronize(c.s));
     if (*rows_host * 21 >= (int64_t)0x1FFFFFFF) return BGX_EINVAL;     // job ids are 29-bit pool tags
     return BGX_OK;
 }
@@ -1826,12 +1822,12 @@ static int build_rows(const SearchCall& c, const TwoPlyLayout& L, const OnePlyRo
                            cand.kept, cand.lane_off, cand.kept_move, row_lane, row_move);
     else
         hipLaunchKernelGGL(k_expand, dim3((A.B + 3) / 4), dim3(256), 0, c.s, A, c.sel, lane_off, &ctr->rows, row_lane);
-    SCK(hipMemsetAsync(L.minv.at(ws), 0x7F, (size_t)jobs * 4, c.s));
-    SCK(hipMemsetAsync(L.maxlen.at(ws), 0xFF, (size_t)jobs, c.s));
+    BGX_CK(hipMemsetAsync(L.minv.at(ws), 0x7F, (size_t)jobs * 4, c.s));
+    BGX_CK(hipMemsetAsync(L.maxlen.at(ws), 0xFF, (size_t)jobs, c.s));
     hipLaunchKernelGGL(k_rows, dim3((rows + 3) / 4 < 16384 ? (rows + 3) / 4 : 16384), dim3(256), 0, c.s, A, row_lane,
                        lane_off, (const int32_t*)row_move, &ctr->rows, L.rowrec.at(ws), L.rowside.at<uint4>(ws),
                        (uint4*)nullptr, &ctr->bad);
-    SCK(hipGetLastError());
+    BGX_CK_LAUNCH();
     return BGX_OK;
 }
 
@@ -1918,9 +1914,9 @@ static int run_rounds(const SearchCall& c, const EnumPlan& plan, const TwoPlyLay
     void* ws = e->search_ws.p;
     Ctr* ctr = L.ctr.at(ws);
     if (!e->search_ev[0])
-        for (hipEvent_t& ev : e->search_ev) SCK(hipEventCreate(&ev));
-    if (!e->search_side) SCK(hipStreamCreateWithFlags(&e->search_side, hipStreamNonBlocking));
-    SCK(hipEventRecord(e->search_ev[0], s));
+        for (hipEvent_t& ev : e->search_ev) BGX_CK(hipEventCreate(&ev));
+    if (!e->search_side) BGX_CK(hipStreamCreateWithFlags(&e->search_side, hipStreamNonBlocking));
+    BGX_CK(hipEventRecord(e->search_ev[0], s));
     // retry rounds run few waves: every wave holding a block wastes its unused
     // part, and a round must leave pool for its jobs to finish (progress with any pool)
     int gcap = 1 << 30;
@@ -1932,14 +1928,14 @@ static int run_rounds(const SearchCall& c, const EnumPlan& plan, const TwoPlyLay
     };
     for (int round = 0;; ++round) {
         if (round == 0) {       // the non-doubles enumerator beside the doubles one
-            SCK(hipEventRecord(e->search_ev[3], s));
-            SCK(hipStreamWaitEvent(e->search_side, e->search_ev[3], 0));
+            BGX_CK(hipEventRecord(e->search_ev[3], s));
+            BGX_CK(hipStreamWaitEvent(e->search_side, e->search_ev[3], 0));
             hipLaunchKernelGGL(plan.kheavy, dim3(plan.g_heavy), dim3(64), 0, s, S);
             hipLaunchKernelGGL(plan.klight, dim3(plan.g_light), dim3(64), 0, e->search_side, S);
-            SCK(hipEventRecord(e->search_ev[4], e->search_side));
-            SCK(hipStreamWaitEvent(s, e->search_ev[4], 0));
+            BGX_CK(hipEventRecord(e->search_ev[4], e->search_side));
+            BGX_CK(hipStreamWaitEvent(s, e->search_ev[4], 0));
             tiers();
-            SCK(hipEventRecord(e->search_ev[1], s));
+            BGX_CK(hipEventRecord(e->search_ev[1], s));
         } else {
             const long long blocks = (long long)(S.cap / kBlk);
             gcap = (int)(blocks / 16 > 1 ? (blocks / 16 < (1 << 30) ? blocks / 16 : (1 << 30)) : 1);
@@ -1947,17 +1943,17 @@ static int run_rounds(const SearchCall& c, const EnumPlan& plan, const TwoPlyLay
             tiers();
         }
         hipLaunchKernelGGL(plan.keval, dim3(plan.g_eval), dim3(plan.eval_threads), 0, s, E);
-        SCK(hipGetLastError());
-        if (round == 0) SCK(hipEventRecord(e->search_ev[2], s));
-        SCK(hipMemcpyAsync(hc, ctr, sizeof *hc, hipMemcpyDeviceToHost, s));
-        SCK(hipStreamSynchronize(s));
+        BGX_CK_LAUNCH();
+        if (round == 0) BGX_CK(hipEventRecord(e->search_ev[2], s));
+        BGX_CK(hipMemcpyAsync(hc, ctr, sizeof *hc, hipMemcpyDeviceToHost, s));
+        BGX_CK(hipStreamSynchronize(s));
         if (hc->bad) {                      // the lanes changed under the call (bgx.h stream ordering)
             bgx_set_error("bgx_two_ply: the lanes' move lists changed under the call (stream ordering)");
             return BGX_ESTATE;
         }
         if (round == 0) {
-            SCK(hipEventElapsedTime(&e->search_ms[0], e->search_ev[0], e->search_ev[1]));
-            SCK(hipEventElapsedTime(&e->search_ms[1], e->search_ev[1], e->search_ev[2]));
+            BGX_CK(hipEventElapsedTime(&e->search_ms[0], e->search_ev[0], e->search_ev[1]));
+            BGX_CK(hipEventElapsedTime(&e->search_ms[1], e->search_ev[1], e->search_ev[2]));
         }
         if (plan.dbg)
             fprintf(stderr, "[bgx 2-ply] round %d: pool %llu/%zu, tier1 %d, tier2 %d, retry %d, leaves %llu\n", round,
@@ -1965,10 +1961,10 @@ static int run_rounds(const SearchCall& c, const EnumPlan& plan, const TwoPlyLay
         if (hc->retry_count == 0) return BGX_OK;
         if (round + 1 >= kMaxRounds) return BGX_ENOMEM;
         // next round: the lost jobs become the explicit list, the pool starts over
-        SCK(hipMemcpyAsync(L.list.at(ws), L.retry.at(ws), (size_t)hc->retry_count * 4, hipMemcpyDeviceToDevice, s));
-        SCK(hipMemcpyAsync(&ctr->list_count, &ctr->retry_count, 4, hipMemcpyDeviceToDevice, s));
-        SCK(hipMemsetAsync(&ctr->cursor, 0, 8, s));
-        SCK(hipMemsetAsync(ctr->qcount, 0, 16, s));          // qcount[3], retry_count
+        BGX_CK(hipMemcpyAsync(L.list.at(ws), L.retry.at(ws), (size_t)hc->retry_count * 4, hipMemcpyDeviceToDevice, s));
+        BGX_CK(hipMemcpyAsync(&ctr->list_count, &ctr->retry_count, 4, hipMemcpyDeviceToDevice, s));
+        BGX_CK(hipMemsetAsync(&ctr->cursor, 0, 8, s));
+        BGX_CK(hipMemsetAsync(ctr->qcount, 0, 16, s));          // qcount[3], retry_count
     }
 }
 
@@ -1986,8 +1982,8 @@ static int dump_search_state(const std::string& prefix, const S2& S, const EvalA
         if (FILE* f = fopen((prefix + ext).c_str(), "wb")) { fwrite(host.data(), 1, bytes, f); fclose(f); }
         return hipSuccess;
     };
-    SCK(dump(E.minv, (size_t)jobs * 4, ""));
-    SCK(dump(rowpart, rowpart_floats * 4, ".rp"));
+    BGX_CK(dump(E.minv, (size_t)jobs * 4, ""));
+    BGX_CK(dump(rowpart, rowpart_floats * 4, ".rp"));
     (void)dump(S.keys, used * 16, ".keys");
     (void)dump(S.tags, used * 4, ".tags");
     (void)dump(E.vdbg, used * 4, ".v");
@@ -2020,7 +2016,7 @@ static int search_rows(const SearchCall& c, const TwoPlyLayout& L, const OnePlyR
     plan.size_grids(e, jobs);
     // the pool is counted in slots of 20 bytes (key + tag); it may be larger than asked
     // for (kept from a bigger call), the call uses its own pool_slots of it
-    SCK(e->search_pool.reserve(plan.pool_slots * 20, 0, c.s, 0));
+    BGX_CK(e->search_pool.reserve(plan.pool_slots * 20, 0, c.s, 0));
     const size_t pcap = plan.pool_slots;
     uint4* keys = (uint4*)e->search_pool.p;
     uint32_t* tags = (uint32_t*)(keys + pcap);
@@ -2029,8 +2025,8 @@ static int search_rows(const SearchCall& c, const TwoPlyLayout& L, const OnePlyR
                &ctr->list_count, e->a.err, plan.cap_light, plan.cap_heavy, plan.cap_mid, 3, 3, plan.barrow ? 1 : 0};
     DeviceFree vdbg;
     if (!plan.dump.empty()) {
-        SCK(hipMalloc(&vdbg.p, pcap * 4));
-        SCK(hipMemsetAsync(vdbg.p, 0, pcap * 4, c.s));
+        BGX_CK(hipMalloc(&vdbg.p, pcap * 4));
+        BGX_CK(hipMemsetAsync(vdbg.p, 0, pcap * 4, c.s));
     }
     const EvalArgs E{keys, tags, &ctr->zero, &ctr->cursor, (unsigned long long)pcap, rowside, L.maxlen.at(ws),
                      L.minv.at(ws), w1q, c.vpacked + 4 + kKB * slices(c.NT) * 64 * 4, c.value_bias,
@@ -2051,10 +2047,9 @@ static int two_ply_search(bgx_engine* e, const float* vpacked, int32_t hidden, f
                           const MoveFilter* filter, int32_t* best_out, float* bestq_out, float* q_out,
                           uint64_t* stats_host, void* stream) {
     if (!e || !vpacked || !best_out || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
-    SCK(hipSetDevice(e->device));
     const SearchCall c{e, (hipStream_t)stream, vpacked, hidden, value_tiles16(hidden), value_bias, sel};
-    EngineUse use(e, c.s);
-    SCK(use.err);
+    EngineCall call(e, c.s);
+    BGX_CK(call.err);
     OnePlyRows cand{};
     int64_t cand64 = 0, rows64 = 0;                   // candidate afterstates (stats), rows
     int rc = filter ? filter_candidates(c, *filter, q_out, cand, &cand64) : BGX_OK;
@@ -2065,7 +2060,7 @@ static int two_ply_search(bgx_engine* e, const float* vpacked, int32_t hidden, f
     const int64_t jobs64 = rows64 * 21;
     const int rows = (int)rows64, jobs = (int)jobs64;
     L.body((size_t)rows, (size_t)jobs, c.NT, filter != nullptr);
-    SCK(e->search_ws.reserve(L.bytes(), 25, c.s, L.head_bytes()));     // the head (lane_off, counters) is live
+    BGX_CK(e->search_ws.reserve(L.bytes(), 25, c.s, L.head_bytes()));     // the head (lane_off, counters) is live
     if (rows > 0) {
         rc = search_rows(c, L, cand, rows, jobs);
         if (rc != BGX_OK) return rc;
@@ -2075,11 +2070,11 @@ static int two_ply_search(bgx_engine* e, const float* vpacked, int32_t hidden, f
     hipLaunchKernelGGL(k_two_ply_reduce, dim3((e->a.B + 3) / 4), dim3(256), 0, c.s, e->a, sel, L.lane_off.at(ws),
                        &ctr->rows, L.minv.at(ws), (const int32_t*)cand.kept,
                        (const int32_t*)(filter ? L.row_move.at(ws) : nullptr), best_out, bestq_out, q_out);
-    SCK(hipGetLastError());
+    BGX_CK_LAUNCH();
     if (stats_host) {
         unsigned long long lv = 0;
-        SCK(hipMemcpyAsync(&lv, &ctr->leaves, 8, hipMemcpyDeviceToHost, c.s));
-        SCK(hipStreamSynchronize(c.s));
+        BGX_CK(hipMemcpyAsync(&lv, &ctr->leaves, 8, hipMemcpyDeviceToHost, c.s));
+        BGX_CK(hipStreamSynchronize(c.s));
         stats_host[0] = lv;
         stats_host[1] = (uint64_t)jobs64;
         stats_host[2] = (uint64_t)rows64;
@@ -2112,21 +2107,21 @@ int bgx_two_ply_topk(bgx_engine* e, const float* vpacked, int32_t hidden, float 
 #ifdef BGX_COUNTERS
 // this translation unit's work counters (experiments; bg_engine.hip has its own set)
 int bgx_debug_search_counters(unsigned long long* out32) {
-    SCK(hipDeviceSynchronize());
+    BGX_CK(hipDeviceSynchronize());
     constexpr size_t n = 16 * (size_t)bg::kCntSlots;
     std::vector<unsigned long long> h(n), z(n, 0ull);
-    SCK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_scnt), n * 8));
+    BGX_CK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_scnt), n * 8));
     for (int i = 0; i < 16; ++i) {
         out32[i] = 0;
         for (int k = 0; k < bg::kCntSlots; ++k) out32[i] += h[(size_t)i * bg::kCntSlots + k];
     }
-    SCK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(bg::g_cnt), n * 8));   // the move generator's (bg_core.h)
+    BGX_CK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(bg::g_cnt), n * 8));   // the move generator's (bg_core.h)
     for (int i = 0; i < 16; ++i) {
         out32[16 + i] = 0;
         for (int k = 0; k < bg::kCntSlots; ++k) out32[16 + i] += h[(size_t)i * bg::kCntSlots + k];
     }
-    SCK(hipMemcpyToSymbol(HIP_SYMBOL(g_scnt), z.data(), n * 8));
-    SCK(hipMemcpyToSymbol(HIP_SYMBOL(bg::g_cnt), z.data(), n * 8));
+    BGX_CK(hipMemcpyToSymbol(HIP_SYMBOL(g_scnt), z.data(), n * 8));
+    BGX_CK(hipMemcpyToSymbol(HIP_SYMBOL(bg::g_cnt), z.data(), n * 8));
     return BGX_OK;
 }
 #endif

@@ -174,3 +174,76 @@ def test_order_pass_is_idempotent(bgx, B, fork):
         assert np.array_equal(x, y)
     _check_order(B, f[0], f[1])
     assert e.error() == 0
+
+
+def _call_sequence(e, B, u, streams):
+    """reset, 6 steps, a reset of the odd lanes, set_lanes of 8 bear-off records, 6 steps, a
+    movegen of 16 positions, set_fork(False), 4 steps, join: call i on streams[i % len]."""
+    odd = (torch.arange(B, device="cuda") % 2).to(torch.uint8)
+    pos = bearoff_records(16)
+    boards, players = pos[:, :52].contiguous().view(torch.int8), pos[:, CUR].contiguous()
+    dice = pos[:, ROLL0:ROLL1 + 1].contiguous()
+    start = bearoff_records(8)
+    rew = torch.zeros(16, B, dtype=torch.float32, device="cuda")
+    done = torch.zeros(16, B, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    calls = iter(range(1 << 30))
+    out = {}
+
+    def on_next_stream():
+        return torch.cuda.stream(streams[next(calls) % len(streams)])
+
+    def steps(t0, n):
+        for t in range(t0, t0 + n):
+            with on_next_stream():               # the actions on the stream the step runs on
+                e.step(legal_actions(e, u[t]), want_obs=False, out=(rew[t], done[t]))
+
+    with on_next_stream():
+        e.reset(want_obs=False)
+    steps(0, 6)
+    with on_next_stream():
+        e.reset(odd, want_obs=False)
+    with on_next_stream():
+        e.set_lanes(start)
+    steps(6, 6)
+    with on_next_stream():
+        out["movegen"] = e.movegen(boards, players, dice)
+    with on_next_stream():
+        e.set_fork(False)
+    steps(12, 4)
+    with on_next_stream():
+        e.join()
+        out["lanes"] = e.lanes()
+    torch.cuda.synchronize()
+    out["order"] = e.order()
+    out["rew"], out["done"] = rew, done
+    return out
+
+
+@pytest.mark.parametrize("B", [256, 200])
+def test_calls_on_two_streams_equal_one_stream(bgx, B):
+    """The engine orders its own calls (the call guard, the dispatch-order join, the rotating
+    overflow counters): the same calls alternating between two non-default streams with no
+    host synchronisation between them give what they give on one stream.  256 and 200 are
+    the smallest batches whose split dispatch has a light launch on the XCD-aware path
+    (heavy 104) and on the plain one (heavy 86)."""
+    g = torch.Generator(device="cuda").manual_seed(21)
+    u = torch.rand(16, B, device="cuda", generator=g)
+    torch.cuda.synchronize()
+    ex = bgx.Engine(batch=B, max_moves=500, dice="philox", seed=91, auto_reset=True)
+    ey = bgx.Engine(batch=B, max_moves=500, dice="philox", seed=91, auto_reset=True)
+    x = _call_sequence(ex, B, u, [torch.cuda.current_stream()])
+    y = _call_sequence(ey, B, u, [torch.cuda.Stream(), torch.cuda.Stream()])
+    assert torch.equal(x["rew"], y["rew"]) and torch.equal(x["done"], y["done"])
+    idx = torch.arange(500, device="cuda")[None, :]
+    (rec_x, mv_x, nt_x), (rec_y, mv_y, nt_y) = x["lanes"], y["lanes"]
+    assert torch.equal(rec_x, rec_y) and torch.equal(nt_x, nt_y)
+    live = idx < (rec_x[:, 60].long() | (rec_x[:, 61].long() << 8))[:, None]       # entries past n are scratch
+    assert torch.equal(torch.where(live, mv_x, 0), torch.where(live, mv_y, 0))
+    (nm_x, mt_x, mg_x), (nm_y, mt_y, mg_y) = x["movegen"], y["movegen"]
+    assert torch.equal(nm_x, nm_y) and torch.equal(mt_x, mt_y)
+    live = idx < nm_x.long()[:, None]
+    assert torch.equal(torch.where(live, mg_x, 0), torch.where(live, mg_y, 0))
+    for a, b in zip(x["order"], y["order"]):
+        assert np.array_equal(a, b)
+    assert ex.error() == 0 and ey.error() == 0
