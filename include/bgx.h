@@ -311,6 +311,24 @@ int bgx_two_ply_topk(bgx_engine* e, const float* vpacked_dev, int32_t hidden, fl
                      const uint8_t* lane_sel_dev, int32_t top_k, float margin, int32_t* best_out,
                      float* bestq_out, float* q_out, float* v1_out, uint64_t* stats_host, void* stream);
 
+/* The luck of each lane's roll (DESIGN.md §10 "Luck adjustment"; the variance reduction of
+ * position rollouts, which the reference lacks).  Lane i holds board X, mover m (byte 52) and
+ * the roll that was drawn (bytes 53, 54).  For each of the 21 rolls r in bgx_two_ply's order,
+ *   v_r = max over m's legal afterstates b for r of V(enc(b, m))      (the mover's one-hot:
+ *         bgx_one_ply's bestv for the lane (X, m, r)),   v_r = V(enc(X, m)) when m cannot move;
+ *   mean = fma(p_20, v_20, ... fma(p_0, v_0, 0)) in fp32, p_r = 1/36 for doubles, else 2/36;
+ *   luck = v_(the lane's own roll) - mean in fp32   (0 when bytes 53, 54 hold no roll).
+ * vpacked_dev is the ordinary bgx_value_pack pack.  Lanes with lane_sel_dev[i] != 0 (NULL =
+ * every lane) get luck_out[i] and, when it is given, mean_out[i] (float[B] each); the other
+ * lanes' entries are not written.  stats_host (uint64[3], may be NULL) receives {leaves
+ * evaluated, (lane, roll) jobs = 21 x rows, rows = selected lanes}.  An all-zero selection is
+ * BGX_OK with zero stats.  BGX_EINVAL for a NULL engine, pack or luck_out, or hidden out of
+ * range.  It reads the lane records only, not the stored move lists: no BGX_ESTATE case.
+ * Ordered like every engine call.  Synchronises the stream (it sizes its workspace from the
+ * selected-lane count and may run retry rounds, as bgx_two_ply does): not graph-capturable. */
+int bgx_roll_luck(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float value_bias,
+                  const uint8_t* lane_sel_dev, float* luck_out, float* mean_out, uint64_t* stats_host, void* stream);
+
 /* ---- head-to-head arena (csrc/bg_engine.hip; bgx/arena.py) ----
  * Two players A and B play each other on the n lanes of an engine created with
  * auto_reset = 1 until every lane has finished games_per_lane games (the reference has no
@@ -406,6 +424,39 @@ int bgx_rollout_advance(const uint8_t* records_dev, const uint8_t* starts_dev, c
                         const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
                         int32_t games_per_lane, int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev,
                         int64_t* tally_dev, int64_t* active_dev, void* stream);
+
+/* Luck bookkeeping of a rollout (DESIGN.md §10 "Luck adjustment"), beside the state above:
+ * lane_luck float[n] (the running sum of the lane's current game) and luck_tally
+ * int64[n_groups][4] (bgx_rollout_luck_field), both zeroed by the caller.  A game's luck L is
+ * the fp32 sum, in step order, of s * luck over its steps, s = +1 when the step's mover is
+ * the start record's mover, else -1.  Plain kernels, no allocation and no synchronisation:
+ * graph-capturable.
+ * bgx_rollout_luck_add: before the players act, with luck_dev = bgx_roll_luck's luck_out for
+ * the lanes as they stand.  Every lane with sel[i] != 0, except in the first step of a game
+ * (plies[i] == 0) whose start record fixed the roll (byte 53 of starts_dev[i] non-zero: that
+ * roll was not drawn, so it has no luck): lane_luck[i] += records[i][52] == starts[i][52] ?
+ * luck[i] : -luck[i] (one fp32 add).
+ * bgx_rollout_luck_flush: after bgx_step and BEFORE bgx_rollout_advance (sel is still the
+ * step's selection), with the step's done and info.  A lane with sel[i] != 0, a valid group
+ * and a game that bgx_rollout_advance counts (done with a winner) adds, with
+ * Lq = llrintf(lane_luck[i] * 65536) clamped to +-2^21 (0 when not finite; round half even)
+ * and res = +-game_score from the start mover's side, to row group[i]:
+ *   LUCK += Lq, LUCK2 += Lq * Lq, RESLUCK += res * Lq, LUCK_GAMES += 1,
+ * and lane_luck[i] = 0; any other done of a selected lane only zeroes lane_luck[i].  The sums
+ * are integers: run-to-run identical.  Range: Lq^2 <= 2^42, so a row holds 2^21 games at the
+ * clamp (|L| = 32 points each) before LUCK2 could pass 2^63.
+ * BGX_EINVAL for n <= 0, n_groups <= 0 or a NULL pointer. */
+enum bgx_rollout_luck_field {
+    BGX_ROLLOUT_LUCK = 0,         /* sum of Lq (2^-16 points) */
+    BGX_ROLLOUT_LUCK2 = 1,        /* sum of Lq^2 (2^-32) */
+    BGX_ROLLOUT_RESLUCK = 2,      /* sum of res * Lq (2^-16) */
+    BGX_ROLLOUT_LUCK_GAMES = 3    /* games added: equals BGX_ROLLOUT_GAMES of the row */
+};
+int bgx_rollout_luck_add(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* plies_dev,
+                         const uint8_t* sel_dev, const float* luck_dev, int32_t n, float* lane_luck_dev, void* stream);
+int bgx_rollout_luck_flush(const uint8_t* starts_dev, const int32_t* group_dev, const uint8_t* sel_dev,
+                           const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
+                           float* lane_luck_dev, int64_t* luck_tally_dev, void* stream);
 
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row

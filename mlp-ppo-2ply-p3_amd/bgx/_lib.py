@@ -58,6 +58,7 @@ SIGNATURES = {
     "bgx_one_ply_sel": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P]),
     "bgx_two_ply_sel": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
     "bgx_two_ply_topk": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
+    "bgx_roll_luck": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P]),
     "bgx_two_ply_timings": (ctypes.c_int, [_P, _P]),
     "bgx_arena_begin": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
     "bgx_arena_merge": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P]),
@@ -65,6 +66,8 @@ SIGNATURES = {
     "bgx_engine_set_starts": (ctypes.c_int, [_P, _P, _P]),
     "bgx_rollout_begin": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "bgx_rollout_advance": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "bgx_rollout_luck_add": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P]),
+    "bgx_rollout_luck_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),

@@ -10,7 +10,8 @@ rollout_moves, "which of these moves is best when the game is played out?".
 Every lane holds one position as its start record: the engine's auto-reset refills the lane
 with it in the step that ends a game, so no lane waits for the longest game of a wave.  One
 player acts for both sides.  Equity is in points (1 / 2 / 3 per game, cubeless) from the
-side of the position's mover.
+side of the position's mover.  --luck: the luck-adjusted (variance-reduced) estimate beside the
+raw one (summarize_luck; DESIGN.md "Luck adjustment").
 """
 from __future__ import annotations
 
@@ -29,6 +30,10 @@ from .engine import Engine, R_CUR, R_ROLL0, R_ROLL1, _ptr, validate_starts
 
 # tally int64[n_groups][8] (include/bgx.h bgx_rollout_field)
 FIELDS = ("games", "plies", "win1", "win2", "win3", "loss1", "loss2", "loss3")
+# luck_tally int64[n_groups][4] (include/bgx.h bgx_rollout_luck_field): fixed point, 2^-16 points
+LUCK_FIELDS = ("luck", "luck2", "resluck", "luck_games")
+LUCK_ONE = 65536                    # Lq = rint(L * LUCK_ONE)
+LUCK_CLAMP = 1 << 21                # |Lq| <= LUCK_CLAMP
 ROLLS36 = [(a, b) for a in range(1, 7) for b in range(1, 7)]       # the 36 ordered rolls
 FIRST_ROLLS = ("stratified", "random")
 
@@ -58,6 +63,88 @@ def summarize(tally_row, unfinished: int = 0) -> dict:
              loss=sum(l) * inv, loss_gammon=(l[1] + l[2]) * inv, loss_backgammon=l[2] * inv,
              equity=eq, equity_stderr=math.sqrt(var), unfinished=int(unfinished))
     return r
+
+
+def summarize_luck(tally_row, luck_row, scale="fit", unfinished: int = 0) -> dict:
+    """summarize(tally_row, unfinished) plus the luck-adjusted estimate from the row's 4 luck
+    sums (LUCK_FIELDS; DESIGN.md "Luck adjustment").  A game's adjusted result is
+    y = res - c L with L its luck (the sum over its rolls of the value after the roll that came
+    minus the mean over all 21 rolls, signed for the start mover).  E[L] = 0, so any constant
+    c leaves the mean unbiased.  In fp64 from the integer sums, n = games, sum L = LUCK / 2^16,
+    sum L^2 = LUCK2 / 2^32, sum res L = RESLUCK / 2^16:
+        equity_luck = (sum res - c sum L) / n
+        var_y = (sum res^2 - 2 c sum res L + c^2 sum L^2 - n equity_luck^2) / (n - 1), >= 0
+        equity_luck_stderr = sqrt(var_y / n)        variance_ratio = var_y / var_res
+    (variance_ratio 1.0 when var_res is 0; n < 2: the stderr is 0).  `scale` = "fit": the
+    control-variate coefficient c = cov(res, L) / var(L) of these games (0 when var(L) is 0),
+    which absorbs the unit difference between the net's reward scale and points and never
+    raises the variance in the limit; fitted on the same games, it biases equity_luck by
+    O(1/n).  A float: that fixed c (1.0 when the net's values are in points).  Adds luck_scale
+    (c), luck_mean (sum L / n), equity_luck, equity_luck_stderr and variance_ratio.  Raises
+    ValueError when the luck row counts other games than the tally row."""
+    r = summarize(tally_row, unfinished)
+    k = [int(v) for v in luck_row]
+    if len(k) != len(LUCK_FIELDS):
+        raise ValueError(f"summarize_luck: a luck row has {len(LUCK_FIELDS)} entries, got {len(k)}")
+    n = r["games"]
+    if k[3] != n:
+        raise ValueError(f"summarize_luck: the luck row counts {k[3]} games, the tally row {n}")
+    sl, sl2, srl = k[0] / LUCK_ONE, k[1] / (LUCK_ONE * LUCK_ONE), k[2] / LUCK_ONE
+    w, l = [r[f"win{j}"] for j in (1, 2, 3)], [r[f"loss{j}"] for j in (1, 2, 3)]
+    sr = sum((j + 1) * (w[j] - l[j]) for j in range(3))
+    sr2 = float(sum((j + 1) ** 2 * (w[j] + l[j]) for j in range(3)))
+    if scale == "fit":
+        # numerator and denominator times n, as exact integers: a constant result gives 0
+        num, den = n * k[2] - sr * k[0], n * k[1] - k[0] * k[0]
+        c = LUCK_ONE * (num / den) if den > 0 else 0.0
+    else:
+        c = float(scale)
+    inv = 1.0 / n if n > 0 else 0.0
+    eq = (sr - c * sl) * inv
+    var_y = max(sr2 - 2.0 * c * srl + c * c * sl2 - n * eq * eq, 0.0) / (n - 1) if n > 1 else 0.0
+    var_r = max(sr2 - n * r["equity"] ** 2, 0.0) / (n - 1) if n > 1 else 0.0
+    r.update(luck_scale=c, luck_mean=sl * inv, equity_luck=eq, equity_luck_stderr=math.sqrt(var_y * inv),
+             variance_ratio=var_y / var_r if var_r > 0.0 else 1.0)
+    return r
+
+
+def luck_tally_reference(luck, mover, done, info, starts, group, n_groups: int, games_per_lane: int) -> np.ndarray:
+    """The luck tally int64[n_groups, 4] of a traced run on the host, with the arithmetic of
+    bgx_rollout_luck_add / bgx_rollout_luck_flush (include/bgx.h): per lane the fp32 sum in
+    step order of +-luck, left out in a game's first step when the start record fixed the
+    roll; at a counted game's end Lq = rint(fp32(sum * 65536)) (round half even) clamped to
+    +-2^21, 0 when not finite.  `luck`, `mover`, `done`, `info`: [steps, B] as run_lanes
+    traces them; `starts` uint8[B, 64]; `group` int32[B].  A lane is active while its group is
+    in [0, n_groups) and it has finished fewer than `games_per_lane` games."""
+    luck = np.asarray(luck, np.float32)
+    mover, done, info = np.asarray(mover), np.asarray(done), np.asarray(info).astype(np.int64)
+    starts, group = np.asarray(starts), np.asarray(group).astype(np.int64)
+    B, P, G = group.shape[0], int(n_groups), int(games_per_lane)
+    valid = (group >= 0) & (group < P)
+    fixed = starts[:, R_ROLL0] != 0
+    lane = np.zeros(B, np.float32)
+    plies = np.zeros(B, np.int64)
+    games = np.zeros(B, np.int64)
+    tally = np.zeros((P, len(LUCK_FIELDS)), np.int64)
+    for t in range(luck.shape[0]):
+        sel = valid & (games < G)
+        add = sel & ~((plies == 0) & fixed)
+        signed = np.where(mover[t] == starts[:, R_CUR], luck[t], -luck[t]).astype(np.float32)
+        lane = np.where(add, (lane + np.where(add, signed, np.float32(0))).astype(np.float32), lane)
+        winner = ((info[t] >> 8) & 0xFF) - 1
+        score = np.clip((info[t] >> 16) & 0xFF, 1, 3)
+        dn = sel & (done[t] != 0)
+        fin = dn & (winner >= 0)
+        x = (lane * np.float32(LUCK_ONE)).astype(np.float32)
+        x = np.where(np.isfinite(x), np.clip(x, -float(LUCK_CLAMP), float(LUCK_CLAMP)), 0.0)
+        lq = np.rint(x).astype(np.int64)
+        res = np.where(winner == (starts[:, R_CUR] & 1), score, -score)
+        for f, v in enumerate((lq, lq * lq, res * lq, np.ones(B, np.int64))):
+            np.add.at(tally[:, f], group[fin], v[fin])
+        lane = np.where(dn, np.float32(0), lane)
+        plies = np.where(sel, np.where(fin, 0, plies + 1), plies)
+        games += fin
+    return tally
 
 
 def layout(n_positions: int, trials: int, first_roll: str = "stratified", batch: int = 4096):
@@ -127,10 +214,11 @@ class Rollout:
         self.sel = torch.zeros(self.B, dtype=torch.uint8, device=dev)
         self.active = torch.zeros(1, dtype=torch.int64, device=dev)
         self.actions = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.lane_luck = torch.zeros(self.B, dtype=torch.float32, device=dev)     # luck of the current games
         self.steps = 0                  # steps of every run so far: the players' random streams go on
 
     def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
-                  trace: bool = False):
+                  trace: bool = False, luck=None):
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
@@ -139,7 +227,15 @@ class Rollout:
         engine keeps the table afterwards.  Returns (tally int64[n_groups, 8], unfinished
         int64[n_groups] = scheduled games that did not end, trace): trace (None without
         trace=True) holds per-step [steps, B] tensors mover, action, done, info, and the final
-        games_done and active."""
+        games_done and active.
+
+        `luck` (a search.ValueHead; DESIGN.md "Luck adjustment"): every step first takes the
+        luck of the active lanes' rolls under that value head and adds it to their games
+        (roll_luck on sel, luck_add, act, step, luck_flush, advance; the host reads the
+        active-lane count every step, as roll_luck synchronises anyway).  The games are the
+        same as without it.  A fourth result follows the trace: luck_tally int64[n_groups, 4]
+        (LUCK_FIELDS), and the trace gains the per-step luck f32[steps, B] (NaN on lanes
+        that never were active).  None: exactly the three results above."""
         max_steps, G, P = int(max_steps), int(games_per_lane), int(n_groups)
         if max_steps < 0 or G < 0 or P <= 0:
             raise ValueError(f"run_lanes: max_steps {max_steps}, games_per_lane {G} must be >= 0, n_groups {P} > 0")
@@ -159,16 +255,27 @@ class Rollout:
         eng.reset(want_obs=False)
         check(L.bgx_rollout_begin(recs, _ptr(starts), _ptr(grp), self.B, P, G, *state, _stream(dev)),
               "bgx_rollout_begin")
+        if luck is not None:
+            from .search import roll_luck
+            luck_tally = torch.zeros(P, len(LUCK_FIELDS), dtype=torch.int64, device=dev)
+            lbuf = torch.full((self.B,), float("nan"), dtype=torch.float32, device=dev)
+            self.lane_luck.zero_()
         tr = None
         if trace:
             tr = {n: torch.zeros(max_steps, self.B, dtype=dt, device=dev)
                   for n, dt in (("mover", torch.uint8), ("action", torch.int32), ("done", torch.uint8),
-                                ("info", torch.int32))}
+                                ("info", torch.int32)) + ((("luck", torch.float32),) if luck is not None else ())}
             rec = torch.empty(self.B, 64, dtype=torch.uint8, device=dev)
-        every = SYNC_EVERY if getattr(player, "sync_free", False) else 1
+        every = SYNC_EVERY if getattr(player, "sync_free", False) and luck is None else 1
         steps = 0
         active = int(self.active.item())
         while active > 0 and steps < max_steps:
+            if luck is not None:
+                roll_luck(eng, luck, sel=self.sel, out=(lbuf, None))
+                check(L.bgx_rollout_luck_add(recs, _ptr(starts), _ptr(self.plies), _ptr(self.sel), _ptr(lbuf), self.B,
+                                             _ptr(self.lane_luck), _stream(dev)), "bgx_rollout_luck_add")
+                if trace:
+                    tr["luck"][steps] = lbuf
             act = player.act(eng, self.sel, self.steps)
             if (not isinstance(act, torch.Tensor) or act.dtype != torch.int32 or act.device != dev
                     or not act.is_contiguous() or act.numel() != self.B):
@@ -181,6 +288,10 @@ class Rollout:
                 tr["mover"][steps] = rec[:, R_CUR]
                 tr["action"][steps] = self.actions
             _, _, done, info = eng.step(self.actions, want_obs=False, want_info=True)
+            if luck is not None:
+                check(L.bgx_rollout_luck_flush(_ptr(starts), _ptr(grp), _ptr(self.sel), _ptr(done), _ptr(info), self.B,
+                                               P, _ptr(self.lane_luck), _ptr(luck_tally), _stream(dev)),
+                      "bgx_rollout_luck_flush")
             check(L.bgx_rollout_advance(recs, _ptr(starts), _ptr(grp), _ptr(done), _ptr(info), self.B, P, G,
                                         *state, _stream(dev)), "bgx_rollout_advance")
             if trace:
@@ -195,32 +306,41 @@ class Rollout:
         if trace:
             tr = {n: v[:steps] for n, v in tr.items()}
             tr.update(games_done=self.games_done.clone(), active=int(self.active.item()))
-        return tally, unfinished, tr
+        return (tally, unfinished, tr) if luck is None else (tally, unfinished, tr, luck_tally)
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
-            trace: bool = False):
+            trace: bool = False, luck=None, luck_scale="fit"):
         """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
         bytes come from the layout) `trials` times with `player` (any arena player object)
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
         (the rest is reported as `unfinished`); standard openings again afterwards.  Returns
         the list of the positions' results (summarize); with trace=True also the last
-        pass's trace with its group, starts and games_per_lane."""
+        pass's trace with its group, starts and games_per_lane.  `luck` (a search.ValueHead):
+        the luck-adjusted rollout (run_lanes); the results are summarize_luck's, with
+        `luck_scale` ("fit" or a float) as its scale."""
         pos = _records(positions)
         P = pos.shape[0]
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
-        total = unfinished = tr = None
+        total = unfinished = tr = ltotal = None
         for k in range(passes):
             grp = torch.from_numpy(group[k])
             starts = pos[grp.clamp(min=0).long()].clone()          # idle lanes: a valid record, never counted
             starts[:, R_ROLL0:R_ROLL1 + 1] = torch.from_numpy(roll[k])
-            tally, unf, tr = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace)
+            out = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck)
+            tally, unf, tr = out[:3]
+            if luck is not None:
+                ltotal = out[3] if ltotal is None else ltotal + out[3]
             total = tally if total is None else total + tally
             unfinished = unf if unfinished is None else unfinished + unf
             if trace:
                 tr.update(group=grp, starts=starts, games_per_lane=G)
         self.eng.set_starts(None)
         rows, unf = total.cpu().tolist(), unfinished.cpu().tolist()
-        res = [summarize(rows[p], unf[p]) for p in range(P)]
+        if luck is not None:
+            lrows = ltotal.cpu().tolist()
+            res = [summarize_luck(rows[p], lrows[p], luck_scale, unf[p]) for p in range(P)]
+        else:
+            res = [summarize(rows[p], unf[p]) for p in range(P)]
         return (res, tr) if trace else res
 
 
@@ -250,13 +370,16 @@ def decode_move(v: int):
 
 
 def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str = "stratified",
-                  max_steps: int = 4000) -> list:
+                  max_steps: int = 4000, luck=None, luck_scale="fit") -> list:
     """A decision: `record` (uint8[64]) holds the board, the mover and the roll to play.  Every
     legal move's afterstate is rolled out with the opponent on roll and the move's equity is
     minus that rollout's; moves that reach the same afterstate share one rollout.  A move
     that ends the game is scored exactly and spends no lanes (`games` 0, `exact` True).
     Returns one dict per move, best first: move (the encoded uint64), submoves, equity,
-    equity_stderr, games, exact.  No legal move: one entry with move None (the pass)."""
+    equity_stderr, games, exact.  No legal move: one entry with move None (the pass).
+    `luck` / `luck_scale` (Rollout.run): luck-adjusted rollouts; every entry also has
+    equity_luck, equity_luck_stderr, luck_scale and variance_ratio (an exact move: its score,
+    0, 0 and 1), and the order is by equity_luck."""
     rec = torch.as_tensor(record).reshape(-1)
     if rec.numel() != 64 or rec.dtype != torch.uint8:
         raise ValueError("rollout_moves: record must be 64 bytes (uint8)")
@@ -284,7 +407,8 @@ def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str
         pos = np.zeros((len(uniq), 64), np.uint8)
         pos[:, :52] = uniq.view(np.uint8)
         pos[:, R_CUR] = 1 - mover
-        res = rollout.run(player, torch.from_numpy(pos), trials, first_roll=first_roll, max_steps=max_steps)
+        res = rollout.run(player, torch.from_numpy(pos), trials, first_roll=first_roll, max_steps=max_steps,
+                          luck=luck, luck_scale=luck_scale)
         for i, u in zip(open_idx, np.asarray(inverse).reshape(-1)):
             results[i] = res[int(u)]
     out = []
@@ -292,12 +416,18 @@ def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str
         if scores[i]:
             out.append(dict(move=m, submoves=decode_move(m), equity=float(scores[i]), equity_stderr=0.0, games=0,
                             exact=True, unfinished=0))
+            if luck is not None:
+                out[-1].update(equity_luck=float(scores[i]), equity_luck_stderr=0.0, luck_scale=0.0,
+                               variance_ratio=1.0)
         else:
             r = results[i]
             out.append(dict(move=m, submoves=decode_move(m) if m is not None else [], equity=-r["equity"],
                             equity_stderr=r["equity_stderr"], games=r["games"], exact=False,
                             unfinished=r["unfinished"]))
-    out.sort(key=lambda d: -d["equity"])
+            if luck is not None:
+                out[-1].update(equity_luck=-r["equity_luck"], equity_luck_stderr=r["equity_luck_stderr"],
+                               luck_scale=r["luck_scale"], variance_ratio=r["variance_ratio"])
+    out.sort(key=lambda d: -d["equity_luck" if luck is not None else "equity"])
     return out
 
 
@@ -328,8 +458,20 @@ def load_positions(path: str) -> torch.Tensor:
     return out
 
 
+def _luck_scale(text: str):
+    if text == "fit":
+        return text
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--luck-scale takes 'fit' or a number, got {text!r}")
+    if not math.isfinite(v):
+        raise argparse.ArgumentTypeError("--luck-scale must be finite")
+    return v
+
+
 class _Parser(argparse.ArgumentParser):
-    """--top-k is an error for any player but a 2ply one with weights."""
+    """--top-k is an error for any player but a 2ply one with weights; --luck needs weights."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -338,6 +480,8 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--top-k needs --player 2ply with weights")
             if ns.top_k < 1:
                 self.error("--top-k must be >= 1")
+        if ns.luck and ns.net == "random":
+            self.error("--luck needs --net with weights (the luck is measured by the net's value head)")
         if ns.trials < 1 or ns.batch < 1:
             self.error("--trials and --batch must be >= 1")
         return ns
@@ -356,6 +500,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--max-steps", type=int, default=4000,
                     help="env steps per pass after which it stops (unfinished games are reported)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--luck", action="store_true",
+                    help="luck-adjusted (variance-reduced) rollout with the net's value head; needs weights")
+    ap.add_argument("--luck-scale", type=_luck_scale, default="fit",
+                    help="'fit' (the control-variate coefficient of the games) or a fixed number")
     return ap
 
 
@@ -370,7 +518,12 @@ def main(argv=None):
     ro = Rollout(args.batch, seed=args.seed, max_moves=max_moves, device=dev)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps)
+    vh = None
+    if args.luck:
+        from .search import ValueHead
+        vh = ValueHead(net)
+    res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
+                 luck_scale=args.luck_scale)
     dt = time.perf_counter() - t0
     for i, r in enumerate(res):
         print(json.dumps(dict(position=i, **r)), flush=True)
@@ -380,6 +533,8 @@ def main(argv=None):
                    trials=args.trials, first_roll=args.first_roll, batch=args.batch, max_steps=args.max_steps,
                    seed=args.seed, seconds=dt, games_per_s=games / dt if dt > 0 else 0.0,
                    env_steps_per_s=ro.steps * args.batch / dt if dt > 0 else 0.0)
+    if args.luck:
+        summary.update(luck=True, luck_scale=args.luck_scale)
     print(json.dumps(summary), flush=True)
     return res, summary
 

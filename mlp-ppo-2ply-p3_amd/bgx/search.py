@@ -153,6 +153,35 @@ def two_ply(eng: Engine, vh: ValueHead, want_q: bool = False, sel: torch.Tensor 
     return (best, bestq, q, st, v1) if want_v1 else (best, bestq, q, st)
 
 
+def roll_luck(eng: Engine, vh: ValueHead, sel: torch.Tensor | None = None, out=None):
+    """The luck of every lane's roll (bgx_roll_luck; DESIGN.md §10 "Luck adjustment"): with
+    v_r = the best 1-ply value of the lane's mover for roll r (V of the position itself when
+    it cannot move), mean = sum_r p_r v_r over the 21 rolls and luck = v of the roll the lane
+    holds - mean.  Returns (luck f32[B], mean f32[B], stats {leaves, jobs, rows}).  `sel`
+    (uint8[B] on the device) as in one_ply: only lanes with sel != 0 are computed and
+    written; `out` = (luck, mean or None) keeps the other entries as they were, else they are
+    NaN.  Synchronises the stream, as two_ply does."""
+    L = _lib.load()
+    B, dev = eng.batch, eng.device
+    _check_sel(eng, sel)
+    if out is not None:
+        luck, mean = out
+        for t in (luck, mean):
+            if t is not None and (t.dtype != torch.float32 or t.device != dev or not t.is_contiguous()
+                                  or t.numel() != B):
+                raise ValueError("roll_luck: out must be contiguous (float32[B], float32[B] or None) on the "
+                                 "engine's device")
+        if luck is None:
+            raise ValueError("roll_luck: out needs the luck tensor")
+    else:
+        luck = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
+        mean = torch.full((B,), float("nan"), dtype=torch.float32, device=dev)
+    stats = (ctypes.c_uint64 * 3)()
+    check(L.bgx_roll_luck(eng._h, _ptr(vh.packed), vh.hidden, vh.bias, _ptr(sel), _ptr(luck), _ptr(mean),
+                          ctypes.cast(stats, ctypes.c_void_p), _stream(dev)), "bgx_roll_luck")
+    return luck, mean, {"leaves": int(stats[0]), "jobs": int(stats[1]), "rows": int(stats[2])}
+
+
 def two_ply_timings(eng: Engine):
     """(enumeration ms, evaluation ms) of the last two_ply call's first round,
     timed with HIP events on the caller's stream."""

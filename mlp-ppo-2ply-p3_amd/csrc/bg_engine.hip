@@ -703,6 +703,65 @@ __global__ __launch_bounds__(256) void k_rollout_advance(const uint8_t* starts, 
     tally_add(active, 0, -count(retired));
 }
 
+// ---- luck-adjusted rollouts (DESIGN.md "Luck adjustment"; bgx_roll_luck gives luck[i]) ----
+// lane_luck float[n] holds the running fp32 sum of s * luck over the steps of the lane's
+// current game, s = +1 when the step's mover is the start record's mover, else -1.  The roll
+// of a game's first step is left out when the start record fixed it (it was not drawn).
+__global__ __launch_bounds__(256) void k_rollout_luck_add(const uint8_t* recs, const uint8_t* starts,
+                                                          const int32_t* plies, const uint8_t* sel, const float* luck,
+                                                          int n, float* lane_luck) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !sel[i]) return;
+    if (plies[i] == 0 && starts[(size_t)i * 64 + R_ROLL0] != 0) return;
+    const float l = luck[i];
+    lane_luck[i] += recs[(size_t)i * 64 + R_CUR] == starts[(size_t)i * 64 + R_CUR] ? l : -l;
+}
+
+__device__ __forceinline__ long long wave_sum(long long v) {
+    #pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// After the step, before k_rollout_advance (sel is still the step's selection): a counted
+// game (k_rollout_advance's rule) adds its luck in 2^-16 fixed point to its group's row and
+// zeroes the lane's sum; any other done of a selected lane only zeroes it.  Per wave, one
+// add per (group, field) it holds finishers of; integer adds commute.
+__global__ __launch_bounds__(256) void k_rollout_luck_flush(const uint8_t* starts, const int32_t* group,
+                                                            const uint8_t* sel, const uint8_t* done,
+                                                            const int32_t* info, int n, int n_groups,
+                                                            float* lane_luck, int64_t* luck_tally) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool on = i < n && sel[i] != 0;
+    const int g = on ? rollout_group(group, i, n_groups) : -1;
+    const bool dn = on && done[i] != 0;
+    const int inf = dn ? info[i] : 0;
+    const int winner = ((inf >> 8) & 0xFF) - 1, score = min(max((inf >> 16) & 0xFF, 1), 3);
+    const bool fin = dn && g >= 0 && winner >= 0;
+    long long lq = 0, res = 0;
+    if (fin) {
+        float x = lane_luck[i] * 65536.0f;
+        x = isfinite(x) ? fminf(fmaxf(x, -2097152.0f), 2097152.0f) : 0.0f;
+        lq = llrintf(x);
+        res = winner == (int)(starts[(size_t)i * 64 + R_CUR] & 1) ? score : -score;
+    }
+    if (dn) lane_luck[i] = 0.0f;
+    uint64_t rest = __ballot(fin);
+    while (rest) {
+        const int lead = __ffsll((unsigned long long)rest) - 1;
+        const int gl = __shfl(g, lead, 64);
+        const bool mine = fin && g == gl;
+        const uint64_t m = __ballot(mine);
+        const long long v = mine ? lq : 0;
+        int64_t* row = luck_tally + (size_t)gl * 4;
+        tally_add(row, BGX_ROLLOUT_LUCK, wave_sum(v));
+        tally_add(row, BGX_ROLLOUT_LUCK2, wave_sum(v * v));
+        tally_add(row, BGX_ROLLOUT_RESLUCK, wave_sum(mine ? res * lq : 0));
+        tally_add(row, BGX_ROLLOUT_LUCK_GAMES, (long long)__popcll(m));
+        rest &= ~m;
+    }
+}
+
 // murmur3's 64-bit finalizer
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
     x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull;
@@ -1368,6 +1427,28 @@ int bgx_rollout_advance(const uint8_t* records_dev, const uint8_t* starts_dev, c
     hipLaunchKernelGGL(k_rollout_advance, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, starts_dev,
                        group_dev, done_dev, info_dev, n, n_groups, games_per_lane, games_done_dev, plies_dev, sel_dev,
                        tally_dev, active_dev);
+    BGX_CK_LAUNCH();
+    return BGX_OK;
+}
+
+int bgx_rollout_luck_add(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* plies_dev,
+                         const uint8_t* sel_dev, const float* luck_dev, int32_t n, float* lane_luck_dev, void* stream) {
+    if (!records_dev || !starts_dev || !plies_dev || !sel_dev || !luck_dev || n <= 0 || !lane_luck_dev)
+        return BGX_EINVAL;
+    hipLaunchKernelGGL(k_rollout_luck_add, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, records_dev,
+                       starts_dev, plies_dev, sel_dev, luck_dev, n, lane_luck_dev);
+    BGX_CK_LAUNCH();
+    return BGX_OK;
+}
+
+int bgx_rollout_luck_flush(const uint8_t* starts_dev, const int32_t* group_dev, const uint8_t* sel_dev,
+                           const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
+                           float* lane_luck_dev, int64_t* luck_tally_dev, void* stream) {
+    if (!starts_dev || !group_dev || !sel_dev || !done_dev || !info_dev || n <= 0 || n_groups <= 0 ||
+        !lane_luck_dev || !luck_tally_dev)
+        return BGX_EINVAL;
+    hipLaunchKernelGGL(k_rollout_luck_flush, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, starts_dev,
+                       group_dev, sel_dev, done_dev, info_dev, n, n_groups, lane_luck_dev, luck_tally_dev);
     BGX_CK_LAUNCH();
     return BGX_OK;
 }

@@ -32,6 +32,10 @@
 // bgx_two_ply_topk: the 1-ply rows' V, k_filter (the top_k best moves within a margin of the
 // best, per lane), k_expand_kept (row -> lane, row -> move), then the 2-ply pipeline on
 // the kept rows alone (DESIGN.md §5 "Move filter").
+// bgx_roll_luck: the same stages on rows made from the lanes' own boards (k_luck_scan,
+// k_luck_rows) with the luck form of the value pack (k_luck_pack), then k_luck_reduce: the
+// mean over the 21 rolls of the mover's best 1-ply value and the luck of the lane's roll
+// (DESIGN.md §10 "Luck adjustment").
 // The reference's filter_full_moves_by_max_submoves (get_all_moves.py:73-94) is
 // applied by the evaluator: a leaf counts iff its sub-move count equals the
 // job's final maximum (written at job end), which is exactly "first insertion
@@ -1642,6 +1646,112 @@ __global__ __launch_bounds__(256) void k_expand_kept(Args A, const uint8_t* sel,
     }
 }
 
+// ---- roll luck (bgx_roll_luck; DESIGN.md §10 "Luck adjustment") ----
+// The 2-ply pipeline on the lanes' own boards: a row is a selected lane's board with no move
+// applied and the player on roll m as the replier, so job (row, r) enumerates m's moves for
+// roll r.  The pipeline gives leaves the one-hot of 1 - q and reduces with min; luck needs
+// the one-hot of q = m and max.  k_luck_pack derives the luck form of the value pack:
+// block 12's two one-hot weights exchanged (the leaf then sees m's one-hot), wvq and the
+// bias negated (V' = -V, every product and sum negated exactly), so that
+//   min_b V'(enc(b, 1 - q)) = -max_b V(enc(b, q))
+// with k_enum*, k_rowpart and k_eval as they are; k_luck_reduce negates it back.
+
+// k_scan with one row per selected lane: PLAYER1 movers' rows first, each group in lane order
+__global__ __launch_bounds__(1024) void k_luck_scan(Args A, const uint8_t* sel, int32_t* lane_off, int64_t* total) {
+    __shared__ int32_t part[2][1024];
+    const int t = threadIdx.x;
+    const int per = (A.B + 1023) / 1024;
+    const int lo = min(A.B, t * per), hi = min(A.B, lo + per);
+    int32_t sum[2] = {0, 0};
+    for (int i = lo; i < hi; ++i)
+        if (lane_selected(sel, i)) ++sum[A.lanes[(size_t)i * 64 + R_CUR] & 1];
+    part[0][t] = sum[0];
+    part[1][t] = sum[1];
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const int32_t v0 = t >= o ? part[0][t - o] : 0, v1 = t >= o ? part[1][t - o] : 0;
+        __syncthreads();
+        part[0][t] += v0;
+        part[1][t] += v1;
+        __syncthreads();
+    }
+    int32_t run[2] = {part[0][t] - sum[0], part[0][1023] + part[1][t] - sum[1]};
+    for (int i = lo; i < hi; ++i) {
+        const int g = A.lanes[(size_t)i * 64 + R_CUR] & 1;
+        lane_off[i] = run[g];
+        if (lane_selected(sel, i)) ++run[g];
+    }
+    if (t == 1023) *total = (int64_t)part[0][1023] + part[1][1023];
+}
+
+// a selected lane's row, held inside the scanned range (-1: none)
+__device__ __forceinline__ int luck_row(const uint8_t* sel, int i, const int32_t* lane_off, int64_t total) {
+    if (!lane_selected(sel, i)) return -1;
+    const int row = lane_off[i];
+    return row >= 0 && row < total ? row : -1;
+}
+
+// rows from lanes, one wave per lane: the lane's board as the row record with replier
+// q = m (byte 52), and the other side's points, bar and off as the row side (k_rows' format)
+__global__ __launch_bounds__(256) void k_luck_rows(Args A, const uint8_t* sel, const int32_t* lane_off,
+                                                   const int64_t* total, int32_t* row_lane, uint8_t* rowrec,
+                                                   uint4* rowside) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= A.B) return;
+    const int row = luck_row(sel, i, lane_off, *total);
+    if (row < 0) return;
+    const int l = lane_id();
+    const int bv = load_rec(A, i);
+    const int m = rd(bv, R_CUR) & 1;
+    uint32_t blocked;
+    const Node s = node_from_bytes(bv, 1 - m, blocked);
+    rowrec[(size_t)row * 64 + l] = (uint8_t)(l < 52 ? bv : (l == 52 ? m : 0));
+    if (l == 0) {
+        row_lane[row] = i;
+        rowside[row] = make_uint4((uint32_t)s.lo, (uint32_t)(s.lo >> 32), s.hi,
+                                  (s.k3 & 15u) | (((s.k3 >> 4) & 15u) << 4) | ((uint32_t)m << 8));
+    }
+}
+
+// the luck form of a value pack (layout above sz_f16), on the words' bits: hdr and w1q
+// copied, except dword 2 of every block-12 fragment (f16 elements 4, 5: the one-hot
+// columns), whose halves are exchanged; wvq with the sign bit flipped
+__global__ __launch_bounds__(256) void k_luck_pack(const uint32_t* src, int NT, uint32_t* dst) {
+    const int NS = slices(NT);
+    const int b12 = 4 + 12 * NS * 64 * 4, wv0 = 4 + kKB * NS * 64 * 4, n = wv0 + NS * 8 * 64;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < n; idx += gridDim.x * 256) {
+        uint32_t v = src[idx];
+        if (idx >= wv0) v ^= 0x80000000u;
+        else if (idx >= b12 && ((idx - 4) & 3) == 2) v = (v >> 16) | (v << 16);
+        dst[idx] = v;
+    }
+}
+
+// mean = sum_r p_r v_r (fp32 FMA, r in roll order, k_two_ply_reduce's constants) with
+// v_r = -minv[row][r], luck = v of the lane's own roll - mean; one thread per lane.  A lane
+// whose roll bytes are not two dice in 1..6 gets luck 0 (nothing was rolled).
+__global__ __launch_bounds__(256) void k_luck_reduce(Args A, const uint8_t* sel, const int32_t* lane_off,
+                                                     const int64_t* total, const int32_t* minv, float* luck,
+                                                     float* mean_out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= A.B) return;
+    const int row = luck_row(sel, i, lane_off, *total);
+    if (row < 0) return;
+    const uint8_t* rr = A.lanes + (size_t)i * 64;
+    const int d0 = rr[R_ROLL0], d1 = rr[R_ROLL1];
+    const int lo = min(d0, d1), hi = max(d0, d1);
+    const int mine = lo >= 1 && hi <= 6 ? roll_start(lo) + hi - lo : -1;
+    const int32_t* mv = minv + (size_t)row * 21;
+    float mean = 0.0f, vmine = 0.0f;
+    for (int r = 0; r < 21; ++r) {
+        const float v = -unord_f32(mv[r]);
+        mean = fmaf(kRoll0[r] == kRoll1[r] ? 1.0f / 36.0f : 2.0f / 36.0f, v, mean);
+        if (r == mine) vmine = v;
+    }
+    luck[i] = mine >= 0 ? vmine - mean : 0.0f;
+    if (mean_out) mean_out[i] = mean;
+}
+
 }  // namespace
 
 static int value_tiles16(int H) { return (H + 15) / 16; }   // 16 hidden units (hi + lo rows) per MFMA tile
@@ -1998,12 +2108,12 @@ struct DeviceFree {
     ~DeviceFree() { if (p) (void)hipFree(p); }
 };
 
-// Stages 3-5 on a non-empty row set: the rows, the plan, the row parts, the pool, the
-// rounds and (tests) the dump.  On return minv holds every job's min.
-static int search_rows(const SearchCall& c, const TwoPlyLayout& L, const OnePlyRows& cand, int rows, int jobs) {
+// Stages 4-5 on a non-empty row set that is built already (build_rows; bgx_roll_luck builds
+// its own): the plan, the row parts, the pool, the rounds and (tests) the dump.  On return
+// minv holds every job's min.
+static int search_rows(const SearchCall& c, const TwoPlyLayout& L, int rows, int jobs) {
     bgx_engine* e = c.e;
-    int rc = build_rows(c, L, cand, rows, jobs);
-    if (rc != BGX_OK) return rc;
+    int rc = BGX_OK;
     EnumPlan plan(c.NT);
     void* ws = e->search_ws.p;
     Ctr* ctr = L.ctr.at(ws);
@@ -2062,7 +2172,8 @@ static int two_ply_search(bgx_engine* e, const float* vpacked, int32_t hidden, f
     L.body((size_t)rows, (size_t)jobs, c.NT, filter != nullptr);
     BGX_CK(e->search_ws.reserve(L.bytes(), 25, c.s, L.head_bytes()));     // the head (lane_off, counters) is live
     if (rows > 0) {
-        rc = search_rows(c, L, cand, rows, jobs);
+        rc = build_rows(c, L, cand, rows, jobs);
+        if (rc == BGX_OK) rc = search_rows(c, L, rows, jobs);
         if (rc != BGX_OK) return rc;
     }
     void* ws = e->search_ws.p;
@@ -2083,7 +2194,65 @@ static int two_ply_search(bgx_engine* e, const float* vpacked, int32_t hidden, f
     return BGX_OK;
 }
 
+// bgx_roll_luck: the 2-ply stages on rows made from the lanes themselves, with the luck form
+// of the pack (k_luck_pack) behind the 2-ply workspace (LuckLayout).
+static int roll_luck(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                     float* luck_out, float* mean_out, uint64_t* stats_host, void* stream) {
+    if (!e || !vpacked || !luck_out || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
+    const int NT = value_tiles16(hidden);
+    hipStream_t s = (hipStream_t)stream;
+    EngineCall call(e, s);
+    BGX_CK(call.err);
+    Args& A = e->a;
+    TwoPlyLayout L((size_t)A.B);
+    BGX_CK(e->search_ws.reserve(L.head_bytes(), 25, s, 0));
+    BGX_CK(hipMemsetAsync(L.ctr.at(e->search_ws.p), 0, 256, s));
+    hipLaunchKernelGGL(k_luck_scan, dim3(1), dim3(1024), 0, s, A, sel, L.lane_off.at(e->search_ws.p),
+                       &L.ctr.at(e->search_ws.p)->rows);
+    BGX_CK_LAUNCH();
+    int64_t rows64 = 0;
+    BGX_CK(hipMemcpyAsync(&rows64, &L.ctr.at(e->search_ws.p)->rows, 8, hipMemcpyDeviceToHost, s));
+    BGX_CK(hipStreamSynchronize(s));
+    const int64_t jobs64 = rows64 * 21;
+    if (jobs64 >= (int64_t)0x1FFFFFFF) return BGX_EINVAL;                 // job ids are 29-bit pool tags
+    if (stats_host) stats_host[0] = stats_host[1] = stats_host[2] = 0;
+    if (rows64 <= 0) return BGX_OK;
+    const int rows = (int)rows64, jobs = (int)jobs64;
+    L.body((size_t)rows, (size_t)jobs, NT, false);
+    const LuckLayout K(L.bytes(), (size_t)sz_f16(NT));
+    BGX_CK(e->search_ws.reserve(K.bytes(), 25, s, L.head_bytes()));      // the head (lane_off, counters) is live
+    void* ws = e->search_ws.p;
+    Ctr* ctr = L.ctr.at(ws);
+    float* lpack = K.pack.at(ws);
+    hipLaunchKernelGGL(k_luck_pack, dim3(64), dim3(256), 0, s, (const uint32_t*)vpacked, NT, (uint32_t*)lpack);
+    BGX_CK(hipMemsetAsync(L.minv.at(ws), 0x7F, (size_t)jobs * 4, s));
+    BGX_CK(hipMemsetAsync(L.maxlen.at(ws), 0xFF, (size_t)jobs, s));
+    hipLaunchKernelGGL(k_luck_rows, dim3((A.B + 3) / 4), dim3(256), 0, s, A, sel, L.lane_off.at(ws), &ctr->rows,
+                       L.row_lane.at(ws), L.rowrec.at(ws), L.rowside.at<uint4>(ws));
+    BGX_CK_LAUNCH();
+    const SearchCall c{e, s, lpack, hidden, NT, -value_bias, sel};
+    const int rc = search_rows(c, L, rows, jobs);
+    if (rc != BGX_OK) return rc;
+    hipLaunchKernelGGL(k_luck_reduce, dim3((A.B + 255) / 256), dim3(256), 0, s, A, sel, L.lane_off.at(ws), &ctr->rows,
+                       L.minv.at(ws), luck_out, mean_out);
+    BGX_CK_LAUNCH();
+    if (stats_host) {
+        unsigned long long lv = 0;
+        BGX_CK(hipMemcpyAsync(&lv, &ctr->leaves, 8, hipMemcpyDeviceToHost, s));
+        BGX_CK(hipStreamSynchronize(s));
+        stats_host[0] = lv;
+        stats_host[1] = (uint64_t)jobs64;
+        stats_host[2] = (uint64_t)rows64;
+    }
+    return BGX_OK;
+}
+
 extern "C" {
+
+int bgx_roll_luck(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                  float* luck_out, float* mean_out, uint64_t* stats_host, void* stream) {
+    return roll_luck(e, vpacked, hidden, value_bias, sel, luck_out, mean_out, stats_host, stream);
+}
 
 int bgx_two_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, int32_t* best_out,
                 float* bestq_out, float* q_out, uint64_t* stats_host, void* stream) {

@@ -129,4 +129,21 @@ private:
     size_t head_, total_;
 };
 
+// bgx_roll_luck's additions to the 2-ply workspace, behind the TwoPlyLayout of the same call
+// (start = its bytes() after body()): the luck form of the value pack, derived per call.
+// The TwoPlyLayout regions keep their offsets; the head stays the part kept over a regrow.
+struct LuckLayout {
+    Region<float> pack;            // [pack_floats] luck form of the bgx_value_pack pack
+    LuckLayout(size_t start, size_t pack_floats) {
+        Carver c(align_up(start));
+        start_ = c.bytes();
+        pack = c.take<float>(pack_floats);
+        total_ = c.bytes();
+    }
+    size_t start() const { return start_; }
+    size_t bytes() const { return total_; }     // end of the whole workspace (2-ply part included)
+private:
+    size_t start_, total_;
+};
+
 }  // namespace bgws
