@@ -1,14 +1,20 @@
 """The fused fp16 output layer + loss head (csrc/bg_ppo_fused.hip: bgx_ppo_rows,
-bgx_ppo_gw2) against the round-2 composition it replaces, on a real rollout:
-hipBLASLt logits y = h W2h^T + b2h, the loss-head kernel bgx_ppo_head_ex (pinned to
-torch autograd by test_gpu_train.py), dh = ReLU'(h) fp16(dy W2h), gW2 = dy^T h,
-gb2 = column sums of dy (ppo_agent.py:268-305 under autocast)."""
+bgx_ppo_gw2): every element against fp64 from the same fp16 operands (the loss head's closed
+form head64 of tests/ppo_head_ref.py, pinned to torch autograd by test_ppo_head_ref_cpu.py),
+on a real rollout and on synthetic rows that reach every clip and clamp case; and against the
+round-2 composition it replaces, on a real rollout: hipBLASLt logits y = h W2h^T + b2h, the
+loss-head kernel bgx_ppo_head_ex (checked element by element against the same closed form by
+test_gpu_ppo_head.py; test_gpu_train.py compares only the parameter gradients behind it with
+torch autograd), dh = ReLU'(h) fp16(dy W2h), gW2 = dy^T h, gb2 = column sums of dy
+(ppo_agent.py:268-305 under autocast)."""
 import ctypes
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+from ppo_head_ref import EPS_CLIP, LOG_EPS, U32, head64, ratio_fields, records_of, ulp16
 
 pytestmark = pytest.mark.gpu
 
@@ -97,106 +103,36 @@ def _rel(a, b):
 
 COEFS = (0.25, 0.5, 0.15, 16.0)      # eps_clip, value coef, entropy coef, per-row gradient scale
 
-U32 = 2.0 ** -24                     # fp32 unit roundoff
-LOG_EPS, LOG_1M_EPS = -15.942384719848633, -1.1920930376163597e-07   # the kernels' fp32 clamp bounds
 
-
-def ulp16(x):
-    """fp16 ulp at |x| (fp64 tensor): 2^(e - 10) in the normal range, 2^-24 below it."""
-    a = x.abs().clamp(min=2.0 ** -14)
-    return torch.exp2(torch.floor(torch.log2(a)) - 10)
-
-
-def _head64(z, recs, acts, old, R, adv, coefs):
-    """The loss head's dL/dy in fp64 from the kernel's own fp16 logits z ([c, 512];
-    ppo_agent.py:276-296 under the masked softmax of :166, the per-row gradient scaled
-    as bgx_ppo_head_ex / k_ppo_rows scale it).  Returns (d64 [c, 512], tol [c, 512],
-    row sums (pol, dv^2, ent) [c, 3]).  tol = the fp32 rounding budget of the kernel's
-    terms; where a log-prob lies on a clamp bound (within the fp32 error of its
-    computation) either side is accepted (`d_alt`)."""
-    eps, cv, ce, gs = coefs
-    gs32, ce32, cv32 = (float(np.float32(v)) for v in (gs, ce, cv))
-    k1 = float(np.float32(gs32) * np.float32(ce32))
-    c = z.shape[0]
+def _head64(z, recs, acts, old, R, adv, coefs, wide=False):
+    """The loss head's dL/dy in fp64 from the kernel's own fp16 logits z ([c, 512]) in the
+    [dlogits | dvalue | 0] layout: head64(drop_masked=True) of tests/ppo_head_ref.py.
+    Returns (d64 [c, 512], d_alt, tol [c, 512], row sums (pol, dv^2, ent) [c, 3]).  tol = the
+    fp32 rounding budget of the kernel's terms; where a log-prob lies on a clamp bound (within
+    the fp32 error of its computation) either side is accepted (`d_alt`)."""
     cnt = recs[:, 60].long() | (recs[:, 61].long() << 8)
-    lim = torch.where(cnt == 0, torch.full_like(cnt, 500), cnt.clamp(max=500))
-    cols = torch.arange(512, device=z.device)[None, :]
-    play = cols < lim[:, None]
-    zz = torch.where(play, z.double(), torch.full_like(z, float("-inf"), dtype=torch.float64))
-    lse = torch.logsumexp(zz, dim=1)
-    u = zz - lse[:, None]
-    p = torch.exp(u)
-    lp = u.clamp(LOG_EPS, LOG_1M_EPS)
-    q = lp + ((lp == u) & play).double()
-    pl = torch.where(play, p, torch.zeros_like(p))
-    ent = -(pl * torch.where(play, lp, torch.zeros_like(lp))).sum(1)
-    entq = -(pl * torch.where(play, q, torch.zeros_like(q))).sum(1)
-    a = acts.long()
-    ua = torch.where(a < lim, u.gather(1, a.clamp(max=511)[:, None])[:, 0], torch.full_like(lse, float("-inf")))
-    la = ua.clamp(LOG_EPS, LOG_1M_EPS)
-    rt = torch.exp(la - old.double())
-    advd = adv.double()
-    s1, s2 = rt * advd, rt.clamp(1 - eps, 1 + eps) * advd
-    pol = -torch.minimum(s1, s2)
-    w1 = torch.where(s1 < s2, 1.0, torch.where(s1 == s2, 0.5, 0.0)).double()
-    w2 = (1 - w1) * ((rt >= 1 - eps) & (rt <= 1 + eps)).double()
-    glp_in = -advd * rt * (w1 + w2)                      # g_lp when the action's log-prob is not clamped
-    ina = (la == ua).double()
-    onehot = (cols == a[:, None]) & play
-    v = z[:, 500].double()
-    dv = v - R.double()
-    gv = gs32 * cv32 * 2.0 * dv
-
-    def dfor(ina_):
-        gla = gs32 * glp_in * ina_
-        k2 = k1 * entq - gla
-        d = pl * (k1 * q + k2[:, None]) + onehot.double() * gla[:, None]
-        d = torch.where(play, d, torch.zeros_like(d))
-        d[:, 500] = gv
-        return d, gla, k2
-
-    d, gla, k2 = dfor(ina)
-    # the action's log-prob within fp32 reach of a clamp bound: the kernel may take either side
-    amb = ((ua - LOG_EPS).abs() < 1e-4) | ((ua - LOG_1M_EPS).abs() < 1e-6)
-    d_alt = torch.where(amb[:, None], dfor(1.0 - ina)[0], d)
-    # fp32 budget: every p from an fp32 log-sum-exp over lim terms, k2 / gla / entq in fp32
-    n = (lim + 16).double()[:, None]
-    tol = n * U32 * (pl * (k1 * q.abs().where(play, torch.zeros_like(q)) + k2.abs()[:, None] + gla.abs()[:, None])
-                     + onehot.double() * gla.abs()[:, None])
-    # a log-prob on a clamp bound: its q may take either side (p k1 apart)
-    on_bound = (((u - LOG_EPS).abs() < 1e-4) | ((u - LOG_1M_EPS).abs() < 1e-6)) & play
-    tol = tol + on_bound.double() * pl * k1
-    tol[:, 500] = 4 * U32 * gv.abs()
-    return d, d_alt, tol, torch.stack([pol, dv * dv, ent], 1)
+    ref = head64(z, z[:, 500], cnt, acts, old, R, adv, coefs, 500, drop_masked=True, wide=wide)
+    c = z.shape[0]
+    d, d_alt, tol = (torch.zeros(c, 512, dtype=torch.float64, device=z.device) for _ in range(3))
+    d[:, :500], d_alt[:, :500], tol[:, :500] = ref.d, ref.d_alt, ref.tol
+    d[:, 500] = d_alt[:, 500] = ref.gv
+    tol[:, 500] = ref.tol_v
+    return d, d_alt, tol, ref.rows
 
 
 CHUNK = 1 << 17
 
 
-def test_fused_head_elementwise_vs_fp64():
-    """bgx_ppo_rows / bgx_ppo_gw2 at 2^21 rows (a 65,536 x 32 rollout, the production
-    launch layout: k_ppo_rows<1/2/4/16> at 2-4 waves per SIMD), every element against
-    an fp64 recompute from the same fp16 operands:
-      * z (the fp16 logits, test output): within one fp16 ulp of fp64 h W2h^T + b2h
-        (+ the fp32 accumulation budget 130 u sum|terms|);
-      * dy: within one fp16 ulp of the loss head's dL/dy evaluated in fp64 on the
-        kernel's own z (+ the fp32 budget of its terms, _head64);
-      * dh: within one fp16 ulp of fp64 (dy W2h) on the kernel's dy (+ 512 u
-        sum|dy||W2h|), exactly 0 where h <= 0;
-      * gW2 / gb2 (k_ppo_gw2, dz recomputed from the row statistics): every element within
-        (1024 + 2048 + 64) u sum_rows |dy||h| of fp64 dy^T [h | 1] -- the kernel's
-        summation chain (1,024-row tasks, fixed-order partial sums) -- and every action
-        column's (= k_ppo_gw2 lane's) relative error below 1e-5;
-      * the loss sums within 1e-6 relative of their fp64 recompute.
-    Round 4's evaluator fault (0.01-0.8 % of items wrong by up to 5 %, confined to 16
-    lanes) fails every one of these."""
-    from bgx.train import ppo_row_plan
-    args = _setup(batch=65536, horizon=32)
+def _check_fused_vs_fp64(args, coefs, out, wide=False):
+    """Every output of bgx_ppo_rows / bgx_ppo_gw2 (`out` = _fused(..., want_z=True)) against
+    an fp64 recompute from the same fp16 operands, in chunks of CHUNK rows: z, dy on the
+    kernel's own z, dh on the kernel's dy, gW2 / gb2 against fp64 dy^T [h | 1], the loss sums,
+    exact zeros on masked columns (the bounds are those of test_fused_head_elementwise_vs_fp64's
+    docstring; `wide`: the loss head's budget follows the fp32 resolution of each row's
+    log-probs, ppo_head_ref.head64).  Returns the worst error / tolerance per quantity."""
     recs, acts, old, R, adv, W2h, b2h, h = args
+    dh, dy, gw2, gb2, sums, z = out
     m = recs.shape[0]
-    assert m == 1 << 21
-    perm, plan, row_plan = ppo_row_plan(recs)
-    dh, dy, gw2, gb2, sums, z = _fused(*args, COEFS, perm, plan, row_plan, want_z=True)
     W = W2h.double()
     sums64 = torch.zeros(3, dtype=torch.float64, device="cuda")
     worst = {}
@@ -221,7 +157,7 @@ def test_fused_head_elementwise_vs_fp64():
         note("z", ez[need], zt[need])
         assert bool((ez <= zt).all()), float((ez / zt).max())
         # dy on the kernel's z
-        d64, dalt, dt, rs = _head64(zc, recs[sl], acts[sl], old[sl], R[sl], adv[sl], COEFS)
+        d64, dalt, dt, rs = _head64(zc, recs[sl], acts[sl], old[sl], R[sl], adv[sl], coefs, wide)
         sums64 += rs.sum(0)
         tol = ulp16(d64) + dt
         e = torch.minimum((dyc.double() - d64).abs(), (dyc.double() - dalt).abs())
@@ -254,13 +190,144 @@ def test_fused_head_elementwise_vs_fp64():
     assert bool((gw2[~live] == 0).all())
     # the loss sums (fp32 per lane, fp64 across lanes) against the fp64 per-row recompute
     assert torch.allclose(sums, sums64, rtol=1e-6, atol=1e-6 * m), (sums, sums64)
-    print("worst error / tolerance:", {k: round(v, 4) for k, v in worst.items()})
     # masked columns (past the legal count of a row with legal moves) get exactly 0
     cnt = recs[:, 60].int() | (recs[:, 61].int() << 8)
     cols = torch.arange(500, device="cuda")[None, :]
     masked = (cols >= cnt[:, None]) & (cnt[:, None] > 0)
     assert bool((dy[:, :500][masked] == 0).all())
     assert bool((dy[:, 501:] == 0).all())
+    return worst
+
+
+def test_fused_head_elementwise_vs_fp64():
+    """bgx_ppo_rows / bgx_ppo_gw2 at 2^21 rows (a 65,536 x 32 rollout, the production
+    launch layout: k_ppo_rows<1/2/4/16> at 2-4 waves per SIMD), every element against
+    an fp64 recompute from the same fp16 operands:
+      * z (the fp16 logits, test output): within one fp16 ulp of fp64 h W2h^T + b2h
+        (+ the fp32 accumulation budget 130 u sum|terms|);
+      * dy: within one fp16 ulp of the loss head's dL/dy evaluated in fp64 on the
+        kernel's own z (+ the fp32 budget of its terms, _head64);
+      * dh: within one fp16 ulp of fp64 (dy W2h) on the kernel's dy (+ 512 u
+        sum|dy||W2h|), exactly 0 where h <= 0;
+      * gW2 / gb2 (k_ppo_gw2, dz recomputed from the row statistics): every element within
+        (1024 + 2048 + 64) u sum_rows |dy||h| of fp64 dy^T [h | 1] -- the kernel's
+        summation chain (1,024-row tasks, fixed-order partial sums) -- and every action
+        column's (= k_ppo_gw2 lane's) relative error below 1e-5;
+      * the loss sums within 1e-6 relative of their fp64 recompute.
+    Round 4's evaluator fault (0.01-0.8 % of items wrong by up to 5 %, confined to 16
+    lanes) fails every one of these."""
+    from bgx.train import ppo_row_plan
+    args = _setup(batch=65536, horizon=32)
+    recs = args[0]
+    m = recs.shape[0]
+    assert m == 1 << 21
+    perm, plan, row_plan = ppo_row_plan(recs)
+    out = _fused(*args, COEFS, perm, plan, row_plan, want_z=True)
+    worst = _check_fused_vs_fp64(args, COEFS, out)
+    print("worst error / tolerance:", {k: round(v, 4) for k, v in worst.items()})
+
+
+SYN_COUNTS = (0, 1, 31, 32, 33, 64, 65, 128, 129, 499, 500, 600)   # every row-plan class and its edges
+SYN_LOW_COL = 3
+
+
+def _synthetic(m=4099, seed=11):
+    """Epoch 2-4 rows for the fused head, which takes h and W2h, not logits:
+      * h = relu(randn) * {0.8, 1.25} per row (fp16), W2h ~ N(0, 0.12^2), b2h ~ N(0, 0.5^2):
+        logits of std ~ 0.8-1.2, the most the shortcut's own precondition leaves room for
+        beside one bias of -13 (column SYN_LOW_COL), which makes that column's probability
+        fall below eps wherever more than a few columns are legal;
+      * legal counts from SYN_COUNTS; the action is the row's least likely legal one on a
+        quarter of the rows, the most likely on a quarter, uniform on the rest; an eighth of
+        the rows with 0 < cnt < 500 take a masked action cnt <= act < 500 instead;
+      * advantage and ratio target per row as ppo_head_ref.synthetic_rows; old_logp =
+        fp32(la64 - log target) with la64 from the fp64 logits of the fp16 operands.
+    Returns (args for _fused, pick [m]: 0 least likely, 1 most likely, 2-3 uniform, 4 masked)."""
+    g = torch.Generator().manual_seed(seed)
+    scale = torch.tensor([0.8, 1.25])[torch.randint(0, 2, (m,), generator=g)]
+    h = (torch.relu(torch.randn(m, 128, generator=g)) * scale[:, None]).half()
+    W2h = torch.zeros(512, 128)
+    W2h[:501] = torch.randn(501, 128, generator=g) * 0.12
+    b2h = torch.zeros(512)
+    b2h[:501] = torch.randn(501, generator=g) * 0.5
+    b2h[SYN_LOW_COL] = -13.0
+    W2h, b2h = W2h.half(), b2h.half()
+    cnt = torch.tensor(SYN_COUNTS)[torch.randint(0, len(SYN_COUNTS), (m,), generator=g)]
+    lim = torch.where(cnt == 0, torch.tensor(500), cnt.clamp(max=500))
+    z64 = h.double() @ W2h.double().t() + b2h.double()
+    zl = torch.where(torch.arange(512)[None] < lim[:, None], z64, torch.full_like(z64, float("nan")))
+    pick = torch.randint(0, 4, (m,), generator=g)
+    act = (torch.rand(m, generator=g) * lim).long().clamp(max=499)
+    act = torch.where(pick == 0, torch.nan_to_num(zl, nan=float("inf")).argmin(1), act)
+    act = torch.where(pick == 1, torch.nan_to_num(zl, nan=float("-inf")).argmax(1), act)
+    msk = (torch.randint(0, 8, (m,), generator=g) == 0) & (cnt > 0) & (cnt < 500)
+    mact = (cnt + ((500 - cnt).double() * torch.rand(m, generator=g).double()).long()).clamp(max=499)
+    act = torch.where(msk, mact, act)
+    pick = torch.where(msk, torch.full_like(pick, 4), pick)
+    R = torch.randn(m, generator=g)
+    adv, tgt = ratio_fields(m, g)
+    la = head64(z64, z64[:, 500], cnt, act, torch.zeros(m), R, adv, COEFS, 500, drop_masked=True).la
+    old = (la - tgt.log()).float()
+    args = (records_of(cnt), act.to(torch.int32), old, R, adv, W2h, b2h, h)
+    return tuple(t.cuda().contiguous() for t in args), pick.cuda()
+
+
+@pytest.mark.parametrize("order", ["plan", "shuffled"])
+def test_fused_head_synthetic_rows_vs_fp64(order):
+    """bgx_ppo_rows + bgx_ppo_gw2 at m = 4099 on rows as epochs 2-4 of an update see them
+    (_synthetic), every element against fp64 as in test_fused_head_elementwise_vs_fp64:
+      * ratio targets 0.5 / 2.0 with either sign of the advantage run the clipped branches
+        (w1, w2) and put clipped rows into the statistics k_ppo_gw2 rebuilds dy from; 0.9 / 1.1
+        the inside branch; 1.0 and advantage 0 the tie s1 == s2;
+      * least likely actions: the lower clamp on the action (la = log eps, no policy gradient);
+        most likely actions with cnt = 1: the upper clamp;
+      * masked actions (cnt <= act < 500, cnt > 0), in a computed tile, in a skipped tile and in
+        the value tile: la = log eps, zero policy gradient, no one-hot term, as head64 defines;
+      * counts 0 / 1 / 31..33 / 64, 65 / 128, 129 / 499, 500, 600: every k_ppo_rows variant and
+        the edges of its tile count; m = 4099 leaves a partial last row tile.
+    `plan`: ppo_row_plan's order and plan; `shuffled`: a random order with the plan for it
+    (every row tile through the 16-tile variant, every action tile visiting every row), which
+    the header allows.  Measured on the MI355X, worst error / tolerance, either order: z 0.49,
+    dy 0.50 (the fp16 rounding: no clamp decided the other way), dh 0.48, gW2 0.005, its
+    columns' relative error within the 1e-5 bound.  No kernel fault found: a masked chosen
+    action already follows head64."""
+    from bgx.ppo_epoch import MASK_SHORTCUT_LIMIT
+    from bgx.train import ppo_row_plan
+    args, pick = _synthetic()
+    recs, acts, old, R, adv, W2h, b2h, h = args
+    m = recs.shape[0]
+    # the shortcut's own precondition (bgx.ppo_epoch._ppo_epoch_amp_fused's guard)
+    U = W2h[:500].float().norm(dim=1).max() * h.float().norm(dim=1).max() + b2h[:500].float().abs().max()
+    assert 2.0 * float(U) < MASK_SHORTCUT_LIMIT, float(U)
+    if order == "plan":
+        perm, plan, row_plan = ppo_row_plan(recs)
+    else:
+        g = torch.Generator().manual_seed(5)
+        perm = torch.randperm(m, generator=g).to(torch.int32).cuda()
+        ntiles = (m + 31) // 32
+        tasks = (ntiles + 31) // 32
+        plan = torch.tensor([tasks * i for i in range(17)] + [0] * 16, dtype=torch.int32, device="cuda")
+        row_plan = torch.tensor([0, 0, 0, 0, 0, 0, 0, ntiles], dtype=torch.int32, device="cuda")
+    out = _fused(*args, COEFS, perm, plan, row_plan, want_z=True)
+    dy, z = out[1], out[5]
+    # the branches, from the reference on the kernel's own logits
+    cnt = recs[:, 60].long() | (recs[:, 61].long() << 8)
+    ref = head64(z, z[:, 500], cnt, acts, old, R, adv, COEFS, 500, drop_masked=True)
+    assert not bool(ref.near_clip.any())
+    rcls = torch.where(ref.rt < 1 - EPS_CLIP, 0, torch.where(ref.rt > 1 + EPS_CLIP, 2, 1))
+    cells = torch.bincount(rcls * 3 + torch.sign(adv).long() + 1, minlength=9)
+    assert int(cells.min()) >= 20, cells
+    legal = acts.long() < ref.lim
+    assert int(((pick == 0) & legal & (ref.ua < LOG_EPS)).sum()) >= 20
+    assert int((ref.ua > -1.1920930376163597e-07).sum()) >= 20
+    masked_act = ~legal
+    assert int(masked_act.sum()) >= 20 and bool((pick[masked_act] == 4).all())
+    worst = _check_fused_vs_fp64(args, COEFS, out, wide=True)
+    print("worst error / tolerance:", {k: round(v, 4) for k, v in worst.items()})
+    # a masked chosen action: no one-hot term (its column is exactly 0), la = log eps in the ratio
+    rows = torch.nonzero(masked_act)[:, 0]
+    assert bool((dy[rows, acts[rows].long()] == 0).all())
+    assert bool((ref.la[masked_act] == LOG_EPS).all())
 
 
 def test_fused_head_matches_round2_composition():
