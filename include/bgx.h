@@ -458,6 +458,94 @@ int bgx_rollout_luck_flush(const uint8_t* starts_dev, const int32_t* group_dev, 
                            const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
                            float* lane_luck_dev, int64_t* luck_tally_dev, void* stream);
 
+/* ---- exact two-sided bearoff database (csrc/bg_bearoff.h; bgx/bearoff.py; no
+ * counterpart in the reference) ----
+ * Once both sides have at most K checkers left, all on their own home points, the cubeless game
+ * is a race between two independent six-point configurations and its value under perfect play
+ * is a finite dynamic program.  A configuration is the six counts c[d-1], d = 1..6 = checkers
+ * at distance d from bearing off (PLAYER1: point 24 - d, PLAYER2: point d - 1), sum <= K;
+ * there are n = C(K + 6, 6) of them, ordered by (pip count sum_d d c[d-1], then the base-9
+ * number sum_d c[d-1] 9^(d-1)) ascending: index 0 is the empty one and every pip count is a
+ * contiguous range.  bgx_bearoff_buffers publishes the order, so no caller needs the formula:
+ *   configs  int8[n][6]      the counts of configuration i
+ *   succ_off int32[n*21+1], succ int32[]   for configuration a and roll r (bgx_two_ply's roll
+ *            order), succ[succ_off[21 a + r] .. succ_off[21 a + r + 1]) = the distinct
+ *            configurations a legal play of r reaches, ascending (both dice when possible, the
+ *            reference's move generator restricted to a bearoff board: the opponent neither
+ *            blocks nor is hit); a roll that cannot be played gives a itself
+ *   table    float[n][n]     W[a][b] = the probability that the side ON ROLL with a wins
+ *            against b when both sides maximise their win probability:
+ *              W[a][empty] = 0,  W[empty][b] = 1 (b not empty),  otherwise
+ *              w_r = max over a' in succ(a, r) of (a' empty ? 1 : 1 - W[b][a'])
+ *              W[a][b] = sum over r = 0..20, in that order from 0.0f, of p_r * w_r,
+ *            p_r = fp32(1/36) for doubles and fp32(2/36) otherwise, every subtraction, product
+ *            and sum rounded to fp32 once (no fma): the value does not depend on the schedule
+ *            or on K, and a numpy float32 loop reproduces it bit for bit.
+ * Equity in points is 2 W - 1: with K <= 8 both sides have checkers off, so a game is single.
+ * bgx_bearoff_create: 1 <= max_checkers <= 8 (else BGX_EINVAL); allocates and builds on
+ * `stream` (successor sets: count, scan, fill; then one launch per total pip count) and
+ * synchronises it (it sizes succ from the count pass); BGX_EOVERFLOW if a successor set
+ * outgrew its room (none does for K <= 8).  bgx_bearoff_destroy synchronises the device. */
+typedef struct bgx_bearoff bgx_bearoff;
+typedef struct {
+    const float* table;
+    const int8_t* configs;
+    const int32_t* succ_off;   /* [n*21+1] */
+    const int32_t* succ;
+    int32_t n, max_checkers;
+} bgx_bearoff_buffers;
+int bgx_bearoff_create(int device, int32_t max_checkers, void* stream, bgx_bearoff** out);
+int bgx_bearoff_buffers_get(bgx_bearoff* db, bgx_bearoff_buffers* out);
+int bgx_bearoff_destroy(bgx_bearoff* db);
+
+/* One thread per 64-byte lane record (records_dev 16-byte aligned), on the caller's stream as
+ * given, like bgx_policy_act.  A record is in the table when game_over (byte 55) is 0, both
+ * bars are empty, each side has between 1 and K checkers on the board, all of them on its own
+ * six home points, and points + off == 15 for both sides.  Then in_db_out[i] = 1 and
+ * win_out[i] = W[cfg(mover)][cfg(opponent)], the mover's exact win probability before its
+ * roll (the roll bytes are not read); else in_db_out[i] = 0 and win_out[i] is not written.
+ * win_out may be NULL.  No allocation, no synchronisation: graph-capturable. */
+int bgx_bearoff_lookup(const bgx_bearoff* db, const uint8_t* records_dev, int32_t n, uint8_t* in_db_out,
+                       float* win_out, void* stream);
+
+/* Perfect play on the engine's lanes; ordered like every engine call.  For each lane with
+ * lane_sel_dev[i] != 0 (NULL = every lane) whose record is in the table and which has a legal
+ * move: every move of the engine's list (bgx_buffers.moves, count in bytes 60-61) gives the
+ * mover's afterstate configuration a' from its sub-moves (start point minus one, end point
+ * plus one unless BEAR_OFF), and act_inout[i] = the first argmax of
+ * (a' empty ? 1 : 1 - W[cfg(opponent)][a']).  Other lanes' entries are not written.
+ * in_db_out (uint8[B], may be NULL) receives the table test of the selected lanes and 0 for
+ * the others.  No allocation, no synchronisation: graph-capturable.  BGX_EINVAL when the
+ * database lives on another device than the engine. */
+int bgx_bearoff_act(bgx_engine* e, const bgx_bearoff* db, const uint8_t* lane_sel_dev, int32_t* act_inout,
+                    uint8_t* in_db_out, void* stream);
+
+/* Rollout cut: a game that reaches the table is stopped and scored with its exact win
+ * probability.  Beside the state of bgx_rollout_begin / bgx_rollout_advance: cut_tally
+ * int64[n_groups][4] (bgx_rollout_cut_field), zeroed by the caller, and reset_mask_out
+ * uint8[n].  Call it once after bgx_rollout_begin and after every bgx_rollout_advance.  A lane
+ * with sel[i] != 0, a valid group and a record in the table (bgx_bearoff_lookup's test):
+ *   q = W when the record's mover (byte 52) is the start record's mover, else 1 - W (fp32);
+ *   Pq = llrintf(q * 1048576.0f) clamped to [0, 2^20];
+ *   row group[i]: CUT_GAMES += 1, CUT_PLIES += plies[i], CUT_P += Pq, CUT_P2 += Pq * Pq;
+ *   games_done[i] += 1, plies[i] = 0; the lane's last game: sel[i] = 0 and active drops;
+ *   reset_mask_out[i] = 1.
+ * Every other lane gets reset_mask_out[i] = 0.  The caller then runs bgx_reset with that mask,
+ * which gives each cut lane its start record again.  The sums are integers: run-to-run
+ * identical; Pq^2 <= 2^40, so a row holds 2^23 cut games.  No allocation, no synchronisation:
+ * graph-capturable.  BGX_EINVAL for n <= 0, n_groups <= 0, games_per_lane < 0, a NULL pointer
+ * or records that are not 16-byte aligned. */
+enum bgx_rollout_cut_field {
+    BGX_ROLLOUT_CUT_GAMES = 0,    /* cut games */
+    BGX_ROLLOUT_CUT_PLIES = 1,    /* their steps */
+    BGX_ROLLOUT_CUT_P = 2,        /* sum of Pq (2^-20) */
+    BGX_ROLLOUT_CUT_P2 = 3        /* sum of Pq^2 (2^-40) */
+};
+int bgx_rollout_bearoff_cut(const bgx_bearoff* db, const uint8_t* records_dev, const uint8_t* starts_dev,
+                            const int32_t* group_dev, int32_t n, int32_t n_groups, int32_t games_per_lane,
+                            int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev, int64_t* cut_tally_dev,
+                            int64_t* active_dev, uint8_t* reset_mask_out, void* stream);
+
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row
  * stride ld_logits; mask from the legal count in bytes 60-61 of each 64-byte

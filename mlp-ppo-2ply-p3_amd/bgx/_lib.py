@@ -68,6 +68,12 @@ SIGNATURES = {
     "bgx_rollout_advance": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P]),
     "bgx_rollout_luck_add": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P]),
     "bgx_rollout_luck_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "bgx_bearoff_create": (ctypes.c_int, [ctypes.c_int, _I32, _P, ctypes.POINTER(_P)]),
+    "bgx_bearoff_buffers_get": (ctypes.c_int, [_P, _P]),
+    "bgx_bearoff_destroy": (ctypes.c_int, [_P]),
+    "bgx_bearoff_lookup": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P]),
+    "bgx_bearoff_act": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "bgx_rollout_bearoff_cut": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),
@@ -149,6 +155,10 @@ MAX_COPY_REGIONS = 8           # include/bgx.h BGX_MAX_COPY_REGIONS
 
 class BgxBuffers(ctypes.Structure):
     _fields_ = [("lanes", _P), ("moves", _P), ("n_total", _P), ("batch", _I32), ("max_moves", _I32)]
+
+
+class BgxBearoffBuffers(ctypes.Structure):
+    _fields_ = [("table", _P), ("configs", _P), ("succ_off", _P), ("succ", _P), ("n", _I32), ("max_checkers", _I32)]
 
 
 _lib = None

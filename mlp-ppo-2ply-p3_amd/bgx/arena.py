@@ -280,6 +280,10 @@ class _Parser(argparse.ArgumentParser):
                 self.error(f"--top-k-{side} must be >= 1")
             if margin is not None and not margin >= 0:
                 self.error(f"--margin-{side} must be >= 0")
+        for side in "ab":
+            k = getattr(ns, f"bearoff_{side}")
+            if k is not None and not 1 <= k <= 8:
+                self.error(f"--bearoff-{side} takes a number of checkers in 1..8")
         return ns
 
 
@@ -300,6 +304,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help=f"player {side.upper()} (2ply only): search only its top-k 1-ply moves")
         ap.add_argument(f"--margin-{side}", type=float, default=None,
                         help=f"player {side.upper()} (2ply only): ... within this 1-ply value of its best move")
+        ap.add_argument(f"--bearoff-{side}", type=int, default=None, metavar="K",
+                        help=f"player {side.upper()} moves perfectly where the position is in the exact bearoff "
+                             "table for K checkers a side (1..8; bgx/bearoff.py)")
     return ap
 
 
@@ -312,7 +319,12 @@ def main(argv=None):
     players = [make_player(k, n, seed=args.seed * 2 + 1 + i, top_k=tk, margin=mg)
                for i, (k, n, tk, mg) in enumerate(zip((args.player_a, args.player_b), nets,
                                                       (args.top_k_a, args.top_k_b), (args.margin_a, args.margin_b)))]
-    arena = Arena(args.batch, args.games_per_lane, seed=args.seed, dice=args.dice, max_moves=max_moves, device=dev)
+    if args.bearoff_a is not None or args.bearoff_b is not None:
+        from .bearoff import BearoffDB, BearoffPlayer
+        dbs = {k: BearoffDB(k, device=dev) for k in {args.bearoff_a, args.bearoff_b} - {None}}
+        players = [p if k is None else BearoffPlayer(p, dbs[k])
+                   for p, k in zip(players, (args.bearoff_a, args.bearoff_b))]
+    arena =Arena(args.batch, args.games_per_lane, seed=args.seed, dice=args.dice, max_moves=max_moves, device=dev)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     res = arena.play(players[0], players[1], max_steps=args.max_steps)
@@ -321,6 +333,7 @@ def main(argv=None):
                player_b="random" if nets[1] is None else args.player_b, batch=args.batch,
                games_per_lane=args.games_per_lane, max_steps=args.max_steps, seed=args.seed, seconds=dt,
                top_k_a=args.top_k_a, top_k_b=args.top_k_b, margin_a=args.margin_a, margin_b=args.margin_b,
+               bearoff_a=args.bearoff_a, bearoff_b=args.bearoff_b,
                games_per_s=res["games"] / dt if dt > 0 else 0.0,
                env_steps_per_s=res["steps"] * args.batch / dt if dt > 0 else 0.0)
     print(json.dumps(res), flush=True)

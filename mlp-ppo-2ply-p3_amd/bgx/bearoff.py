@@ -1,0 +1,205 @@
+"""Exact two-sided bearoff database (the device side is csrc/bg_bearoff.h behind
+bgx_bearoff_* of include/bgx.h).  Once both sides have at most K checkers left, all in their
+home boards, the cubeless game is a race between two independent six-point configurations, and
+W[a][b] -- the probability that the side on roll with configuration a wins against b under
+perfect play -- is a finite dynamic program.  The table gives
+
+  * the true value of endgame positions (BearoffDB.lookup; equity in points = 2 W - 1),
+  * a perfect endgame player (BearoffPlayer: one table read per legal move),
+  * an exact truncation for rollouts (Rollout.run(..., bearoff=db), bgx/rollout.py).
+
+A configuration is the six counts c[d-1], d = 1..6, of checkers at distance d from bearing off
+(PLAYER1: point 24 - d; PLAYER2: point d - 1).  BearoffDB.configs() publishes the index order.
+"""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from .engine import R_CUR, R_OVER, _ptr, _stream
+
+MAX_CHECKERS = 8
+# the 21 rolls in bgx_two_ply's order and their probabilities as the table's build adds them
+ROLLS21 = [(a, b) for a in range(1, 7) for b in range(a, 7)]
+ROLL_P = np.array([1.0 / 36.0 if a == b else 2.0 / 36.0 for a, b in ROLLS21], np.float32)
+
+
+class BearoffDB:
+    """The table for at most `max_checkers` (1..8) checkers a side, built on `device` on the
+    current stream; n = C(max_checkers + 6, 6) configurations (924 at the default 6)."""
+
+    def __init__(self, max_checkers: int = 6, device=None):
+        K = int(max_checkers)
+        if not 1 <= K <= MAX_CHECKERS:
+            raise ValueError(f"BearoffDB: max_checkers must be in 1..{MAX_CHECKERS}, got {max_checkers}")
+        self._lib = _lib.load()
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise ValueError("BearoffDB needs a GPU device (HIP); there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        h = ctypes.c_void_p()
+        check(self._lib.bgx_bearoff_create(dev.index, K, _stream(dev), ctypes.byref(h)), "bgx_bearoff_create")
+        self._h = h
+        b = _lib.BgxBearoffBuffers()
+        check(self._lib.bgx_bearoff_buffers_get(h, ctypes.byref(b)), "bgx_bearoff_buffers_get")
+        self.n, self.K = int(b.n), int(b.max_checkers)
+        # copies of the small tables; the big one stays where it is (table())
+        m = self.n * 21
+        self._succ_off = self._view(b.succ_off, (m + 1,), torch.int32).cpu().numpy()
+        self._succ = self._view(b.succ, (int(self._succ_off[-1]),), torch.int32).cpu().numpy()
+        self._configs = self._view(b.configs, (self.n, 6), torch.int8)
+        self._table = self._view(b.table, (self.n, self.n), torch.float32)
+        self._index = {tuple(int(v) for v in c): i for i, c in enumerate(self._configs.cpu().numpy())}
+
+    def _view(self, ptr, shape, dtype):
+        """A tensor over the database's own device memory (alive as long as this object)."""
+        n = int(np.prod(shape))
+        size = n * torch.empty(0, dtype=dtype).element_size()
+        iface = {"shape": (size,), "typestr": "|u1", "data": (int(ptr), False), "version": 3, "strides": None}
+        holder = type("_DevMem", (), {"__cuda_array_interface__": iface, "_owner": self})()
+        t = torch.as_tensor(holder, device=self.device)
+        return t.view(dtype).view(*shape)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self._lib.bgx_bearoff_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def handle(self):
+        return self._h
+
+    def table(self) -> torch.Tensor:
+        """W as an [n, n] fp32 tensor view of the database's memory (do not write to it)."""
+        return self._table
+
+    def configs(self) -> torch.Tensor:
+        """The index order: [n, 6] int8, row i = the counts of configuration i at distances 1..6."""
+        return self._configs
+
+    def successors(self, idx: int) -> list:
+        """The 21 sorted lists (one per roll, ROLLS21's order) of the configurations that
+        configuration `idx` reaches with a legal play of the roll."""
+        i = int(idx)
+        if not 0 <= i < self.n:
+            raise IndexError(f"successors: configuration index {idx} not in [0, {self.n})")
+        off = self._succ_off[21 * i:21 * i + 22]
+        return [self._succ[off[r]:off[r + 1]].tolist() for r in range(21)]
+
+    def index_of(self, config) -> int:
+        """The index of a configuration given as its six counts (a host convenience)."""
+        key = tuple(int(v) for v in config)
+        if len(key) != 6 or key not in self._index:
+            raise ValueError(f"index_of: {config!r} is not six counts with a sum of at most {self.K}")
+        return self._index[key]
+
+    def lookup(self, records: torch.Tensor, out=None):
+        """(in_db uint8[n], win f32[n]) for uint8 [n, 64] lane records on the database's device:
+        in_db = the record is in the table (bgx_bearoff_lookup's test), win = the mover's exact
+        win probability before its roll -- written only where in_db is 1; the other entries
+        keep what `out` = (in_db, win) held (NaN without `out`)."""
+        r = records
+        if r.dim() != 2 or r.shape[1] != 64 or r.dtype != torch.uint8 or r.device != self.device:
+            raise ValueError(f"lookup: records must be uint8 [n, 64] on {self.device}, got {r.dtype} "
+                             f"{tuple(r.shape)} on {r.device}")
+        r = r.contiguous()
+        n = r.shape[0]
+        if out is None:
+            out = (torch.empty(n, dtype=torch.uint8, device=self.device),
+                   torch.full((n,), float("nan"), dtype=torch.float32, device=self.device))
+        in_db, win = out
+        check(self._lib.bgx_bearoff_lookup(self._h, _ptr(r), n, _ptr(in_db), _ptr(win), _stream(self.device)),
+              "bgx_bearoff_lookup")
+        return in_db, win
+
+    def act(self, eng, sel, act: torch.Tensor, in_db=None):
+        """bgx_bearoff_act: act[i] = the perfect move of every lane with sel[i] != 0 (None:
+        every lane) whose record is in the table; the other entries stay."""
+        check(self._lib.bgx_bearoff_act(eng._h, self._h, _ptr(sel), _ptr(act), _ptr(in_db), _stream(eng.device)),
+              "bgx_bearoff_act")
+        return act
+
+
+class BearoffPlayer:
+    """An arena player: the table's perfect move where the position is in the table, `inner`'s
+    move elsewhere.  `inner` acts on sel & ~in_db only, so a 2-ply player does no search where
+    the answer is known."""
+
+    def __init__(self, inner, db: BearoffDB):
+        self.inner, self.db = inner, db
+        self.sync_free = bool(getattr(inner, "sync_free", False))
+        self.buf = None
+
+    def act(self, eng, sel, step):
+        B, dev = eng.batch, eng.device
+        if self.buf is None or self.buf[0].numel() != B or self.buf[0].device != dev:
+            self.buf = (torch.empty(B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev),
+                        torch.empty(B, dtype=torch.int32, device=dev))
+        in_db, rest, act = self.buf
+        check(self.db._lib.bgx_bearoff_lookup(self.db._h, ctypes.c_void_p(eng.lanes_ptr()), B, _ptr(in_db), None,
+                                              _stream(dev)), "bgx_bearoff_lookup")
+        torch.logical_and(sel != 0, in_db == 0, out=rest.view(torch.bool))
+        act.copy_(self.inner.act(eng, rest, step))
+        return self.db.act(eng, sel, act)
+
+
+# ------------------------------------------------------------- host references --
+def lookup_reference(records, configs, table, max_checkers: int):
+    """bgx_bearoff_lookup on the host: (in_db bool[n], win f32[n], NaN where not in the table)
+    for uint8 [n, 64] records, with `configs` int8[n_cfg, 6] and `table` f32[n_cfg, n_cfg] as
+    BearoffDB publishes them."""
+    r = np.asarray(records).astype(np.int64)
+    configs, table, K = np.asarray(configs), np.asarray(table, np.float32), int(max_checkers)
+    index = {tuple(int(v) for v in c): i for i, c in enumerate(configs)}
+    c0, c1 = r[:, 23:17:-1], r[:, 24:30]                      # distances 1..6 of PLAYER1 / PLAYER2
+    h0, h1 = c0.sum(1), c1.sum(1)
+    in_db = ((r[:, R_OVER] == 0) & (r[:, 48] == 0) & (r[:, 49] == 0) & (r[:, 0:18].sum(1) == 0) &
+             (r[:, 30:48].sum(1) == 0) & (h0 >= 1) & (h0 <= K) & (h1 >= 1) & (h1 <= K) &
+             (h0 + r[:, 50] == 15) & (h1 + r[:, 51] == 15))
+    win = np.full(r.shape[0], np.nan, np.float32)
+    for i in np.nonzero(in_db)[0]:
+        idx = (index[tuple(c0[i])], index[tuple(c1[i])])
+        m = int(r[i, R_CUR]) & 1
+        win[i] = table[idx[m], idx[1 - m]]
+    return in_db, win
+
+
+def table_reference(succ, n: int, dtype=np.float32) -> np.ndarray:
+    """W[n, n] on the host from successor sets given as index lists, succ[a][r] for
+    configuration a and roll r (index 0 = the empty configuration; every play leads to a
+    smaller index, as any order by pip count ensures), by the recurrence of include/bgx.h with
+    every subtraction, product and sum rounded to `dtype` once, the rolls in order from 0:
+    np.float32 gives the device table's bits, np.float64 a reference for its rounding error."""
+    f = dtype
+    W = np.zeros((n, n), f)
+    W[0, 1:] = f(1)
+    p = ROLL_P.astype(f) if f is np.float32 else np.array([1 / 36 if a == b else 2 / 36 for a, b in ROLLS21], f)
+    flat = [[np.asarray(s, np.int64) for s in succ[a]] for a in range(n)]
+    # a level function that falls along every play, like the pip count: the longest chain of
+    # plays to the empty configuration.  W[a][b] needs W[b][a'] of a smaller level sum only.
+    depth = np.zeros(n, np.int64)
+    for a in range(1, n):
+        depth[a] = 1 + max(depth[int(x)] for s in flat[a] for x in s)
+    by_depth = [np.nonzero(depth == d)[0] for d in range(int(depth.max()) + 1)]
+    for t in range(2, 2 * len(by_depth) - 1):
+        for a in range(1, n):
+            db = t - int(depth[a])
+            if not 1 <= db < len(by_depth):
+                continue
+            bs = by_depth[db]                               # every b of this level at once
+            acc = np.zeros(len(bs), f)
+            for r in range(21):
+                s = flat[a][r]
+                v = np.where(s == 0, f(1), f(1) - W[np.ix_(bs, s)]).astype(f).max(axis=1)
+                acc = (acc + (p[r] * v).astype(f)).astype(f)
+            W[a, bs] = acc
+    return W

@@ -11,7 +11,9 @@ Every lane holds one position as its start record: the engine's auto-reset refil
 with it in the step that ends a game, so no lane waits for the longest game of a wave.  One
 player acts for both sides.  Equity is in points (1 / 2 / 3 per game, cubeless) from the
 side of the position's mover.  --luck: the luck-adjusted (variance-reduced) estimate beside the
-raw one (summarize_luck; DESIGN.md "Luck adjustment").
+raw one (summarize_luck; DESIGN.md "Luck adjustment").  --bearoff K: a game that reaches the exact
+bearoff table (bgx/bearoff.py) stops there and is scored with its exact win probability
+(summarize_bearoff).
 """
 from __future__ import annotations
 
@@ -36,6 +38,9 @@ LUCK_ONE = 65536                    # Lq = rint(L * LUCK_ONE)
 LUCK_CLAMP = 1 << 21                # |Lq| <= LUCK_CLAMP
 ROLLS36 = [(a, b) for a in range(1, 7) for b in range(1, 7)]       # the 36 ordered rolls
 FIRST_ROLLS = ("stratified", "random")
+# cut_tally int64[n_groups][4] (include/bgx.h bgx_rollout_cut_field): fixed point, 2^-20
+CUT_FIELDS = ("cut_games", "cut_plies", "cut_p", "cut_p2")
+CUT_ONE = 1 << 20                   # Pq = rint(q * CUT_ONE), q the start mover's exact win probability
 
 
 def summarize(tally_row, unfinished: int = 0) -> dict:
@@ -147,6 +152,97 @@ def luck_tally_reference(luck, mover, done, info, starts, group, n_groups: int, 
     return tally
 
 
+def summarize_bearoff(tally_row, cut_row, unfinished: int = 0) -> dict:
+    """One position's result from its 8 tally entries (the games played to the end) and its 4
+    cut sums (CUT_FIELDS: the games that reached the bearoff table and were scored with the
+    start mover's exact win probability P).  A cut game's result is y = 2 P - 1
+    points (a single game: both sides have checkers off).  With n_c cut games,
+    sum P = CUT_P / 2^20 and sum P^2 = CUT_P2 / 2^40: sum y = 2 sum P - n_c and
+    sum y^2 = 4 sum P^2 - 4 sum P + n_c.  On summarize's fields: `games` = natural + cut,
+    `equity` = (sum res + sum y) / games, `equity_stderr` from sum res^2 + sum y^2 as summarize
+    forms it, `win` = (wins + sum P) / games and `loss` likewise, the gammon and backgammon
+    rates count natural games only (over all games), `plies_per_game` over both kinds; adds
+    `natural_games`, `cut_games` and `cut_share` = cut_games / games.  The sums are combined as
+    integers, so equal cut values give their value exactly and a standard error of 0.  The
+    cut removes the endgame's dice noise, so equity_stderr is that of the mixed sample."""
+    r = summarize(tally_row, unfinished)
+    c = [int(v) for v in cut_row]
+    if len(c) != len(CUT_FIELDS):
+        raise ValueError(f"summarize_bearoff: a cut row has {len(CUT_FIELDS)} entries, got {len(c)}")
+    n_c, cut_plies, sp, sp2 = c
+    w, l = [r[f"win{j}"] for j in (1, 2, 3)], [r[f"loss{j}"] for j in (1, 2, 3)]
+    n_nat = r["games"]
+    n = n_nat + n_c
+    # sum of results in 2^-20 points, sum of squares in 2^-40: exact integers
+    s1 = sum((k + 1) * (w[k] - l[k]) for k in range(3)) * CUT_ONE + 2 * sp - n_c * CUT_ONE
+    s2 = sum((k + 1) ** 2 * (w[k] + l[k]) for k in range(3)) * CUT_ONE ** 2 + 4 * sp2 - 4 * sp * CUT_ONE + n_c * CUT_ONE ** 2
+    inv = 1.0 / n if n > 0 else 0.0
+    var_num = max(n * s2 - s1 * s1, 0)                       # n^2 (n - 1) CUT_ONE^2 x the variance of the mean
+    r.update(games=n, natural_games=n_nat, cut_games=n_c, cut_share=n_c * inv,
+             plies_per_game=(r["plies"] + cut_plies) * inv,
+             win=(sum(w) * CUT_ONE + sp) / (n * CUT_ONE) if n > 0 else 0.0,
+             loss=(sum(l) * CUT_ONE + n_c * CUT_ONE - sp) / (n * CUT_ONE) if n > 0 else 0.0,
+             win_gammon=(w[1] + w[2]) * inv, win_backgammon=w[2] * inv,
+             loss_gammon=(l[1] + l[2]) * inv, loss_backgammon=l[2] * inv,
+             equity=s1 / (n * CUT_ONE) if n > 0 else 0.0,
+             equity_stderr=math.sqrt(var_num / (n * n * (n - 1))) / CUT_ONE if n > 1 else 0.0)
+    return r
+
+
+def bearoff_cut_reference(records0, records, done, info, starts, group, n_groups: int, games_per_lane: int,
+                          configs, table, max_checkers: int) -> dict:
+    """A traced run with the bearoff cut replayed on the host, with the arithmetic of
+    bgx_rollout_begin / bgx_rollout_advance / bgx_rollout_bearoff_cut (include/bgx.h): a
+    selected lane whose record is in the table (bearoff.lookup_reference) adds
+    Pq = rint(fp32(q * 2^20)) clamped to [0, 2^20], q = W for the start mover on roll, else
+    fp32(1 - W), counts the game and is masked for the reset.  `records0` uint8[B, 64] = the
+    records the cut after begin saw, `records` uint8[steps, B, 64] those after each step (before
+    the masked reset), `done` / `info` [steps, B] as run_lanes traces them, `configs` / `table`
+    as BearoffDB publishes them.  Returns dict(tally int64[P, 8], cut_tally int64[P, 4],
+    games_done int64[B], active int, cut0 bool[B], cut bool[steps, B])."""
+    from .bearoff import lookup_reference
+    records0, records = np.asarray(records0), np.asarray(records)
+    done, info = np.asarray(done), np.asarray(info).astype(np.int64)
+    starts, group = np.asarray(starts), np.asarray(group).astype(np.int64)
+    B, P, G = group.shape[0], int(n_groups), int(games_per_lane)
+    valid = (group >= 0) & (group < P)
+    sel = valid & (G > 0)
+    plies, games = np.zeros(B, np.int64), np.zeros(B, np.int64)
+    tally, cut_tally = np.zeros((P, len(FIELDS)), np.int64), np.zeros((P, len(CUT_FIELDS)), np.int64)
+
+    def cut(recs):
+        nonlocal sel
+        in_db, w = lookup_reference(recs, configs, table, max_checkers)
+        m = sel & in_db
+        w = np.where(m, w, np.float32(0)).astype(np.float32)
+        q = np.where(recs[:, R_CUR] == starts[:, R_CUR], w, (np.float32(1) - w).astype(np.float32))
+        pq = np.clip(np.rint((q * np.float32(CUT_ONE)).astype(np.float32)).astype(np.int64), 0, CUT_ONE)
+        for f, v in enumerate((np.ones(B, np.int64), plies, pq, pq * pq)):
+            np.add.at(cut_tally[:, f], group[m], v[m])
+        games[m] += 1
+        plies[m] = 0
+        sel = sel & ~(m & (games >= G))
+        return m
+
+    cut0 = cut(records0)
+    cuts = np.zeros(done.shape, bool)
+    for t in range(done.shape[0]):
+        winner = ((info[t] >> 8) & 0xFF) - 1
+        score = np.clip((info[t] >> 16) & 0xFF, 1, 3)
+        fin = sel & (done[t] != 0) & (winner >= 0)
+        plies[sel] += 1
+        won = winner == (starts[:, R_CUR] & 1)
+        field = np.where(won, 2, 5) + score - 1
+        np.add.at(tally[:, 0], group[fin], 1)
+        np.add.at(tally[:, 1], group[fin], plies[fin])
+        np.add.at(tally, (group[fin], field[fin]), 1)
+        games[fin] += 1
+        plies[fin] = 0
+        sel = sel & ~(fin & (games >= G))
+        cuts[t] = cut(records[t])
+    return dict(tally=tally, cut_tally=cut_tally, games_done=games, active=int(sel.sum()), cut0=cut0, cut=cuts)
+
+
 def layout(n_positions: int, trials: int, first_roll: str = "stratified", batch: int = 4096):
     """How `trials` games of each of `n_positions` positions go onto `batch` lanes.  Returns
     (group int32[passes, batch], roll_of_lane uint8[passes, batch, 2], games_per_lane, passes):
@@ -218,7 +314,7 @@ class Rollout:
         self.steps = 0                  # steps of every run so far: the players' random streams go on
 
     def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
-                  trace: bool = False, luck=None):
+                  trace: bool = False, luck=None, bearoff=None):
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
@@ -235,7 +331,20 @@ class Rollout:
         active-lane count every step, as roll_luck synchronises anyway).  The games are the
         same as without it.  A fourth result follows the trace: luck_tally int64[n_groups, 4]
         (LUCK_FIELDS), and the trace gains the per-step luck f32[steps, B] (NaN on lanes
-        that never were active).  None: exactly the three results above."""
+        that never were active).  None: exactly the three results above.
+
+        `bearoff` (a bearoff.BearoffDB): a game that reaches the table stops
+        there -- [act, merge, step, advance, cut, reset(mask)] per step and one cut and reset
+        after begin (bgx_rollout_bearoff_cut, then the masked bgx_reset gives every cut lane
+        its start record again).  A start record that is in the table itself is cut before a
+        move is made; a lane's later games from it are cut after one ply.  A further result
+        follows the trace: cut_tally int64[n_groups, 4] (CUT_FIELDS), and the trace gains
+        cut uint8[steps, B] (each step's reset mask), cut_records uint8[steps, B, 64] (the
+        records that cut saw) and cut0 / cut_records0, the same for the cut after begin.
+        Together with `luck` it raises ValueError (the combined estimator needs cross sums
+        that are not kept).  None: nothing changes."""
+        if luck is not None and bearoff is not None:
+            raise ValueError("run_lanes: bearoff together with luck is not supported")
         max_steps, G, P = int(max_steps), int(games_per_lane), int(n_groups)
         if max_steps < 0 or G < 0 or P <= 0:
             raise ValueError(f"run_lanes: max_steps {max_steps}, games_per_lane {G} must be >= 0, n_groups {P} > 0")
@@ -266,6 +375,29 @@ class Rollout:
                   for n, dt in (("mover", torch.uint8), ("action", torch.int32), ("done", torch.uint8),
                                 ("info", torch.int32)) + ((("luck", torch.float32),) if luck is not None else ())}
             rec = torch.empty(self.B, 64, dtype=torch.uint8, device=dev)
+        if bearoff is not None:
+            if bearoff.device != dev:
+                raise ValueError(f"run_lanes: the bearoff database is on {bearoff.device}, the engine on {dev}")
+            cut_tally = torch.zeros(P, len(CUT_FIELDS), dtype=torch.int64, device=dev)
+            mask = torch.empty(self.B, dtype=torch.uint8, device=dev)
+            if trace:
+                tr["cut"] = torch.zeros(max_steps, self.B, dtype=torch.uint8, device=dev)
+                tr["cut_records"] = torch.zeros(max_steps, self.B, 64, dtype=torch.uint8, device=dev)
+
+            def cut(step):
+                if trace:
+                    eng.records(out=rec)
+                check(L.bgx_rollout_bearoff_cut(bearoff.handle(), recs, _ptr(starts), _ptr(grp), self.B, P, G,
+                                                _ptr(self.games_done), _ptr(self.plies), _ptr(self.sel),
+                                                _ptr(cut_tally), _ptr(self.active), _ptr(mask), _stream(dev)),
+                      "bgx_rollout_bearoff_cut")
+                if trace and step is not None:
+                    tr["cut"][step] = mask
+                    tr["cut_records"][step] = rec
+                eng.reset(lane_mask=mask, want_obs=False)
+
+            cut(None)
+            cut_begin = (mask.clone(), rec.clone()) if trace else None
         every = SYNC_EVERY if getattr(player, "sync_free", False) and luck is None else 1
         steps = 0
         active = int(self.active.item())
@@ -297,6 +429,8 @@ class Rollout:
             if trace:
                 tr["done"][steps] = done
                 tr["info"][steps] = info
+            if bearoff is not None:
+                cut(steps)
             steps += 1
             self.steps += 1
             if steps % every == 0 or steps == max_steps:
@@ -306,10 +440,14 @@ class Rollout:
         if trace:
             tr = {n: v[:steps] for n, v in tr.items()}
             tr.update(games_done=self.games_done.clone(), active=int(self.active.item()))
+            if bearoff is not None:
+                tr.update(cut0=cut_begin[0], cut_records0=cut_begin[1])
+        if bearoff is not None:
+            return tally, unfinished, tr, cut_tally
         return (tally, unfinished, tr) if luck is None else (tally, unfinished, tr, luck_tally)
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
-            trace: bool = False, luck=None, luck_scale="fit"):
+            trace: bool = False, luck=None, luck_scale="fit", bearoff=None):
         """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
         bytes come from the layout) `trials` times with `player` (any arena player object)
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
@@ -317,7 +455,11 @@ class Rollout:
         the list of the positions' results (summarize); with trace=True also the last
         pass's trace with its group, starts and games_per_lane.  `luck` (a search.ValueHead):
         the luck-adjusted rollout (run_lanes); the results are summarize_luck's, with
-        `luck_scale` ("fit" or a float) as its scale."""
+        `luck_scale` ("fit" or a float) as its scale.  `bearoff` (a bearoff.BearoffDB): the
+        rollout cut at the bearoff table (run_lanes); the results are summarize_bearoff's.
+        Not together with `luck` (ValueError)."""
+        if luck is not None and bearoff is not None:
+            raise ValueError("run: bearoff together with luck is not supported")
         pos = _records(positions)
         P = pos.shape[0]
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
@@ -326,9 +468,10 @@ class Rollout:
             grp = torch.from_numpy(group[k])
             starts = pos[grp.clamp(min=0).long()].clone()          # idle lanes: a valid record, never counted
             starts[:, R_ROLL0:R_ROLL1 + 1] = torch.from_numpy(roll[k])
-            out = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck)
+            out = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck,
+                                 bearoff=bearoff)
             tally, unf, tr = out[:3]
-            if luck is not None:
+            if luck is not None or bearoff is not None:
                 ltotal = out[3] if ltotal is None else ltotal + out[3]
             total = tally if total is None else total + tally
             unfinished = unf if unfinished is None else unfinished + unf
@@ -339,6 +482,9 @@ class Rollout:
         if luck is not None:
             lrows = ltotal.cpu().tolist()
             res = [summarize_luck(rows[p], lrows[p], luck_scale, unf[p]) for p in range(P)]
+        elif bearoff is not None:
+            crows = ltotal.cpu().tolist()
+            res = [summarize_bearoff(rows[p], crows[p], unf[p]) for p in range(P)]
         else:
             res = [summarize(rows[p], unf[p]) for p in range(P)]
         return (res, tr) if trace else res
@@ -482,6 +628,12 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--top-k must be >= 1")
         if ns.luck and ns.net == "random":
             self.error("--luck needs --net with weights (the luck is measured by the net's value head)")
+        if ns.bearoff is not None and ns.luck:
+            self.error("--bearoff and --luck cannot be combined")
+        for name in ("bearoff", "bearoff_play"):
+            k = getattr(ns, name)
+            if k is not None and not 1 <= k <= 8:
+                self.error(f"--{name.replace('_', '-')} takes a number of checkers in 1..8")
         if ns.trials < 1 or ns.batch < 1:
             self.error("--trials and --batch must be >= 1")
         return ns
@@ -504,6 +656,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="luck-adjusted (variance-reduced) rollout with the net's value head; needs weights")
     ap.add_argument("--luck-scale", type=_luck_scale, default="fit",
                     help="'fit' (the control-variate coefficient of the games) or a fixed number")
+    ap.add_argument("--bearoff", type=int, default=None, metavar="K",
+                    help="stop a game at the exact bearoff table for K checkers a side (1..8) and score it "
+                         "with its exact win probability; not with --luck")
+    ap.add_argument("--bearoff-play", type=int, nargs="?", const=6, default=None, metavar="K",
+                    help="the player moves perfectly where the position is in the bearoff table (K checkers "
+                         "a side, default 6)")
     return ap
 
 
@@ -522,8 +680,17 @@ def main(argv=None):
     if args.luck:
         from .search import ValueHead
         vh = ValueHead(net)
+    dbs = {}
+    if args.bearoff is not None or args.bearoff_play is not None:
+        from .bearoff import BearoffDB, BearoffPlayer
+        for k in {args.bearoff, args.bearoff_play} - {None}:
+            dbs[k] = BearoffDB(k, device=dev)
+        if args.bearoff_play is not None:
+            player = BearoffPlayer(player, dbs[args.bearoff_play])
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()                        # the table's build is not the rollout's time
     res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
-                 luck_scale=args.luck_scale)
+                 luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff))
     dt = time.perf_counter() - t0
     for i, r in enumerate(res):
         print(json.dumps(dict(position=i, **r)), flush=True)
@@ -535,6 +702,11 @@ def main(argv=None):
                    env_steps_per_s=ro.steps * args.batch / dt if dt > 0 else 0.0)
     if args.luck:
         summary.update(luck=True, luck_scale=args.luck_scale)
+    if dbs:
+        cut = sum(r.get("cut_games", 0) for r in res)
+        summary.update(bearoff=args.bearoff, bearoff_play=args.bearoff_play, cut_games=cut,
+                       cut_share=cut / games if games else 0.0,
+                       plies_per_game=sum(r["plies_per_game"] * r["games"] for r in res) / games if games else 0.0)
     print(json.dumps(summary), flush=True)
     return res, summary
 

@@ -989,6 +989,9 @@ static int step_debug_dump(bgx_engine* e, hipStream_t s) {
     return BGX_OK;
 }
 
+// the bearoff database: its kernels and entry points (they use the rollout helpers above)
+#include "bg_bearoff.h"
+
 extern "C" {
 
 int bgx_engine_create(int device, int32_t batch, int32_t max_moves, uint64_t seed, int32_t dice_mode,
