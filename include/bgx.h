@@ -546,6 +546,76 @@ int bgx_rollout_bearoff_cut(const bgx_bearoff* db, const uint8_t* records_dev, c
                             int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev, int64_t* cut_tally_dev,
                             int64_t* active_dev, uint8_t* reset_mask_out, void* stream);
 
+/* ---- one-sided bearoff database (csrc/bg_bearoff1.h; bgx/bearoff.py; no
+ * counterpart in the reference) ----
+ * For every configuration of ONE side's home board with at most K checkers, 1 <= K <= 15, the
+ * distribution of the number of rolls the side needs to bear everything off when it plays to
+ * minimise the mean of that number.  Two rows give the win probability of any race between two
+ * home boards -- an approximation (each side plays its own race and ignores the other's), where
+ * the two-sided table above is exact; DESIGN.md §12 has the measured distance.
+ * Configurations are those of the two-sided table (six counts c[d-1], sum <= K), n = C(K + 6, 6)
+ * of them (54,264 at K = 15), ordered by (pip count, then the base-16 number
+ * sum_d c[d-1] 16^(d-1)) ascending: index 0 is the empty one, every pip count is a contiguous
+ * range, and for K <= 8 the order is the two-sided table's (both are lexicographic on
+ * (c6, ..., c1) within a pip count).  succ(a, r) is the two-sided table's successor set, for
+ * the 21 rolls in bgx_two_ply's order.  With T = 32 entries a row and every product,
+ * difference and sum rounded to fp32 once (no fma):
+ *   D[empty][0] = 1, D[empty][t > 0] = 0;  mean[empty] = 0
+ *   choice[a][r] = the a' in succ(a, r) with the smallest (mean[a'], index a'), lexicographic
+ *                  (fp32 means tie, so the index decides); choice[empty][r] = empty
+ *   D[a][0] = 0;  D[a][t] = sum over r = 0..20, in that order from 0.0f, of
+ *                  p_r * D[choice[a][r]][t - 1],  t = 1..31
+ *   mean[a] = sum over t = 1..31, in that order from 0.0f, of fp32(t) * D[a][t]
+ *   S[a][0] = S[a][1] = 1.0f;  S[a][t + 1] = S[a][t] - D[a][t]      (a not empty;
+ *                  S[a][t] = P(a needs >= t rolls));  S[empty] = (1, 0, 0, ...)
+ *   win1(x on roll, y) = sum over t = 1..31, in that order from 0.0f, of D[x][t] * S[y][t]
+ *                  (x, y not empty): x wins when it needs no more rolls than y
+ * with p_r as above.  A numpy float32 loop reproduces every entry bit for bit.  At K = 15 the
+ * last non-zero entry of a row is at t = 30.  bgx_bearoff1_buffers:
+ *   dist float[n][32] = D,  surv float[n][32] = S,  mean float[n],  choice int32[n][21],
+ *   configs int8[n][6] the counts of configuration i.
+ * bgx_bearoff1_create: 1 <= max_checkers <= 15 (else BGX_EINVAL); allocates and builds on
+ * `stream`, two launches per pip count, and synchronises it once at the end; BGX_EOVERFLOW when
+ * a row has a non-zero D[a][31] (none does).  bgx_bearoff1_destroy synchronises the device. */
+typedef struct bgx_bearoff1 bgx_bearoff1;
+typedef struct {
+    const float* dist;
+    const float* surv;
+    const float* mean;
+    const int32_t* choice;
+    const int8_t* configs;
+    int32_t n, max_checkers;
+} bgx_bearoff1_buffers;
+int bgx_bearoff1_create(int device, int32_t max_checkers, void* stream, bgx_bearoff1** out);
+int bgx_bearoff1_buffers_get(bgx_bearoff1* db, bgx_bearoff1_buffers* out);
+int bgx_bearoff1_destroy(bgx_bearoff1* db);
+
+/* bgx_bearoff_lookup's record test with this table's K (a side may have all 15 checkers on the
+ * board).  in_db_out[i] = 1: in the table and both sides have borne a checker off, so every game
+ * from here is a single one and the equity is 2 win - 1; 2: in the table with all 15 checkers of
+ * a side on the board: win_out is still the win probability, but gammons are possible and it is
+ * no equity; 0: not in the table, win_out[i] is not written.  Where in_db_out[i] != 0,
+ * win_out[i] = win1(cfg(mover), cfg(opponent)).  win_out may be NULL.  No allocation, no
+ * synchronisation: graph-capturable. */
+int bgx_bearoff1_lookup(const bgx_bearoff1* db, const uint8_t* records_dev, int32_t n, uint8_t* in_db_out,
+                        float* win_out, void* stream);
+
+/* bgx_bearoff_act's contract on this table: for each selected lane whose record is in the table
+ * (in_db 1 or 2) and which has a legal move, act_inout[i] = the first argmax over the engine's
+ * move list of (a' empty ? 1 : 1 - win1(cfg(opponent), a')): it plays for the win given both
+ * sides' rows, which is better than minimising its own mean.  in_db_out receives the test's
+ * value (0, 1, 2) of the selected lanes and 0 for the others. */
+int bgx_bearoff1_act(bgx_engine* e, const bgx_bearoff1* db, const uint8_t* lane_sel_dev, int32_t* act_inout,
+                     uint8_t* in_db_out, void* stream);
+
+/* bgx_rollout_bearoff_cut with W = win1(cfg(mover), cfg(opponent)): the same arguments, sums,
+ * fixed point and reset mask.  It cuts only the lanes whose test gives 1: with 15 checkers of a
+ * side on the board the game may still be a gammon and is played on. */
+int bgx_rollout_bearoff1_cut(const bgx_bearoff1* db, const uint8_t* records_dev, const uint8_t* starts_dev,
+                             const int32_t* group_dev, int32_t n, int32_t n_groups, int32_t games_per_lane,
+                             int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev, int64_t* cut_tally_dev,
+                             int64_t* active_dev, uint8_t* reset_mask_out, void* stream);
+
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row
  * stride ld_logits; mask from the legal count in bytes 60-61 of each 64-byte

@@ -74,6 +74,12 @@ SIGNATURES = {
     "bgx_bearoff_lookup": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P]),
     "bgx_bearoff_act": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "bgx_rollout_bearoff_cut": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "bgx_bearoff1_create": (ctypes.c_int, [ctypes.c_int, _I32, _P, ctypes.POINTER(_P)]),
+    "bgx_bearoff1_buffers_get": (ctypes.c_int, [_P, _P]),
+    "bgx_bearoff1_destroy": (ctypes.c_int, [_P]),
+    "bgx_bearoff1_lookup": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P]),
+    "bgx_bearoff1_act": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
+    "bgx_rollout_bearoff1_cut": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),
@@ -159,6 +165,11 @@ class BgxBuffers(ctypes.Structure):
 
 class BgxBearoffBuffers(ctypes.Structure):
     _fields_ = [("table", _P), ("configs", _P), ("succ_off", _P), ("succ", _P), ("n", _I32), ("max_checkers", _I32)]
+
+
+class BgxBearoff1Buffers(ctypes.Structure):
+    _fields_ = [("dist", _P), ("surv", _P), ("mean", _P), ("choice", _P), ("configs", _P), ("n", _I32),
+                ("max_checkers", _I32)]
 
 
 _lib = None

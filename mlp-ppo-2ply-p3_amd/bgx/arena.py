@@ -284,6 +284,9 @@ class _Parser(argparse.ArgumentParser):
             k = getattr(ns, f"bearoff_{side}")
             if k is not None and not 1 <= k <= 8:
                 self.error(f"--bearoff-{side} takes a number of checkers in 1..8")
+            k = getattr(ns, f"bearoff1_{side}")
+            if k is not None and not 1 <= k <= 15:
+                self.error(f"--bearoff1-{side} takes a number of checkers in 1..15")
         return ns
 
 
@@ -307,6 +310,9 @@ def build_parser() -> argparse.ArgumentParser:
         ap.add_argument(f"--bearoff-{side}", type=int, default=None, metavar="K",
                         help=f"player {side.upper()} moves perfectly where the position is in the exact bearoff "
                              "table for K checkers a side (1..8; bgx/bearoff.py)")
+        ap.add_argument(f"--bearoff1-{side}", type=int, default=None, metavar="K",
+                        help=f"player {side.upper()} moves by the one-sided bearoff table for K checkers a side "
+                             f"(1..15) in every pure home-board race; inside --bearoff-{side}'s table that one plays")
     return ap
 
 
@@ -319,6 +325,11 @@ def main(argv=None):
     players = [make_player(k, n, seed=args.seed * 2 + 1 + i, top_k=tk, margin=mg)
                for i, (k, n, tk, mg) in enumerate(zip((args.player_a, args.player_b), nets,
                                                       (args.top_k_a, args.top_k_b), (args.margin_a, args.margin_b)))]
+    if args.bearoff1_a is not None or args.bearoff1_b is not None:
+        from .bearoff import OneSidedBearoffDB, OneSidedPlayer
+        dbs1 = {k: OneSidedBearoffDB(k, device=dev) for k in {args.bearoff1_a, args.bearoff1_b} - {None}}
+        players = [p if k is None else OneSidedPlayer(p, dbs1[k])
+                   for p, k in zip(players, (args.bearoff1_a, args.bearoff1_b))]
     if args.bearoff_a is not None or args.bearoff_b is not None:
         from .bearoff import BearoffDB, BearoffPlayer
         dbs = {k: BearoffDB(k, device=dev) for k in {args.bearoff_a, args.bearoff_b} - {None}}
@@ -334,6 +345,7 @@ def main(argv=None):
                games_per_lane=args.games_per_lane, max_steps=args.max_steps, seed=args.seed, seconds=dt,
                top_k_a=args.top_k_a, top_k_b=args.top_k_b, margin_a=args.margin_a, margin_b=args.margin_b,
                bearoff_a=args.bearoff_a, bearoff_b=args.bearoff_b,
+               **{k: v for k, v in (("bearoff1_a", args.bearoff1_a), ("bearoff1_b", args.bearoff1_b)) if v is not None},
                games_per_s=res["games"] / dt if dt > 0 else 0.0,
                env_steps_per_s=res["steps"] * args.batch / dt if dt > 0 else 0.0)
     print(json.dumps(res), flush=True)

@@ -10,6 +10,14 @@ perfect play -- is a finite dynamic program.  The table gives
 
 A configuration is the six counts c[d-1], d = 1..6, of checkers at distance d from bearing off
 (PLAYER1: point 24 - d; PLAYER2: point d - 1).  BearoffDB.configs() publishes the index order.
+
+The table stops at 8 checkers a side.  OneSidedBearoffDB (csrc/bg_bearoff1.h
+behind bgx_bearoff1_*) covers every pure home-board race, up to all 15 checkers: per
+configuration the distribution of the number of rolls to bear off, and from two rows an
+approximate win probability (each side minimises its own mean number of rolls), with
+OneSidedPlayer and the same rollout cut.  Because the cut's values are then approximate, the
+`equity_stderr` of a rollout cut at this table measures the spread of the sample and no longer
+the error against the truth.
 """
 from __future__ import annotations
 
@@ -23,6 +31,8 @@ from ._lib import check
 from .engine import R_CUR, R_OVER, _ptr, _stream
 
 MAX_CHECKERS = 8
+MAX_CHECKERS1 = 15                  # the one-sided table
+ROW = 32                            # entries of a one-sided row: t = 0..31 rolls
 # the 21 rolls in bgx_two_ply's order and their probabilities as the table's build adds them
 ROLLS21 = [(a, b) for a in range(1, 7) for b in range(a, 7)]
 ROLL_P = np.array([1.0 / 36.0 if a == b else 2.0 / 36.0 for a, b in ROLLS21], np.float32)
@@ -31,6 +41,10 @@ ROLL_P = np.array([1.0 / 36.0 if a == b else 2.0 / 36.0 for a, b in ROLLS21], np
 class BearoffDB:
     """The table for at most `max_checkers` (1..8) checkers a side, built on `device` on the
     current stream; n = C(max_checkers + 6, 6) configurations (924 at the default 6)."""
+
+    kind = "two-sided"
+    lookup_entry = "bgx_bearoff_lookup"            # the C entry points of this kind of table
+    cut_entry = "bgx_rollout_bearoff_cut"          # (BearoffPlayer; Rollout.run_lanes)
 
     def __init__(self, max_checkers: int = 6, device=None):
         K = int(max_checkers)
@@ -145,14 +159,196 @@ class BearoffPlayer:
             self.buf = (torch.empty(B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev),
                         torch.empty(B, dtype=torch.int32, device=dev))
         in_db, rest, act = self.buf
-        check(self.db._lib.bgx_bearoff_lookup(self.db._h, ctypes.c_void_p(eng.lanes_ptr()), B, _ptr(in_db), None,
-                                              _stream(dev)), "bgx_bearoff_lookup")
+        check(getattr(self.db._lib, self.db.lookup_entry)(self.db._h, ctypes.c_void_p(eng.lanes_ptr()), B, _ptr(in_db),
+                                                          None, _stream(dev)), self.db.lookup_entry)
         torch.logical_and(sel != 0, in_db == 0, out=rest.view(torch.bool))
         act.copy_(self.inner.act(eng, rest, step))
         return self.db.act(eng, sel, act)
 
 
+class OneSidedBearoffDB:
+    """The one-sided table (csrc/bg_bearoff1.h behind bgx_bearoff1_*) for at
+    most `max_checkers` (1..15) checkers a side, built on `device` on the current stream:
+    for each of the n = C(max_checkers + 6, 6) configurations (54,264 at the default 15) the
+    distribution of the number of rolls it needs to bear off when it minimises their mean.
+    Two rows give a race's win probability -- an approximation where BearoffDB is exact, but
+    for every pure home-board race.  Configurations are indexed as in BearoffDB."""
+
+    kind = "one-sided"
+    lookup_entry = "bgx_bearoff1_lookup"
+    cut_entry = "bgx_rollout_bearoff1_cut"
+    _view = BearoffDB._view
+
+    def __init__(self, max_checkers: int = MAX_CHECKERS1, device=None):
+        K = int(max_checkers)
+        if not 1 <= K <= MAX_CHECKERS1:
+            raise ValueError(f"OneSidedBearoffDB: max_checkers must be in 1..{MAX_CHECKERS1}, got {max_checkers}")
+        self._lib = _lib.load()
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise ValueError("OneSidedBearoffDB needs a GPU device (HIP); there is no CPU fallback")
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        h = ctypes.c_void_p()
+        check(self._lib.bgx_bearoff1_create(dev.index, K, _stream(dev), ctypes.byref(h)), "bgx_bearoff1_create")
+        self._h = h
+        b = _lib.BgxBearoff1Buffers()
+        check(self._lib.bgx_bearoff1_buffers_get(h, ctypes.byref(b)), "bgx_bearoff1_buffers_get")
+        self.n, self.K = int(b.n), int(b.max_checkers)
+        self._dist = self._view(b.dist, (self.n, ROW), torch.float32)
+        self._surv = self._view(b.surv, (self.n, ROW), torch.float32)
+        self._mean = self._view(b.mean, (self.n,), torch.float32)
+        self._choice = self._view(b.choice, (self.n, 21), torch.int32)
+        self._configs = self._view(b.configs, (self.n, 6), torch.int8)
+        self._index = None
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self._lib.bgx_bearoff1_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def handle(self):
+        return self._h
+
+    def dist(self) -> torch.Tensor:
+        """D as an [n, 32] fp32 view of the database's memory (do not write to it): D[a, t] =
+        the probability that configuration a is borne off with exactly t rolls."""
+        return self._dist
+
+    def surv(self) -> torch.Tensor:
+        """S as an [n, 32] fp32 view: S[a, t] = the probability that a needs at least t rolls."""
+        return self._surv
+
+    def mean(self) -> torch.Tensor:
+        """The mean number of rolls, an [n] fp32 view."""
+        return self._mean
+
+    def choice(self) -> torch.Tensor:
+        """[n, 21] int32 view: the configuration the table plays to from a with roll r (ROLLS21)."""
+        return self._choice
+
+    def configs(self) -> torch.Tensor:
+        """The index order: [n, 6] int8, row i = the counts of configuration i at distances 1..6."""
+        return self._configs
+
+    def index_of(self, config) -> int:
+        """The index of a configuration given as its six counts (a host convenience)."""
+        if self._index is None:
+            self._index = {tuple(int(v) for v in c): i for i, c in enumerate(self._configs.cpu().numpy())}
+        key = tuple(int(v) for v in config)
+        if len(key) != 6 or key not in self._index:
+            raise ValueError(f"index_of: {config!r} is not six counts with a sum of at most {self.K}")
+        return self._index[key]
+
+    def lookup(self, records: torch.Tensor, out=None):
+        """(in_db uint8[n], win f32[n]) for uint8 [n, 64] lane records on the database's device
+        (bgx_bearoff1_lookup): in_db = 1 in the table with checkers of both sides off (equity
+        2 win - 1), 2 in the table with all 15 checkers of a side on the board (win is the win
+        probability, gammons are possible), 0 not in it.  win is written only where in_db is not
+        0; the other entries keep what `out` = (in_db, win) held (NaN without `out`)."""
+        r = records
+        if r.dim() != 2 or r.shape[1] != 64 or r.dtype != torch.uint8 or r.device != self.device:
+            raise ValueError(f"lookup: records must be uint8 [n, 64] on {self.device}, got {r.dtype} "
+                             f"{tuple(r.shape)} on {r.device}")
+        r = r.contiguous()
+        n = r.shape[0]
+        if out is None:
+            out = (torch.empty(n, dtype=torch.uint8, device=self.device),
+                   torch.full((n,), float("nan"), dtype=torch.float32, device=self.device))
+        in_db, win = out
+        check(self._lib.bgx_bearoff1_lookup(self._h, _ptr(r), n, _ptr(in_db), _ptr(win), _stream(self.device)),
+              "bgx_bearoff1_lookup")
+        return in_db, win
+
+    def act(self, eng, sel, act: torch.Tensor, in_db=None):
+        """bgx_bearoff1_act: act[i] = the move with the best win probability by the table, of
+        every lane with sel[i] != 0 (None: every lane) whose record is in the table; the other
+        entries stay."""
+        check(self._lib.bgx_bearoff1_act(eng._h, self._h, _ptr(sel), _ptr(act), _ptr(in_db), _stream(eng.device)),
+              "bgx_bearoff1_act")
+        return act
+
+
+class OneSidedPlayer(BearoffPlayer):
+    """BearoffPlayer on a OneSidedBearoffDB: the table's move in every pure home-board race,
+    `inner`'s move elsewhere.  It nests: BearoffPlayer(OneSidedPlayer(inner, db1), db) plays
+    exactly where the small exact table reaches and by the one-sided table in the rest of the
+    bearoff."""
+
+
 # ------------------------------------------------------------- host references --
+def dist_reference(succ, n: int):
+    """(dist f32[n, 32], surv f32[n, 32], mean f32[n], choice int32[n, 21]) of the one-sided
+    table on the host, from successor sets given as index lists as for table_reference (index
+    0 = the empty configuration, every play leads to a smaller index; duplicates do not
+    matter), by the recurrence of include/bgx.h in numpy float32, every product, difference and
+    sum rounded once: the device table's bits."""
+    f = np.float32
+    dist, surv = np.zeros((n, ROW), f), np.zeros((n, ROW), f)
+    mean, choice = np.zeros(n, f), np.zeros((n, 21), np.int32)
+    dist[0, 0] = surv[0, 0] = f(1)
+    for a in range(1, n):
+        for r in range(21):
+            choice[a, r] = min((mean[int(x)], int(x)) for x in succ[a][r])[1]
+        dist[a], surv[a], mean[a] = row_reference(dist[choice[a]])
+    return dist, surv, mean, choice
+
+
+def row_reference(rows):
+    """One configuration's (dist f32[32], surv f32[32], mean f32) from the f32[21, 32] rows of
+    its 21 chosen successors: the recurrence's step for one a."""
+    f = np.float32
+    acc = np.zeros(ROW - 1, f)
+    for r in range(21):
+        acc = (acc + (ROLL_P[r] * np.asarray(rows[r], f)[:-1]).astype(f)).astype(f)
+    d = np.concatenate([np.zeros(1, f), acc])
+    s = np.ones(ROW, f)
+    m = f(0)
+    for t in range(1, ROW):
+        m = f(m + f(f(t) * d[t]))
+        if t + 1 < ROW:
+            s[t + 1] = f(s[t] - d[t])
+    return d, s, m
+
+
+def win1_reference(dist_x, surv_y) -> np.ndarray:
+    """win1(x on roll, y) = sum over t = 1..31, in that order from 0, of D[x][t] S[y][t] in numpy
+    float32 for rows dist_x f32[..., 32] of x and surv_y f32[..., 32] of y (broadcast together)."""
+    f = np.float32
+    dx, sy = np.asarray(dist_x, f), np.asarray(surv_y, f)
+    acc = np.zeros(np.broadcast(dx[..., 0], sy[..., 0]).shape, f)
+    for t in range(1, ROW):
+        acc = (acc + (dx[..., t] * sy[..., t]).astype(f)).astype(f)
+    return acc
+
+
+def lookup1_reference(records, configs, dist, surv, max_checkers: int):
+    """bgx_bearoff1_lookup on the host: (in_db uint8[n] in {0, 1, 2}, win f32[n], NaN where not
+    in the table) for uint8 [n, 64] records, with `configs`, `dist` and `surv` as
+    OneSidedBearoffDB publishes them."""
+    r = np.asarray(records).astype(np.int64)
+    configs, K = np.asarray(configs), int(max_checkers)
+    dist, surv = np.asarray(dist, np.float32), np.asarray(surv, np.float32)
+    index = {tuple(int(v) for v in c): i for i, c in enumerate(configs)}
+    c0, c1 = r[:, 23:17:-1], r[:, 24:30]                      # distances 1..6 of PLAYER1 / PLAYER2
+    h0, h1 = c0.sum(1), c1.sum(1)
+    inside = ((r[:, R_OVER] == 0) & (r[:, 48] == 0) & (r[:, 49] == 0) & (r[:, 0:18].sum(1) == 0) &
+              (r[:, 30:48].sum(1) == 0) & (h0 >= 1) & (h0 <= K) & (h1 >= 1) & (h1 <= K) &
+              (h0 + r[:, 50] == 15) & (h1 + r[:, 51] == 15))
+    in_db = np.where(inside, np.where((h0 < 15) & (h1 < 15), 1, 2), 0).astype(np.uint8)
+    win = np.full(r.shape[0], np.nan, np.float32)
+    for i in np.nonzero(inside)[0]:
+        idx = (index[tuple(c0[i])], index[tuple(c1[i])])
+        m = int(r[i, R_CUR]) & 1
+        win[i] = win1_reference(dist[idx[m]], surv[idx[1 - m]])
+    return in_db, win
+
+
 def lookup_reference(records, configs, table, max_checkers: int):
     """bgx_bearoff_lookup on the host: (in_db bool[n], win f32[n], NaN where not in the table)
     for uint8 [n, 64] records, with `configs` int8[n_cfg, 6] and `table` f32[n_cfg, n_cfg] as

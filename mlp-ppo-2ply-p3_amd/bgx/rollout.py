@@ -13,7 +13,9 @@ player acts for both sides.  Equity is in points (1 / 2 / 3 per game, cubeless) 
 side of the position's mover.  --luck: the luck-adjusted (variance-reduced) estimate beside the
 raw one (summarize_luck; DESIGN.md "Luck adjustment").  --bearoff K: a game that reaches the exact
 bearoff table (bgx/bearoff.py) stops there and is scored with its exact win probability
-(summarize_bearoff).
+(summarize_bearoff).  --bearoff1 K: the same cut at the one-sided table, which
+reaches every pure home-board race but whose win probability is an approximation (DESIGN.md
+§12): the `equity_stderr` of cut games then no longer measures the error against the truth.
 """
 from __future__ import annotations
 
@@ -190,7 +192,7 @@ def summarize_bearoff(tally_row, cut_row, unfinished: int = 0) -> dict:
 
 
 def bearoff_cut_reference(records0, records, done, info, starts, group, n_groups: int, games_per_lane: int,
-                          configs, table, max_checkers: int) -> dict:
+                          configs=None, table=None, max_checkers: int = 0, lookup=None) -> dict:
     """A traced run with the bearoff cut replayed on the host, with the arithmetic of
     bgx_rollout_begin / bgx_rollout_advance / bgx_rollout_bearoff_cut (include/bgx.h): a
     selected lane whose record is in the table (bearoff.lookup_reference) adds
@@ -198,9 +200,16 @@ def bearoff_cut_reference(records0, records, done, info, starts, group, n_groups
     fp32(1 - W), counts the game and is masked for the reset.  `records0` uint8[B, 64] = the
     records the cut after begin saw, `records` uint8[steps, B, 64] those after each step (before
     the masked reset), `done` / `info` [steps, B] as run_lanes traces them, `configs` / `table`
-    as BearoffDB publishes them.  Returns dict(tally int64[P, 8], cut_tally int64[P, 4],
+    as BearoffDB publishes them.  `lookup` (optional): another table's test and value instead,
+    a function records uint8[B, 64] -> (cut bool[B], w f32[B]); for the one-sided table, the
+    lanes with bearoff.lookup1_reference's in_db == 1 and its win; configs, table and
+    max_checkers are then not read.  Returns dict(tally int64[P, 8], cut_tally int64[P, 4],
     games_done int64[B], active int, cut0 bool[B], cut bool[steps, B])."""
-    from .bearoff import lookup_reference
+    if lookup is None:
+        from .bearoff import lookup_reference
+
+        def lookup(recs):
+            return lookup_reference(recs, configs, table, max_checkers)
     records0, records = np.asarray(records0), np.asarray(records)
     done, info = np.asarray(done), np.asarray(info).astype(np.int64)
     starts, group = np.asarray(starts), np.asarray(group).astype(np.int64)
@@ -212,7 +221,7 @@ def bearoff_cut_reference(records0, records, done, info, starts, group, n_groups
 
     def cut(recs):
         nonlocal sel
-        in_db, w = lookup_reference(recs, configs, table, max_checkers)
+        in_db, w = lookup(recs)
         m = sel & in_db
         w = np.where(m, w, np.float32(0)).astype(np.float32)
         q = np.where(recs[:, R_CUR] == starts[:, R_CUR], w, (np.float32(1) - w).astype(np.float32))
@@ -333,9 +342,11 @@ class Rollout:
         (LUCK_FIELDS), and the trace gains the per-step luck f32[steps, B] (NaN on lanes
         that never were active).  None: exactly the three results above.
 
-        `bearoff` (a bearoff.BearoffDB): a game that reaches the table stops
+        `bearoff` (a bearoff.BearoffDB, DESIGN.md §11, or a bearoff.OneSidedBearoffDB, §12,
+        which cuts where both sides have a checker off): a game that reaches the table stops
         there -- [act, merge, step, advance, cut, reset(mask)] per step and one cut and reset
-        after begin (bgx_rollout_bearoff_cut, then the masked bgx_reset gives every cut lane
+        after begin (the table's cut, bgx_rollout_bearoff_cut or bgx_rollout_bearoff1_cut,
+        then the masked bgx_reset gives every cut lane
         its start record again).  A start record that is in the table itself is cut before a
         move is made; a lane's later games from it are cut after one ply.  A further result
         follows the trace: cut_tally int64[n_groups, 4] (CUT_FIELDS), and the trace gains
@@ -387,10 +398,10 @@ class Rollout:
             def cut(step):
                 if trace:
                     eng.records(out=rec)
-                check(L.bgx_rollout_bearoff_cut(bearoff.handle(), recs, _ptr(starts), _ptr(grp), self.B, P, G,
-                                                _ptr(self.games_done), _ptr(self.plies), _ptr(self.sel),
-                                                _ptr(cut_tally), _ptr(self.active), _ptr(mask), _stream(dev)),
-                      "bgx_rollout_bearoff_cut")
+                check(getattr(L, bearoff.cut_entry)(bearoff.handle(), recs, _ptr(starts), _ptr(grp), self.B, P, G,
+                                                    _ptr(self.games_done), _ptr(self.plies), _ptr(self.sel),
+                                                    _ptr(cut_tally), _ptr(self.active), _ptr(mask), _stream(dev)),
+                      bearoff.cut_entry)
                 if trace and step is not None:
                     tr["cut"][step] = mask
                     tr["cut_records"][step] = rec
@@ -455,9 +466,12 @@ class Rollout:
         the list of the positions' results (summarize); with trace=True also the last
         pass's trace with its group, starts and games_per_lane.  `luck` (a search.ValueHead):
         the luck-adjusted rollout (run_lanes); the results are summarize_luck's, with
-        `luck_scale` ("fit" or a float) as its scale.  `bearoff` (a bearoff.BearoffDB): the
-        rollout cut at the bearoff table (run_lanes); the results are summarize_bearoff's.
-        Not together with `luck` (ValueError)."""
+        `luck_scale` ("fit" or a float) as its scale.  `bearoff` (a bearoff.BearoffDB or
+        bearoff.OneSidedBearoffDB): the rollout cut at the bearoff table (run_lanes); the results
+        are summarize_bearoff's.  With the one-sided table they also carry
+        `bearoff_kind` = "one-sided": its cut values are approximations, so `equity_stderr` is
+        the sample's spread and no longer measures the error against the truth.  Not together
+        with `luck` (ValueError)."""
         if luck is not None and bearoff is not None:
             raise ValueError("run: bearoff together with luck is not supported")
         pos = _records(positions)
@@ -485,6 +499,9 @@ class Rollout:
         elif bearoff is not None:
             crows = ltotal.cpu().tolist()
             res = [summarize_bearoff(rows[p], crows[p], unf[p]) for p in range(P)]
+            if bearoff.kind != "two-sided":
+                for r in res:
+                    r["bearoff_kind"] = bearoff.kind
         else:
             res = [summarize(rows[p], unf[p]) for p in range(P)]
         return (res, tr) if trace else res
@@ -630,10 +647,14 @@ class _Parser(argparse.ArgumentParser):
             self.error("--luck needs --net with weights (the luck is measured by the net's value head)")
         if ns.bearoff is not None and ns.luck:
             self.error("--bearoff and --luck cannot be combined")
-        for name in ("bearoff", "bearoff_play"):
+        if ns.bearoff1 is not None and ns.luck:
+            self.error("--bearoff1 and --luck cannot be combined")
+        if ns.bearoff is not None and ns.bearoff1 is not None:
+            self.error("--bearoff and --bearoff1 cannot be combined (one cut per rollout)")
+        for name, top in (("bearoff", 8), ("bearoff_play", 8), ("bearoff1", 15), ("bearoff1_play", 15)):
             k = getattr(ns, name)
-            if k is not None and not 1 <= k <= 8:
-                self.error(f"--{name.replace('_', '-')} takes a number of checkers in 1..8")
+            if k is not None and not 1 <= k <= top:
+                self.error(f"--{name.replace('_', '-')} takes a number of checkers in 1..{top}")
         if ns.trials < 1 or ns.batch < 1:
             self.error("--trials and --batch must be >= 1")
         return ns
@@ -662,6 +683,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--bearoff-play", type=int, nargs="?", const=6, default=None, metavar="K",
                     help="the player moves perfectly where the position is in the bearoff table (K checkers "
                          "a side, default 6)")
+    ap.add_argument("--bearoff1", type=int, default=None, metavar="K",
+                    help="stop a game at the one-sided bearoff table for K checkers a side (1..15) once both "
+                         "sides have a checker off, and score it with the table's approximate win probability; "
+                         "not with --luck or --bearoff")
+    ap.add_argument("--bearoff1-play", type=int, nargs="?", const=15, default=None, metavar="K",
+                    help="the player moves by the one-sided bearoff table in every pure home-board race (K "
+                         "checkers a side, default 15); with --bearoff-play the exact table plays where it reaches")
     return ap
 
 
@@ -680,17 +708,21 @@ def main(argv=None):
     if args.luck:
         from .search import ValueHead
         vh = ValueHead(net)
-    dbs = {}
-    if args.bearoff is not None or args.bearoff_play is not None:
-        from .bearoff import BearoffDB, BearoffPlayer
+    dbs, dbs1 = {}, {}
+    if any(k is not None for k in (args.bearoff, args.bearoff_play, args.bearoff1, args.bearoff1_play)):
+        from .bearoff import BearoffDB, BearoffPlayer, OneSidedBearoffDB, OneSidedPlayer
         for k in {args.bearoff, args.bearoff_play} - {None}:
             dbs[k] = BearoffDB(k, device=dev)
-        if args.bearoff_play is not None:
+        for k in {args.bearoff1, args.bearoff1_play} - {None}:
+            dbs1[k] = OneSidedBearoffDB(k, device=dev)
+        if args.bearoff1_play is not None:
+            player = OneSidedPlayer(player, dbs1[args.bearoff1_play])
+        if args.bearoff_play is not None:               # outside: the exact table where it reaches
             player = BearoffPlayer(player, dbs[args.bearoff_play])
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()                        # the table's build is not the rollout's time
     res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
-                 luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff))
+                 luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff) or dbs1.get(args.bearoff1))
     dt = time.perf_counter() - t0
     for i, r in enumerate(res):
         print(json.dumps(dict(position=i, **r)), flush=True)
@@ -702,8 +734,10 @@ def main(argv=None):
                    env_steps_per_s=ro.steps * args.batch / dt if dt > 0 else 0.0)
     if args.luck:
         summary.update(luck=True, luck_scale=args.luck_scale)
-    if dbs:
+    if dbs or dbs1:
         cut = sum(r.get("cut_games", 0) for r in res)
+        if dbs1:
+            summary.update(bearoff1=args.bearoff1, bearoff1_play=args.bearoff1_play)
         summary.update(bearoff=args.bearoff, bearoff_play=args.bearoff_play, cut_games=cut,
                        cut_share=cut / games if games else 0.0,
                        plies_per_game=sum(r["plies_per_game"] * r["games"] for r in res) / games if games else 0.0)

@@ -11,7 +11,8 @@
 // reference's enumeration order for order (handle_moves.py:109-310 + the max-length filter,
 // get_all_moves.py:9-94) on a pure bearoff board, where the opponent never blocks or is hit.
 // Part 2 (device): the build, lookup, perfect-play and rollout-cut kernels and their C entry
-// points.  BGX_BEAROFF_HOST_ONLY (a host test program, any C++ compiler) takes part 1 alone.
+// points.  BGX_BEAROFF_HOST_ONLY (a host test program, any C++ compiler) takes part 1 alone;
+// BGX_BEAROFF_PART1_ONLY does so in a device translation unit (bg_bearoff1.h).
 #pragma once
 #include <stdint.h>
 
@@ -126,7 +127,7 @@ BO_HD int bo_successors(uint32_t pack, int r0, int r1, BoSet& s) {
 
 }  // namespace bg
 
-#ifndef BGX_BEAROFF_HOST_ONLY
+#if !defined(BGX_BEAROFF_HOST_ONLY) && !defined(BGX_BEAROFF_PART1_ONLY)
 // ======================================================================== part 2 ==
 
 // The object behind the C ABI's opaque bgx_bearoff*: device buffers, fixed after creation.
@@ -531,4 +532,4 @@ int bgx_rollout_bearoff_cut(const bgx_bearoff* db, const uint8_t* records_dev, c
 }
 
 }  // extern "C"
-#endif  // BGX_BEAROFF_HOST_ONLY
+#endif  // part 2

@@ -285,3 +285,6 @@ extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, floa
     hipLaunchKernelGGL(k_normalize_adv, dim3(nb), dim3(256), 0, (hipStream_t)stream, adv, n, n4, sums, eps);
     return bgx_launch_status();
 }
+
+// the one-sided bearoff database: its kernels use mul_rn / add_rn / sub_rn above
+#include "bg_bearoff1.h"
