@@ -616,6 +616,77 @@ int bgx_rollout_bearoff1_cut(const bgx_bearoff1* db, const uint8_t* records_dev,
                              int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev, int64_t* cut_tally_dev,
                              int64_t* active_dev, uint8_t* reset_mask_out, void* stream);
 
+/* ---- the doubling cube in position rollouts, money play (csrc/bg_cube.h; bgx/cube.py,
+ * bgx/rollout.py; no counterpart in the reference) ----
+ * Beside the state of bgx_rollout_begin / bgx_rollout_advance: cube uint8[n], the cube of the
+ * lane's current game, and cube0 uint8[n], the cube each game on lane i starts with, both the
+ * caller's device arrays.  A state byte: bits 0-3 = k (the cube shows 2^k, 0 <= k <= 10), bits
+ * 4-5 = the owner (0 centred, 1 PLAYER1 = mover byte 0, 2 PLAYER2).  A byte is valid when
+ * k <= cap, owner <= 2 and owner == 0 exactly when k == 0; the kernels read k as min(k, cap) and
+ * owner 3 as 0, so they are defined on any byte.  cube_tally int64[n_groups][8]
+ * (bgx_rollout_cube_field) is zeroed by the caller.  The rule is passed by value:
+ *   scale, double_at, pass_at, too_good_at: with e = scale * equity in fp32 (one product), the
+ *     side on roll doubles iff double_at <= e <= too_good_at (a NaN never doubles), and the
+ *     opponent passes iff e > pass_at, else it takes;
+ *   cap: no double at k == cap (0..10);  jacoby != 0: a game that ends with the cube at k == 0
+ *     counts 1 point, gammon or not.
+ * Per step: cube_sel, the equity of the dsel lanes (bgx_roll_luck's mean_out with dsel as its
+ * lane selection, or any other source), cube_decide, bgx_reset with the mask, the players' act,
+ * bgx_step, cube_flush, bgx_rollout_advance; cube_begin once after bgx_rollout_begin.
+ * bgx_rollout_cube_begin: cube[i] = cube0[i], sanitised as above.
+ * bgx_rollout_cube_sel: dsel_out[i] = 1 when sel[i] != 0, the group is valid, plies[i] > 0 (no
+ * cube action on a game's first ply), the record is not game_over (byte 55), k < cap and the cube
+ * is centred or owned by the record's mover; else 0.
+ * bgx_rollout_cube_decide: for a lane with dsel[i] != 0 and a valid group, m = the record's mover
+ * and equity[i] = m's own equity before its roll (cube_sel's test of the cube itself, k < cap and
+ * centred or m's own, is made again, so a dsel of another origin cannot take the cube past the
+ * cap).  The mover doubles and the opponent
+ * passes: the game ends worth y = +-(1 << k), positive when m is the start record's mover (byte
+ * 52 of starts_dev[i]); row group[i]: CUBE_GAMES += 1, CUBE_POINTS += y, CUBE_POINTS2 += y * y,
+ * CUBE_LOG2 += k, PASS_GAMES += 1, PASS_PLIES += plies[i], PASS_WON += (y > 0), DOUBLES += 1;
+ * games_done[i] += 1, plies[i] = 0; the lane's last game: sel[i] = 0 and active drops;
+ * cube[i] = cube0[i]; reset_mask_out[i] = 1.  The mover doubles and the opponent takes: k += 1,
+ * owner = 2 - m (the other side), DOUBLES += 1.  Every other lane gets reset_mask_out[i] = 0 and
+ * is otherwise untouched.  The caller then runs bgx_reset with the mask.
+ * bgx_rollout_cube_flush: after bgx_step and BEFORE bgx_rollout_advance, with the step's done and
+ * info.  A lane with sel[i] != 0, a valid group and a game that bgx_rollout_advance counts (done
+ * with a winner): s = info's game_score, or 1 when rule.jacoby and k == 0; y = +-(s << k) from
+ * the start mover's side; CUBE_GAMES += 1, CUBE_POINTS += y, CUBE_POINTS2 += y * y,
+ * CUBE_LOG2 += k; then cube[i] = cube0[i].  Any other done of a selected lane only resets the
+ * cube.  |y| <= 3 * 2^10, so y^2 < 2^24 and a row holds 2^39 games.  The sums are integers:
+ * run-to-run identical, and CUBE_GAMES = BGX_ROLLOUT_GAMES of the plain tally + PASS_GAMES.
+ * Plain kernels, one thread per lane, no allocation and no synchronisation: graph-capturable.
+ * BGX_EINVAL for n <= 0, n_groups <= 0, games_per_lane < 0, a NULL pointer, cap outside 0..10 or
+ * a NaN in scale, double_at or pass_at (too_good_at may be +inf). */
+typedef struct {
+    float scale, double_at, pass_at, too_good_at;
+    int32_t cap;
+    int32_t jacoby;
+} bgx_cube_rule;
+enum bgx_rollout_cube_field {
+    BGX_ROLLOUT_CUBE_GAMES = 0,       /* games that ended, played out or passed */
+    BGX_ROLLOUT_CUBE_POINTS = 1,      /* sum of y, points from the start mover's side */
+    BGX_ROLLOUT_CUBE_POINTS2 = 2,     /* sum of y^2 */
+    BGX_ROLLOUT_CUBE_LOG2 = 3,        /* sum of k at the game's end */
+    BGX_ROLLOUT_CUBE_PASS_GAMES = 4,  /* games ended by a passed double */
+    BGX_ROLLOUT_CUBE_PASS_PLIES = 5,  /* their steps */
+    BGX_ROLLOUT_CUBE_PASS_WON = 6,    /* of them, won by the start mover */
+    BGX_ROLLOUT_CUBE_DOUBLES = 7      /* doubles offered, taken or passed */
+};
+int bgx_rollout_cube_begin(const uint8_t* cube0_dev, int32_t n, int32_t cap, uint8_t* cube_dev, void* stream);
+int bgx_rollout_cube_sel(const uint8_t* records_dev, const int32_t* group_dev, int32_t n_groups,
+                         const int32_t* plies_dev, const uint8_t* sel_dev, const uint8_t* cube_dev, int32_t n,
+                         int32_t cap, uint8_t* dsel_out, void* stream);
+int bgx_rollout_cube_decide(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev,
+                            const uint8_t* dsel_dev, const float* equity_dev, int32_t n, int32_t n_groups,
+                            int32_t games_per_lane, bgx_cube_rule rule, const uint8_t* cube0_dev, uint8_t* cube_dev,
+                            int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev, int64_t* cube_tally_dev,
+                            int64_t* active_dev, uint8_t* reset_mask_out, void* stream);
+int bgx_rollout_cube_flush(const uint8_t* starts_dev, const int32_t* group_dev, const uint8_t* sel_dev,
+                           const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
+                           bgx_cube_rule rule, const uint8_t* cube0_dev, uint8_t* cube_dev, int64_t* cube_tally_dev,
+                           void* stream);
+
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row
  * stride ld_logits; mask from the legal count in bytes 60-61 of each 64-byte

@@ -19,6 +19,14 @@ DICE_MT_LANE, DICE_MT_SHARED, DICE_PHILOX = 0, 1, 2
 # (name, restype, argtypes) for every symbol declared in include/bgx.h
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
+
+
+class BgxCubeRule(ctypes.Structure):
+    """include/bgx.h bgx_cube_rule, passed by value."""
+    _fields_ = [("scale", ctypes.c_float), ("double_at", ctypes.c_float), ("pass_at", ctypes.c_float),
+                ("too_good_at", ctypes.c_float), ("cap", _I32), ("jacoby", _I32)]
+
+
 SIGNATURES = {
     "bgx_engine_create": (ctypes.c_int, [ctypes.c_int, _I32, _I32, ctypes.c_uint64, _I32, _I32, _I32,
                                          ctypes.POINTER(_P)]),
@@ -80,6 +88,11 @@ SIGNATURES = {
     "bgx_bearoff1_lookup": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P]),
     "bgx_bearoff1_act": (ctypes.c_int, [_P, _P, _P, _P, _P, _P]),
     "bgx_rollout_bearoff1_cut": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P]),
+    "bgx_rollout_cube_begin": (ctypes.c_int, [_P, _I32, _I32, _P, _P]),
+    "bgx_rollout_cube_sel": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P, _I32, _I32, _P, _P]),
+    "bgx_rollout_cube_decide": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, BgxCubeRule, _P, _P, _P, _P, _P, _P,
+                                               _P, _P, _P]),
+    "bgx_rollout_cube_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, BgxCubeRule, _P, _P, _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),

@@ -1,0 +1,249 @@
+"""The doubling cube in position rollouts, money play (the device side is
+csrc/bg_cube.h, the four bgx_rollout_cube_* entry points of include/bgx.h; bgx/rollout.py runs
+them in its loop).  A game is worth its cubeless 1 / 2 / 3 points times the cube, 2^k; the side
+on roll may double before it rolls when the cube is centred or its own, the opponent takes
+(k + 1, the cube is now the taker's) or passes (the game ends at 2^k).  Both decisions follow one
+threshold rule, CubeRule, on the mover's equity before the roll.
+
+    python -m bgx.rollout --net ckpt.pt --player 1ply --positions opening --trials 1296 --cube
+    python -m bgx.rollout --net ckpt.pt --player 1ply --positions pos.json --cube --cube-decision
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# cube_tally int64[n_groups][8] (include/bgx.h bgx_rollout_cube_field)
+CUBE_FIELDS = ("cube_games", "cube_points", "cube_points2", "cube_log2", "pass_games", "pass_plies", "pass_won",
+               "doubles")
+MAX_CAP = 10
+CENTRED = 0                         # the owner field: 0 centred, 1 PLAYER1, 2 PLAYER2
+
+
+def pack(k: int, owner: int) -> int:
+    """The cube's state byte: k in bits 0-3 (the cube shows 2^k), the owner in bits 4-5."""
+    return int(k) | (int(owner) << 4)
+
+
+def unpack(byte):
+    """(k, owner) of state bytes (an int or an array)."""
+    b = np.asarray(byte).astype(np.int64)
+    return b & 15, (b >> 4) & 3
+
+
+def sanitise(byte, cap: int):
+    """The byte as the kernels read it: k as min(k, cap), owner 3 as 0."""
+    k, o = unpack(byte)
+    return (np.minimum(k, int(cap)) | (np.where(o == 3, 0, o) << 4)).astype(np.uint8)
+
+
+def validate_cube0(cube0: torch.Tensor, cap: int) -> None:
+    """ValueError naming the first lane whose byte is not a cube state: k <= cap, owner <= 2 and
+    owner == 0 exactly when k == 0 (torch ops: the bytes stay where they are)."""
+    c = cube0.to(torch.int32)
+    k, o = c & 15, c >> 4
+    bad = (k > int(cap)) | (o > 2) | ((o == 0) != (k == 0))
+    if bool(bad.any()):
+        i = int(torch.nonzero(bad)[0, 0])
+        raise ValueError(f"cube0: lane {i} holds {int(c[i])} (k {int(k[i])}, owner {int(o[i])}): need k <= cap = "
+                         f"{int(cap)}, owner <= 2 and owner == 0 exactly when k == 0")
+
+
+class CubeRule:
+    """The threshold rule of both cube decisions.  With e = scale * equity, equity the mover's own
+    equity before its roll: the mover doubles iff double_at <= e <= too_good_at, the opponent
+    passes iff e > pass_at and takes otherwise.  `pass_at` = 0.5 is the dead-cube take point:
+    taking at stakes 2 costs 2 e, passing costs 1.  `double_at` is a parameter of the rule, not a
+    claim about the best window.  `cap`: no double once the cube shows 2^cap (0..10).  `jacoby`:
+    a game that ends with the cube still centred at 1 counts 1 point, gammon or not.
+
+    `value` gives the equity: a search.ValueHead -- equity = roll_luck's mean on the lanes that
+    may double, the mover's expected best 1-ply value over the 21 rolls, taken without a look at
+    the roll the lane holds -- or a callable f(eng, dsel) -> contiguous float32[B] on the
+    engine's device with the mover's equity (entries off dsel are ignored).  `scale` plays the
+    part of the luck adjustment's c: it turns the value's unit into points.  The rule presumes a
+    mover's-view value (positive = good for the side on roll), which is what `--returns selfplay`
+    trains; a net trained on another target gives decisions that mean nothing."""
+
+    def __init__(self, value, scale: float = 1.0, double_at: float = 0.40, pass_at: float = 0.50,
+                 too_good_at: float = math.inf, cap: int = 6, jacoby: bool = False):
+        from .search import ValueHead
+        if not isinstance(value, ValueHead) and not callable(value):
+            raise ValueError("CubeRule: value must be a search.ValueHead or a callable f(eng, dsel)")
+        for name, v in (("scale", scale), ("double_at", double_at), ("pass_at", pass_at), ("too_good_at", too_good_at)):
+            if math.isnan(float(v)):
+                raise ValueError(f"CubeRule: {name} is NaN")
+        if int(cap) != cap or not 0 <= int(cap) <= MAX_CAP:
+            raise ValueError(f"CubeRule: cap must be in 0..{MAX_CAP}, got {cap!r}")
+        self.value, self.is_head = value, isinstance(value, ValueHead)
+        self.scale, self.double_at, self.pass_at = float(scale), float(double_at), float(pass_at)
+        self.too_good_at, self.cap, self.jacoby = float(too_good_at), int(cap), bool(jacoby)
+        # equity calls so far and, with a value head, the lanes they covered (rows) and the leaves
+        self.totals = {"calls": 0, "rows": 0, "leaves": 0}
+
+    def struct(self) -> _lib.BgxCubeRule:
+        return _lib.BgxCubeRule(self.scale, self.double_at, self.pass_at, self.too_good_at, self.cap, int(self.jacoby))
+
+    def equity(self, eng, dsel: torch.Tensor, scratch: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """The mover's equity on the dsel lanes, float32[B] on the engine's device."""
+        self.totals["calls"] += 1
+        if self.is_head:
+            from .search import roll_luck
+            stats = roll_luck(eng, self.value, sel=dsel, out=(scratch, out))[2]
+            self.totals["rows"] += stats["rows"]
+            self.totals["leaves"] += stats["leaves"]
+            return out
+        e = self.value(eng, dsel)
+        if (not isinstance(e, torch.Tensor) or e.dtype != torch.float32 or e.device != eng.device
+                or not e.is_contiguous() or e.numel() != eng.batch):
+            raise ValueError("a cube rule's value must return a contiguous float32[B] tensor on the engine's device")
+        return e
+
+
+def summarize_cube(tally_row, cube_row, unfinished: int = 0) -> dict:
+    """One position's cubeful result from its 8 tally entries (the games played to the end) and its
+    8 cube sums (CUBE_FIELDS), in fp64 from the integers: `games` (played out + passed),
+    `equity_cubeful` = CUBE_POINTS / games in points from the start mover's side,
+    `equity_cubeful_stderr` = sqrt((CUBE_POINTS2 - games equity^2) / (games - 1) / games),
+    `pass_share` = PASS_GAMES / games, `doubles_per_game`, `mean_cube_log2` (the mean k at the
+    game's end), `plies_per_game` over PLIES + PASS_PLIES, the 8 sums under their names, and
+    `played_out` = summarize(tally_row): the cubeless result of the subset of games that
+    reached the end -- no estimate of the position's cubeless equity, as the passed games are
+    missing from it.  No games: the rates are 0; one game: the standard error is 0.  Raises
+    ValueError when CUBE_GAMES != GAMES + PASS_GAMES."""
+    from .rollout import summarize
+    played = summarize(tally_row, unfinished)
+    c = [int(v) for v in cube_row]
+    if len(c) != len(CUBE_FIELDS):
+        raise ValueError(f"summarize_cube: a cube row has {len(CUBE_FIELDS)} entries, got {len(c)}")
+    r = dict(zip(CUBE_FIELDS, c))
+    n = r["cube_games"]
+    if n != played["games"] + r["pass_games"]:
+        raise ValueError(f"summarize_cube: the cube row counts {n} games, the tally row {played['games']} and "
+                         f"{r['pass_games']} passed")
+    def per_game(v):
+        return v / n if n > 0 else 0.0
+
+    var_num = max(n * r["cube_points2"] - r["cube_points"] ** 2, 0)        # n^2 (n - 1) x the variance of the mean
+    r.update(games=n, equity_cubeful=per_game(r["cube_points"]),
+             equity_cubeful_stderr=math.sqrt(var_num / (n * n * (n - 1))) if n > 1 else 0.0,
+             pass_share=per_game(r["pass_games"]), doubles_per_game=per_game(r["doubles"]),
+             mean_cube_log2=per_game(r["cube_log2"]), plies_per_game=per_game(played["plies"] + r["pass_plies"]),
+             unfinished=int(unfinished), played_out=played)
+    return r
+
+
+def decide_reference(cube, mover, equity, rule: CubeRule):
+    """cube_decision of csrc/bg_cube.h on arrays: (action int[B]: 0 none, 1 take, 2 pass; next
+    uint8[B]; access bool[B] = cube_access), without the lane selection."""
+    cube, mover = np.asarray(cube), np.asarray(mover).astype(np.int64) & 1
+    cap = rule.cap
+    c = sanitise(cube, cap)
+    k, o = unpack(c)
+    access = (k < cap) & ((o == 0) | (o == mover + 1))
+    f = np.float32
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = (f(rule.scale) * np.asarray(equity, f)).astype(f)
+        dbl = access & (e >= f(rule.double_at)) & (e <= f(rule.too_good_at))
+        pas = dbl & (e > f(rule.pass_at))
+    take = dbl & ~pas
+    nxt = np.where(take, (k + 1) | ((2 - mover) << 4), c).astype(np.uint8)
+    return np.where(pas, 2, np.where(take, 1, 0)), nxt, access
+
+
+def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rule: CubeRule, cube0=None) -> dict:
+    """A traced cube run replayed on the host with the kernels' arithmetic (include/bgx.h
+    bgx_rollout_cube_*).  `trace`: run_lanes' with cube_mover, cube_equity, done and info
+    [steps, B]; the lane records are taken as not game_over, which holds between the steps of an
+    auto-reset engine.  Returns dict(cube_tally int64[P, 8], tally int64[P, 8], cube uint8[steps,
+    B] = the states before each decision, dsel / mask bool[steps, B], games_done int64[B],
+    active int)."""
+    from .rollout import FIELDS, R_CUR
+    mover = np.asarray(torch.as_tensor(trace["cube_mover"]).cpu()).astype(np.int64)
+    equity = np.asarray(torch.as_tensor(trace["cube_equity"]).cpu()).astype(np.float32)
+    done = np.asarray(torch.as_tensor(trace["done"]).cpu())
+    info = np.asarray(torch.as_tensor(trace["info"]).cpu()).astype(np.int64)
+    starts, group = np.asarray(torch.as_tensor(starts).cpu()), np.asarray(torch.as_tensor(group).cpu()).astype(np.int64)
+    B, P, G, cap = group.shape[0], int(n_groups), int(games_per_lane), rule.cap
+    c0 = np.zeros(B, np.uint8) if cube0 is None else sanitise(np.asarray(torch.as_tensor(cube0).cpu()), cap)
+    cube = c0.copy()
+    valid = (group >= 0) & (group < P)
+    start_m = starts[:, R_CUR].astype(np.int64) & 1
+    plies, games = np.zeros(B, np.int64), np.zeros(B, np.int64)
+    tally, ct = np.zeros((P, len(FIELDS)), np.int64), np.zeros((P, len(CUBE_FIELDS)), np.int64)
+    T = done.shape[0]
+    states, dsels, masks = np.zeros((T, B), np.uint8), np.zeros((T, B), bool), np.zeros((T, B), bool)
+
+    def add(rows, lanes, values):
+        for f, v in values.items():
+            np.add.at(rows[:, f], group[lanes], np.broadcast_to(v, (B,))[lanes])
+
+    for t in range(T):
+        sel = valid & (games < G)
+        states[t] = cube
+        k, _ = unpack(cube)
+        m = mover[t] & 1
+        act, nxt, access = decide_reference(cube, m, equity[t], rule)
+        dsel = sel & (plies > 0) & access
+        dsels[t] = dsel
+        act = np.where(dsel, act, 0)
+        pas, dbl = act == 2, act > 0
+        y = np.where(m == start_m, 1, -1) * (1 << k)
+        add(ct, pas, {0: 1, 1: y, 2: y * y, 3: k, 4: 1, 5: plies, 6: (y > 0).astype(np.int64)})
+        add(ct, dbl, {7: 1})
+        masks[t] = pas
+        games += pas
+        plies = np.where(pas, 0, plies)
+        cube = np.where(pas, c0, np.where(dbl, nxt, cube)).astype(np.uint8)
+        # the step, cube_flush and advance
+        sel = valid & (games < G)
+        plies = plies + sel
+        winner = ((info[t] >> 8) & 0xFF) - 1
+        score = np.clip((info[t] >> 16) & 0xFF, 1, 3)
+        dn = sel & (done[t] != 0)
+        fin = dn & (winner >= 0)
+        k, _ = unpack(cube)
+        won = winner == start_m
+        s = np.where(rule.jacoby & (k == 0), 1, score)
+        y = np.where(won, 1, -1) * (s << k)
+        add(ct, fin, {0: 1, 1: y, 2: y * y, 3: k})
+        add(tally, fin, {0: 1, 1: plies})
+        np.add.at(tally, (group[fin], (np.where(won, 2, 5) + score - 1)[fin]), 1)
+        cube = np.where(dn, c0, cube).astype(np.uint8)
+        games += fin
+        plies = np.where(fin, 0, plies)
+    return dict(cube_tally=ct, tally=tally, cube=states, dsel=dsels, mask=masks, games_done=games,
+                active=int((valid & (games < G)).sum()))
+
+
+def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, cube=(0, CENTRED),
+                          first_roll: str = "stratified", max_steps: int = 4000) -> dict:
+    """"Double or not, take or pass?" for the side on roll in `record` (uint8[64]: board and
+    mover), holding the cube `cube` = (k, owner) with access to it.  The position is rolled out
+    twice in one run, as two groups over the same start records: "no double", with the cube as
+    given, and "double, take", with k + 1 owned by the opponent.  No cube action happens on a
+    game's first ply, so both start after the decision asked about.  Returns `no_double`,
+    `double_take` and `double_pass` = +1, the mover's equities in units of the current cube 2^k,
+    each with its `_stderr`, the two rollouts' summaries (`rollouts`), and the verdict: `double`
+    iff min(double_take, 1) > no_double, `take` iff double_take <= 1."""
+    rec = torch.as_tensor(record).reshape(-1)
+    if rec.numel() != 64 or rec.dtype != torch.uint8:
+        raise ValueError("rollout_cube_decision: record must be 64 bytes (uint8)")
+    k, owner = int(cube[0]), int(cube[1])
+    mover = int(rec[52]) & 1
+    if not 0 <= k < rule.cap or owner not in (0, mover + 1) or (owner == 0) != (k == 0):
+        raise ValueError(f"rollout_cube_decision: cube {(k, owner)} gives the mover (PLAYER{mover + 1}) no double below "
+                         f"the cap {rule.cap}")
+    pos = torch.stack([rec.cpu(), rec.cpu()])
+    res = rollout.run(player, pos, trials, first_roll=first_roll, max_steps=max_steps, cube=rule,
+                      cube_start=[(k, owner), (k + 1, 2 - mover)])
+    unit = float(1 << k)
+    nd, dt = res[0]["equity_cubeful"] / unit, res[1]["equity_cubeful"] / unit
+    return dict(no_double=nd, no_double_stderr=res[0]["equity_cubeful_stderr"] / unit,
+                double_take=dt, double_take_stderr=res[1]["equity_cubeful_stderr"] / unit,
+                double_pass=1.0, double_pass_stderr=0.0, double=bool(min(dt, 1.0) > nd), take=bool(dt <= 1.0),
+                cube=[k, owner], rollouts=res)

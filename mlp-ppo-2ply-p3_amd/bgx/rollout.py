@@ -16,6 +16,10 @@ bearoff table (bgx/bearoff.py) stops there and is scored with its exact win prob
 (summarize_bearoff).  --bearoff1 K: the same cut at the one-sided table, which
 reaches every pure home-board race but whose win probability is an approximation (DESIGN.md
 §12): the `equity_stderr` of cut games then no longer measures the error against the truth.
+--cube: money play with the doubling cube (bgx/cube.py): before its roll the side
+on roll may double by a threshold rule on a net's value, a passed double ends the game, and the
+result is the cubeful equity (cube.summarize_cube); --cube-decision answers "double or not,
+take or pass?" per position.
 """
 from __future__ import annotations
 
@@ -323,7 +327,7 @@ class Rollout:
         self.steps = 0                  # steps of every run so far: the players' random streams go on
 
     def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
-                  trace: bool = False, luck=None, bearoff=None):
+                  trace: bool = False, luck=None, bearoff=None, cube=None, cube0=None):
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
@@ -353,9 +357,30 @@ class Rollout:
         cut uint8[steps, B] (each step's reset mask), cut_records uint8[steps, B, 64] (the
         records that cut saw) and cut0 / cut_records0, the same for the cut after begin.
         Together with `luck` it raises ValueError (the combined estimator needs cross sums
-        that are not kept).  None: nothing changes."""
+        that are not kept).  None: nothing changes.
+
+        `cube` (a cube.CubeRule): money play with the doubling cube.  `cube0`
+        uint8[B] = the cube every game on the lane starts with (cube.pack(k, owner); None:
+        centred at 1 everywhere; ValueError names the first lane with an invalid byte).  Per
+        step [cube_sel, equity, cube_decide, reset(mask), act, merge, step, cube_flush,
+        advance] and cube_begin after begin: before its roll, but never on a game's first ply,
+        the side on roll may double by the rule on its equity (the rule's value head or
+        callable); a passed double ends the game at the cube's value and the masked reset
+        gives the lane its start record again.  The host reads the active-lane count every
+        step, as the equity synchronises.  A further result follows the trace: cube_tally
+        int64[n_groups, 8] (cube.CUBE_FIELDS), and the trace gains per step cube uint8 (the
+        state before the decision), cube_mover (the side on roll there), cube_dsel (the lanes
+        that may double), cube_equity (NaN off cube_dsel) and cube_mask (the passes).  Together
+        with `luck` or `bearoff` it raises ValueError: the luck of a cubeful game and cubeful
+        table values do not exist.  None: nothing changes."""
         if luck is not None and bearoff is not None:
             raise ValueError("run_lanes: bearoff together with luck is not supported")
+        if cube is not None and luck is not None:
+            raise ValueError("run_lanes: cube together with luck is not supported")
+        if cube is not None and bearoff is not None:
+            raise ValueError("run_lanes: cube together with bearoff is not supported")
+        if cube is None and cube0 is not None:
+            raise ValueError("run_lanes: cube0 without cube")
         max_steps, G, P = int(max_steps), int(games_per_lane), int(n_groups)
         if max_steps < 0 or G < 0 or P <= 0:
             raise ValueError(f"run_lanes: max_steps {max_steps}, games_per_lane {G} must be >= 0, n_groups {P} > 0")
@@ -375,6 +400,19 @@ class Rollout:
         eng.reset(want_obs=False)
         check(L.bgx_rollout_begin(recs, _ptr(starts), _ptr(grp), self.B, P, G, *state, _stream(dev)),
               "bgx_rollout_begin")
+        if cube is not None:
+            from .cube import CUBE_FIELDS, validate_cube0
+            c0 = (torch.zeros(self.B, dtype=torch.uint8, device=dev) if cube0 is None
+                  else torch.as_tensor(cube0).to(dev).contiguous())
+            if c0.shape != (self.B,) or c0.dtype != torch.uint8:
+                raise ValueError(f"run_lanes: cube0 must be uint8[{self.B}]")
+            validate_cube0(c0, cube.cap)
+            rule = cube.struct()
+            cube_tally = torch.zeros(P, len(CUBE_FIELDS), dtype=torch.int64, device=dev)
+            cstate, dsel, cmask = (torch.zeros(self.B, dtype=torch.uint8, device=dev) for _ in range(3))
+            ebuf, escratch = (torch.full((self.B,), float("nan"), dtype=torch.float32, device=dev) for _ in range(2))
+            check(L.bgx_rollout_cube_begin(_ptr(c0), self.B, cube.cap, _ptr(cstate), _stream(dev)),
+                  "bgx_rollout_cube_begin")
         if luck is not None:
             from .search import roll_luck
             luck_tally = torch.zeros(P, len(LUCK_FIELDS), dtype=torch.int64, device=dev)
@@ -384,7 +422,9 @@ class Rollout:
         if trace:
             tr = {n: torch.zeros(max_steps, self.B, dtype=dt, device=dev)
                   for n, dt in (("mover", torch.uint8), ("action", torch.int32), ("done", torch.uint8),
-                                ("info", torch.int32)) + ((("luck", torch.float32),) if luck is not None else ())}
+                                ("info", torch.int32)) + ((("luck", torch.float32),) if luck is not None else ())
+                  + ((("cube", torch.uint8), ("cube_mover", torch.uint8), ("cube_dsel", torch.uint8),
+                      ("cube_equity", torch.float32), ("cube_mask", torch.uint8)) if cube is not None else ())}
             rec = torch.empty(self.B, 64, dtype=torch.uint8, device=dev)
         if bearoff is not None:
             if bearoff.device != dev:
@@ -409,7 +449,7 @@ class Rollout:
 
             cut(None)
             cut_begin = (mask.clone(), rec.clone()) if trace else None
-        every = SYNC_EVERY if getattr(player, "sync_free", False) and luck is None else 1
+        every = SYNC_EVERY if getattr(player, "sync_free", False) and luck is None and cube is None else 1
         steps = 0
         active = int(self.active.item())
         while active > 0 and steps < max_steps:
@@ -419,6 +459,23 @@ class Rollout:
                                              _ptr(self.lane_luck), _stream(dev)), "bgx_rollout_luck_add")
                 if trace:
                     tr["luck"][steps] = lbuf
+            if cube is not None:
+                check(L.bgx_rollout_cube_sel(recs, _ptr(grp), P, _ptr(self.plies), _ptr(self.sel), _ptr(cstate), self.B,
+                                             cube.cap, _ptr(dsel), _stream(dev)), "bgx_rollout_cube_sel")
+                eq = cube.equity(eng, dsel, escratch, ebuf)
+                if trace:
+                    eng.records(out=rec)
+                    tr["cube"][steps] = cstate
+                    tr["cube_mover"][steps] = rec[:, R_CUR]
+                    tr["cube_dsel"][steps] = dsel
+                    tr["cube_equity"][steps] = torch.where(dsel != 0, eq, float("nan"))
+                check(L.bgx_rollout_cube_decide(recs, _ptr(starts), _ptr(grp), _ptr(dsel), _ptr(eq), self.B, P, G, rule,
+                                                _ptr(c0), _ptr(cstate), _ptr(self.games_done), _ptr(self.plies),
+                                                _ptr(self.sel), _ptr(cube_tally), _ptr(self.active), _ptr(cmask),
+                                                _stream(dev)), "bgx_rollout_cube_decide")
+                if trace:
+                    tr["cube_mask"][steps] = cmask
+                eng.reset(lane_mask=cmask, want_obs=False)
             act = player.act(eng, self.sel, self.steps)
             if (not isinstance(act, torch.Tensor) or act.dtype != torch.int32 or act.device != dev
                     or not act.is_contiguous() or act.numel() != self.B):
@@ -435,6 +492,10 @@ class Rollout:
                 check(L.bgx_rollout_luck_flush(_ptr(starts), _ptr(grp), _ptr(self.sel), _ptr(done), _ptr(info), self.B,
                                                P, _ptr(self.lane_luck), _ptr(luck_tally), _stream(dev)),
                       "bgx_rollout_luck_flush")
+            if cube is not None:
+                check(L.bgx_rollout_cube_flush(_ptr(starts), _ptr(grp), _ptr(self.sel), _ptr(done), _ptr(info), self.B, P,
+                                               rule, _ptr(c0), _ptr(cstate), _ptr(cube_tally), _stream(dev)),
+                      "bgx_rollout_cube_flush")
             check(L.bgx_rollout_advance(recs, _ptr(starts), _ptr(grp), _ptr(done), _ptr(info), self.B, P, G,
                                         *state, _stream(dev)), "bgx_rollout_advance")
             if trace:
@@ -455,10 +516,12 @@ class Rollout:
                 tr.update(cut0=cut_begin[0], cut_records0=cut_begin[1])
         if bearoff is not None:
             return tally, unfinished, tr, cut_tally
+        if cube is not None:
+            return tally, unfinished, tr, cube_tally
         return (tally, unfinished, tr) if luck is None else (tally, unfinished, tr, luck_tally)
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
-            trace: bool = False, luck=None, luck_scale="fit", bearoff=None):
+            trace: bool = False, luck=None, luck_scale="fit", bearoff=None, cube=None, cube_start=(0, 0)):
         """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
         bytes come from the layout) `trials` times with `player` (any arena player object)
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
@@ -471,21 +534,33 @@ class Rollout:
         are summarize_bearoff's.  With the one-sided table they also carry
         `bearoff_kind` = "one-sided": its cut values are approximations, so `equity_stderr` is
         the sample's spread and no longer measures the error against the truth.  Not together
-        with `luck` (ValueError)."""
+        with `luck` (ValueError).  `cube` (a cube.CubeRule): money play with the
+        doubling cube (run_lanes); every game starts with the cube `cube_start` = (k, owner),
+        owner 0 centred, 1 PLAYER1, 2 PLAYER2, or one such pair per position; the results are
+        cube.summarize_cube's.  Not together with `luck` or `bearoff` (ValueError)."""
         if luck is not None and bearoff is not None:
             raise ValueError("run: bearoff together with luck is not supported")
+        if cube is not None and (luck is not None or bearoff is not None):
+            raise ValueError(f"run: cube together with {'luck' if luck is not None else 'bearoff'} is not supported")
         pos = _records(positions)
         P = pos.shape[0]
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
         total = unfinished = tr = ltotal = None
+        if cube is not None:
+            from .cube import pack, summarize_cube
+            cs = np.asarray(cube_start, np.int64)
+            if cs.shape not in ((2,), (P, 2)):
+                raise ValueError(f"run: cube_start must be (k, owner) or one pair per position, got shape {cs.shape}")
+            start_byte = torch.tensor([pack(k, o) for k, o in np.broadcast_to(cs, (P, 2))], dtype=torch.uint8)
         for k in range(passes):
             grp = torch.from_numpy(group[k])
             starts = pos[grp.clamp(min=0).long()].clone()          # idle lanes: a valid record, never counted
             starts[:, R_ROLL0:R_ROLL1 + 1] = torch.from_numpy(roll[k])
             out = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck,
-                                 bearoff=bearoff)
+                                 bearoff=bearoff, cube=cube,
+                                 cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None)
             tally, unf, tr = out[:3]
-            if luck is not None or bearoff is not None:
+            if luck is not None or bearoff is not None or cube is not None:
                 ltotal = out[3] if ltotal is None else ltotal + out[3]
             total = tally if total is None else total + tally
             unfinished = unf if unfinished is None else unfinished + unf
@@ -502,6 +577,9 @@ class Rollout:
             if bearoff.kind != "two-sided":
                 for r in res:
                     r["bearoff_kind"] = bearoff.kind
+        elif cube is not None:
+            crows = ltotal.cpu().tolist()
+            res = [summarize_cube(rows[p], crows[p], unf[p]) for p in range(P)]
         else:
             res = [summarize(rows[p], unf[p]) for p in range(P)]
         return (res, tr) if trace else res
@@ -634,7 +712,8 @@ def _luck_scale(text: str):
 
 
 class _Parser(argparse.ArgumentParser):
-    """--top-k is an error for any player but a 2ply one with weights; --luck needs weights."""
+    """--top-k is an error for any player but a 2ply one with weights; --luck and --cube need
+    weights; --cube goes with neither --luck nor a bearoff cut."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -655,6 +734,20 @@ class _Parser(argparse.ArgumentParser):
             k = getattr(ns, name)
             if k is not None and not 1 <= k <= top:
                 self.error(f"--{name.replace('_', '-')} takes a number of checkers in 1..{top}")
+        if ns.cube_decision and not ns.cube:
+            self.error("--cube-decision needs --cube")
+        if ns.cube:
+            if ns.net == "random" and ns.cube_net is None:
+                self.error("--cube needs --net with weights or --cube-net (the decisions are made on a net's "
+                           "value head)")
+            for name in ("luck", "bearoff", "bearoff1"):
+                if getattr(ns, name) not in (None, False):
+                    self.error(f"--cube and --{name} cannot be combined")
+            if not 0 <= ns.cube_cap <= 10:
+                self.error("--cube-cap takes a number in 0..10")
+            for name in ("cube_double", "cube_pass", "cube_too_good", "cube_scale"):
+                if math.isnan(getattr(ns, name)):
+                    self.error(f"--{name.replace('_', '-')} must be a number")
         if ns.trials < 1 or ns.batch < 1:
             self.error("--trials and --batch must be >= 1")
         return ns
@@ -690,6 +783,21 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--bearoff1-play", type=int, nargs="?", const=15, default=None, metavar="K",
                     help="the player moves by the one-sided bearoff table in every pure home-board race (K "
                          "checkers a side, default 15); with --bearoff-play the exact table plays where it reaches")
+    ap.add_argument("--cube", action="store_true",
+                    help="money play with the doubling cube: cubeful equity beside the played-out games' result; "
+                         "needs weights; not with --luck, --bearoff or --bearoff1")
+    ap.add_argument("--cube-net", default=None, metavar="PATH",
+                    help="the state_dict whose value head makes the cube decisions (default: the player's net)")
+    ap.add_argument("--cube-double", type=float, default=0.40, help="the mover doubles from this equity on")
+    ap.add_argument("--cube-pass", type=float, default=0.50, help="the opponent passes above this equity")
+    ap.add_argument("--cube-too-good", type=float, default=math.inf,
+                    help="the mover plays on for the gammon above this equity")
+    ap.add_argument("--cube-scale", type=float, default=1.0, help="points per unit of the net's value")
+    ap.add_argument("--cube-cap", type=int, default=6, help="no double once the cube shows 2^CAP (0..10)")
+    ap.add_argument("--jacoby", action="store_true", help="gammons count only after a double")
+    ap.add_argument("--cube-decision", action="store_true",
+                    help="per position: no double / double, take / double, pass for the side on roll with a "
+                         "centred cube, and the verdict")
     return ap
 
 
@@ -721,13 +829,31 @@ def main(argv=None):
             player = BearoffPlayer(player, dbs[args.bearoff_play])
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()                        # the table's build is not the rollout's time
-    res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
-                 luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff) or dbs1.get(args.bearoff1))
+    rule = None
+    if args.cube:
+        from .cube import CubeRule, rollout_cube_decision
+        from .search import ValueHead
+        rule = CubeRule(ValueHead(net if args.cube_net is None else load_net(args.cube_net, dev)),
+                        scale=args.cube_scale, double_at=args.cube_double, pass_at=args.cube_pass,
+                        too_good_at=args.cube_too_good, cap=args.cube_cap, jacoby=args.jacoby)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+    if args.cube_decision:
+        # one line per position: the three equities and the verdict; the summary counts both rollouts' games
+        res = []
+        for i in range(positions.shape[0]):
+            d = rollout_cube_decision(ro, player, positions[i], args.trials, rule, first_roll=args.first_roll,
+                                      max_steps=args.max_steps)
+            print(json.dumps(dict(position=i, cube_decision=True, **d)), flush=True)
+            res.extend(d["rollouts"])
+    else:
+        res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
+                     luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff) or dbs1.get(args.bearoff1), cube=rule)
     dt = time.perf_counter() - t0
-    for i, r in enumerate(res):
+    for i, r in enumerate(res if not args.cube_decision else ()):
         print(json.dumps(dict(position=i, **r)), flush=True)
     games = sum(r["games"] for r in res)
-    summary = dict(summary=True, positions=len(res), games=games, unfinished=sum(r["unfinished"] for r in res),
+    summary = dict(summary=True, positions=int(positions.shape[0]), games=games, unfinished=sum(r["unfinished"] for r in res),
                    steps=ro.steps, net=args.net, player="random" if net is None else args.player, top_k=args.top_k,
                    trials=args.trials, first_roll=args.first_roll, batch=args.batch, max_steps=args.max_steps,
                    seed=args.seed, seconds=dt, games_per_s=games / dt if dt > 0 else 0.0,
@@ -740,6 +866,14 @@ def main(argv=None):
             summary.update(bearoff1=args.bearoff1, bearoff1_play=args.bearoff1_play)
         summary.update(bearoff=args.bearoff, bearoff_play=args.bearoff_play, cut_games=cut,
                        cut_share=cut / games if games else 0.0,
+                       plies_per_game=sum(r["plies_per_game"] * r["games"] for r in res) / games if games else 0.0)
+    if args.cube:
+        summary.update(cube=True, cube_net=args.cube_net, cube_double=args.cube_double, cube_pass=args.cube_pass,
+                       cube_too_good=args.cube_too_good if math.isfinite(args.cube_too_good) else None,
+                       cube_scale=args.cube_scale, cube_cap=args.cube_cap, jacoby=args.jacoby,
+                       cube_decision=args.cube_decision,
+                       pass_share=sum(r["pass_games"] for r in res) / games if games else 0.0,
+                       doubles_per_game=sum(r["doubles"] for r in res) / games if games else 0.0,
                        plies_per_game=sum(r["plies_per_game"] * r["games"] for r in res) / games if games else 0.0)
     print(json.dumps(summary), flush=True)
     return res, summary

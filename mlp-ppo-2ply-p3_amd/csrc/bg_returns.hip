@@ -288,3 +288,6 @@ extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, floa
 
 // the one-sided bearoff database: its kernels use mul_rn / add_rn / sub_rn above
 #include "bg_bearoff1.h"
+
+// the doubling cube of position rollouts: its kernels reuse bg_bearoff1.h's tally helpers
+#include "bg_cube.h"
