@@ -329,6 +329,26 @@ int bgx_two_ply_topk(bgx_engine* e, const float* vpacked_dev, int32_t hidden, fl
 int bgx_roll_luck(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float value_bias,
                   const uint8_t* lane_sel_dev, float* luck_out, float* mean_out, uint64_t* stats_host, void* stream);
 
+/* The static value of lane records (the value a truncated rollout scores a game
+ * with).  records_dev = uint8[n][64] lane records, 16-byte aligned (the engine's, or any copy);
+ * vpacked_dev the ordinary bgx_value_pack pack, every hidden with bgx_value_packed_size >= 0.
+ * For a lane with lane_sel_dev[i] != 0 (NULL = every lane):
+ *   value_out[i] = wv . relu(W1 x + b1) + bv,   x = the 198 features of the record's board with
+ *   the one-hot of the record's mover (byte 52): the x bgx_policy_act forms from the same record,
+ *   and bgx_roll_luck's v_r of a mover that cannot move,
+ * in the search kernels' fp32-equivalent (split-f16 MFMA) arithmetic; the roll bytes are not
+ * read.  A lane's value does not depend on the selection: selected entries are bit for bit
+ * those of the call with NULL.  Unselected lanes are not written; an all-zero selection is
+ * BGX_OK.  A workgroup packs the selected lanes of its chunk of 256 or 512 lanes before it
+ * evaluates them and stages the weights only once it meets a selected lane, so the cost follows
+ * the chunks that hold one; no scratch is needed.  Runs on the caller's stream as given (no
+ * engine, so no ordering of its own).  No allocation, no synchronisation, no host read:
+ * graph-capturable (the first call per device and width asks the occupancy once; make it
+ * outside a capture).  BGX_EINVAL for n <= 0, a NULL records, pack or value_out, records that
+ * are not 16-byte aligned or hidden out of range. */
+int bgx_value_lanes(const uint8_t* records_dev, int32_t n, const float* vpacked_dev, int32_t hidden,
+                    float value_bias, const uint8_t* lane_sel_dev, float* value_out, void* stream);
+
 /* ---- head-to-head arena (csrc/bg_engine.hip; bgx/arena.py) ----
  * Two players A and B play each other on the n lanes of an engine created with
  * auto_reset = 1 until every lane has finished games_per_lane games (the reference has no
@@ -686,6 +706,55 @@ int bgx_rollout_cube_flush(const uint8_t* starts_dev, const int32_t* group_dev, 
                            const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
                            bgx_cube_rule rule, const uint8_t* cube0_dev, uint8_t* cube_dev, int64_t* cube_tally_dev,
                            void* stream);
+
+/* ---- truncated position rollouts (csrc/bg_trunc.h; bgx/rollout.py; no
+ * counterpart in the reference) ----
+ * A game that has run `horizon` plies without ending stops there and is scored with a value of
+ * the position it reached.  Beside the state of bgx_rollout_begin / bgx_rollout_advance: tsel
+ * uint8[n], value float[n] (the caller's: bgx_value_lanes or bgx_roll_luck's mean_out with tsel
+ * as the lane selection, or any other source), trunc_tally int64[n_groups][7]
+ * (bgx_rollout_trunc_field), zeroed by the caller, and reset_mask_out uint8[n].  Per step:
+ * [bgx_roll_luck, bgx_rollout_luck_add,] the players' act, bgx_step, [bgx_rollout_luck_flush,]
+ * bgx_rollout_advance, trunc_sel, the value of the tsel lanes, trunc_cut, bgx_reset with the
+ * mask.  After advance a truncated game's luck sum is complete: the roll now in the record is
+ * added only at the next step.
+ * bgx_rollout_trunc_sel: tsel_out[i] = 1 when sel[i] != 0, the group is valid, the record is not
+ * game_over (byte 55) and plies[i] >= horizon; else 0.  count_inout (int64[1], may be NULL) is
+ * increased by the number of lanes set.  BGX_EINVAL for horizon < 1.
+ * bgx_rollout_trunc_cut: for a lane with tsel[i] != 0 and a valid group, v = value[i] = the
+ * equity of the record's mover (byte 52):
+ *   e = scale * v in fp32 (one product);  e = 0 for a NaN, else clamped to [-3, 3];
+ *   y = e when the record's mover is the start record's mover, else -e;
+ *   Vq = llrintf(y * 65536.0f)                                    (|Vq| <= 196608);
+ *   row group[i]: TRUNC_GAMES += 1, TRUNC_PLIES += plies[i], TRUNC_V += Vq, TRUNC_V2 += Vq * Vq;
+ *   with lane_luck (float[n], may be NULL): Lq as bgx_rollout_luck_flush defines it
+ *   (llrintf(lane_luck[i] * 65536.0f) clamped to +-2^21, 0 when not finite), TRUNC_LUCK += Lq,
+ *   TRUNC_LUCK2 += Lq * Lq, TRUNC_VLUCK += Vq * Lq (units of 2^-32; at most 2^39 each, so a row
+ *   holds 2^24 games), lane_luck[i] = 0;
+ *   games_done[i] += 1, plies[i] = 0; the lane's last game: sel[i] = 0 and active drops;
+ *   reset_mask_out[i] = 1.
+ * Every other lane gets reset_mask_out[i] = 0 and is otherwise untouched.  The caller then runs
+ * bgx_reset with the mask, which gives each truncated lane its start record again.  The sums
+ * are integers: run-to-run identical.  Plain kernels, one thread per lane, no allocation and no
+ * synchronisation: graph-capturable.  BGX_EINVAL for n <= 0, n_groups <= 0, games_per_lane < 0,
+ * a NaN scale or a NULL pointer (other than count_inout and lane_luck). */
+enum bgx_rollout_trunc_field {
+    BGX_ROLLOUT_TRUNC_GAMES = 0,      /* truncated games */
+    BGX_ROLLOUT_TRUNC_PLIES = 1,      /* their steps */
+    BGX_ROLLOUT_TRUNC_V = 2,          /* sum of Vq (2^-16 points, from the start mover's side) */
+    BGX_ROLLOUT_TRUNC_V2 = 3,         /* sum of Vq^2 (2^-32) */
+    BGX_ROLLOUT_TRUNC_LUCK = 4,       /* sum of Lq (2^-16) */
+    BGX_ROLLOUT_TRUNC_LUCK2 = 5,      /* sum of Lq^2 (2^-32) */
+    BGX_ROLLOUT_TRUNC_VLUCK = 6       /* sum of Vq * Lq (2^-32) */
+};
+int bgx_rollout_trunc_sel(const uint8_t* records_dev, const int32_t* group_dev, int32_t n, int32_t n_groups,
+                          int32_t horizon, const int32_t* plies_dev, const uint8_t* sel_dev, uint8_t* tsel_out,
+                          int64_t* count_inout_or_null, void* stream);
+int bgx_rollout_trunc_cut(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev,
+                          const uint8_t* tsel_dev, const float* value_dev, float scale, int32_t n,
+                          int32_t n_groups, int32_t games_per_lane, int32_t* games_done_dev, int32_t* plies_dev,
+                          uint8_t* sel_dev, float* lane_luck_or_null, int64_t* trunc_tally_dev,
+                          int64_t* active_dev, uint8_t* reset_mask_out, void* stream);
 
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row

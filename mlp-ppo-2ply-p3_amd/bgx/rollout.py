@@ -19,7 +19,10 @@ reaches every pure home-board race but whose win probability is an approximation
 --cube: money play with the doubling cube (bgx/cube.py): before its roll the side
 on roll may double by a threshold rule on a net's value, a passed double ends the game, and the
 result is the cubeful equity (cube.summarize_cube); --cube-decision answers "double or not,
-take or pass?" per position.
+take or pass?" per position.  --truncate N: a game that has run N plies stops there and is scored by
+a net's value head (bgx/truncate.py; DESIGN.md §14), which makes the slow players affordable;
+with --luck the dice noise of the plies played goes too (summarize_truncated_luck).  The
+estimate then carries the net's own error, which no standard error shows.
 """
 from __future__ import annotations
 
@@ -35,6 +38,8 @@ from . import _lib
 from ._lib import check
 from .arena import PLAYER_KINDS, SYNC_EVERY, TRACE_LIMIT, _stream, load_net, make_player
 from .engine import Engine, R_CUR, R_ROLL0, R_ROLL1, _ptr, validate_starts
+from .truncate import (TRUNC_FIELDS, Truncation, summarize_truncated, summarize_truncated_luck,  # noqa: F401
+                       truncate_reference)
 
 # tally int64[n_groups][8] (include/bgx.h bgx_rollout_field)
 FIELDS = ("games", "plies", "win1", "win2", "win3", "loss1", "loss2", "loss3")
@@ -327,7 +332,7 @@ class Rollout:
         self.steps = 0                  # steps of every run so far: the players' random streams go on
 
     def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
-                  trace: bool = False, luck=None, bearoff=None, cube=None, cube0=None):
+                  trace: bool = False, luck=None, bearoff=None, cube=None, cube0=None, truncate=None):
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
@@ -372,7 +377,26 @@ class Rollout:
         state before the decision), cube_mover (the side on roll there), cube_dsel (the lanes
         that may double), cube_equity (NaN off cube_dsel) and cube_mask (the passes).  Together
         with `luck` or `bearoff` it raises ValueError: the luck of a cubeful game and cubeful
-        table values do not exist.  None: nothing changes."""
+        table values do not exist.  None: nothing changes.
+
+        `truncate` (a truncate.Truncation): a game that has run truncate.plies
+        plies without ending stops there and is scored with the truncation's value of the side
+        on roll.  Per step [roll_luck, luck_add,] act, merge, step, [luck_flush,] advance,
+        trunc_sel, value, trunc_cut, reset(mask): the cut sits where the bearoff cut sits, where
+        the truncated game's luck sum is complete (the roll now in the record is added only at
+        the next step), and the masked reset gives the lane its start record again.  With a
+        sync-free player, a value head at lookahead 0 and no luck the host keeps reading the
+        active-lane count every SYNC_EVERY steps; else every step.  A further result follows
+        the trace -- with `luck`, it follows luck_tally --: trunc_tally int64[n_groups, 7]
+        (truncate.TRUNC_FIELDS), and the trace gains per step trunc uint8 (the lanes truncated),
+        trunc_value (NaN off them) and trunc_mover (the side on roll there).  Together with
+        `luck` it is supported (summarize_truncated_luck); together with `bearoff` or `cube` it
+        raises ValueError (the three-way summaries do not exist).  None: nothing changes."""
+        if truncate is not None and (bearoff is not None or cube is not None):
+            raise ValueError(f"run_lanes: truncate together with {'bearoff' if bearoff is not None else 'cube'} "
+                             "is not supported")
+        if truncate is not None and not isinstance(truncate, Truncation):
+            raise ValueError("run_lanes: truncate must be a truncate.Truncation")
         if luck is not None and bearoff is not None:
             raise ValueError("run_lanes: bearoff together with luck is not supported")
         if cube is not None and luck is not None:
@@ -418,13 +442,19 @@ class Rollout:
             luck_tally = torch.zeros(P, len(LUCK_FIELDS), dtype=torch.int64, device=dev)
             lbuf = torch.full((self.B,), float("nan"), dtype=torch.float32, device=dev)
             self.lane_luck.zero_()
+        if truncate is not None:
+            trunc_tally = torch.zeros(P, len(TRUNC_FIELDS), dtype=torch.int64, device=dev)
+            tsel, tmask = (torch.zeros(self.B, dtype=torch.uint8, device=dev) for _ in range(2))
+            tbuf, tscratch = (torch.full((self.B,), float("nan"), dtype=torch.float32, device=dev) for _ in range(2))
         tr = None
         if trace:
             tr = {n: torch.zeros(max_steps, self.B, dtype=dt, device=dev)
                   for n, dt in (("mover", torch.uint8), ("action", torch.int32), ("done", torch.uint8),
                                 ("info", torch.int32)) + ((("luck", torch.float32),) if luck is not None else ())
                   + ((("cube", torch.uint8), ("cube_mover", torch.uint8), ("cube_dsel", torch.uint8),
-                      ("cube_equity", torch.float32), ("cube_mask", torch.uint8)) if cube is not None else ())}
+                      ("cube_equity", torch.float32), ("cube_mask", torch.uint8)) if cube is not None else ())
+                  + ((("trunc", torch.uint8), ("trunc_value", torch.float32), ("trunc_mover", torch.uint8))
+                     if truncate is not None else ())}
             rec = torch.empty(self.B, 64, dtype=torch.uint8, device=dev)
         if bearoff is not None:
             if bearoff.device != dev:
@@ -449,7 +479,8 @@ class Rollout:
 
             cut(None)
             cut_begin = (mask.clone(), rec.clone()) if trace else None
-        every = SYNC_EVERY if getattr(player, "sync_free", False) and luck is None and cube is None else 1
+        every = (SYNC_EVERY if getattr(player, "sync_free", False) and luck is None and cube is None
+                 and (truncate is None or truncate.sync_free) else 1)
         steps = 0
         active = int(self.active.item())
         while active > 0 and steps < max_steps:
@@ -503,6 +534,20 @@ class Rollout:
                 tr["info"][steps] = info
             if bearoff is not None:
                 cut(steps)
+            if truncate is not None:
+                check(L.bgx_rollout_trunc_sel(recs, _ptr(grp), self.B, P, truncate.plies, _ptr(self.plies),
+                                              _ptr(self.sel), _ptr(tsel), None, _stream(dev)), "bgx_rollout_trunc_sel")
+                tv = truncate.equity(eng, tsel, tscratch, tbuf)
+                if trace:
+                    eng.records(out=rec)
+                    tr["trunc"][steps] = tsel
+                    tr["trunc_value"][steps] = torch.where(tsel != 0, tv, float("nan"))
+                    tr["trunc_mover"][steps] = rec[:, R_CUR]
+                check(L.bgx_rollout_trunc_cut(recs, _ptr(starts), _ptr(grp), _ptr(tsel), _ptr(tv), truncate.scale,
+                                              self.B, P, G, _ptr(self.games_done), _ptr(self.plies), _ptr(self.sel),
+                                              _ptr(self.lane_luck) if luck is not None else None, _ptr(trunc_tally),
+                                              _ptr(self.active), _ptr(tmask), _stream(dev)), "bgx_rollout_trunc_cut")
+                eng.reset(lane_mask=tmask, want_obs=False)
             steps += 1
             self.steps += 1
             if steps % every == 0 or steps == max_steps:
@@ -518,10 +563,14 @@ class Rollout:
             return tally, unfinished, tr, cut_tally
         if cube is not None:
             return tally, unfinished, tr, cube_tally
+        if truncate is not None:
+            return ((tally, unfinished, tr, trunc_tally) if luck is None
+                    else (tally, unfinished, tr, luck_tally, trunc_tally))
         return (tally, unfinished, tr) if luck is None else (tally, unfinished, tr, luck_tally)
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
-            trace: bool = False, luck=None, luck_scale="fit", bearoff=None, cube=None, cube_start=(0, 0)):
+            trace: bool = False, luck=None, luck_scale="fit", bearoff=None, cube=None, cube_start=(0, 0),
+            truncate=None):
         """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
         bytes come from the layout) `trials` times with `player` (any arena player object)
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
@@ -537,7 +586,13 @@ class Rollout:
         with `luck` (ValueError).  `cube` (a cube.CubeRule): money play with the
         doubling cube (run_lanes); every game starts with the cube `cube_start` = (k, owner),
         owner 0 centred, 1 PLAYER1, 2 PLAYER2, or one such pair per position; the results are
-        cube.summarize_cube's.  Not together with `luck` or `bearoff` (ValueError)."""
+        cube.summarize_cube's.  Not together with `luck` or `bearoff` (ValueError).  `truncate` (a
+        truncate.Truncation): games stop at its horizon and are scored with its
+        value (run_lanes); the results are summarize_truncated's, with `luck` those of
+        summarize_truncated_luck.  Not together with `bearoff` or `cube` (ValueError)."""
+        if truncate is not None and (bearoff is not None or cube is not None):
+            raise ValueError(f"run: truncate together with {'bearoff' if bearoff is not None else 'cube'} is not "
+                             "supported")
         if luck is not None and bearoff is not None:
             raise ValueError("run: bearoff together with luck is not supported")
         if cube is not None and (luck is not None or bearoff is not None):
@@ -545,7 +600,7 @@ class Rollout:
         pos = _records(positions)
         P = pos.shape[0]
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
-        total = unfinished = tr = ltotal = None
+        total = unfinished = tr = ltotal = ttotal = None
         if cube is not None:
             from .cube import pack, summarize_cube
             cs = np.asarray(cube_start, np.int64)
@@ -558,8 +613,11 @@ class Rollout:
             starts[:, R_ROLL0:R_ROLL1 + 1] = torch.from_numpy(roll[k])
             out = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck,
                                  bearoff=bearoff, cube=cube,
-                                 cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None)
+                                 cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None,
+                                 truncate=truncate)
             tally, unf, tr = out[:3]
+            if truncate is not None:
+                ttotal = out[-1] if ttotal is None else ttotal + out[-1]
             if luck is not None or bearoff is not None or cube is not None:
                 ltotal = out[3] if ltotal is None else ltotal + out[3]
             total = tally if total is None else total + tally
@@ -568,7 +626,14 @@ class Rollout:
                 tr.update(group=grp, starts=starts, games_per_lane=G)
         self.eng.set_starts(None)
         rows, unf = total.cpu().tolist(), unfinished.cpu().tolist()
-        if luck is not None:
+        if truncate is not None:
+            trows = ttotal.cpu().tolist()
+            if luck is not None:
+                lrows = ltotal.cpu().tolist()
+                res = [summarize_truncated_luck(rows[p], lrows[p], trows[p], luck_scale, unf[p]) for p in range(P)]
+            else:
+                res = [summarize_truncated(rows[p], trows[p], unf[p]) for p in range(P)]
+        elif luck is not None:
             lrows = ltotal.cpu().tolist()
             res = [summarize_luck(rows[p], lrows[p], luck_scale, unf[p]) for p in range(P)]
         elif bearoff is not None:
@@ -611,7 +676,7 @@ def decode_move(v: int):
 
 
 def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str = "stratified",
-                  max_steps: int = 4000, luck=None, luck_scale="fit") -> list:
+                  max_steps: int = 4000, luck=None, luck_scale="fit", truncate=None) -> list:
     """A decision: `record` (uint8[64]) holds the board, the mover and the roll to play.  Every
     legal move's afterstate is rolled out with the opponent on roll and the move's equity is
     minus that rollout's; moves that reach the same afterstate share one rollout.  A move
@@ -620,7 +685,8 @@ def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str
     equity_stderr, games, exact.  No legal move: one entry with move None (the pass).
     `luck` / `luck_scale` (Rollout.run): luck-adjusted rollouts; every entry also has
     equity_luck, equity_luck_stderr, luck_scale and variance_ratio (an exact move: its score,
-    0, 0 and 1), and the order is by equity_luck."""
+    0, 0 and 1), and the order is by equity_luck.  `truncate` (Rollout.run): truncated rollouts;
+    every rolled-out entry also has truncated_share (an exact move: 0)."""
     rec = torch.as_tensor(record).reshape(-1)
     if rec.numel() != 64 or rec.dtype != torch.uint8:
         raise ValueError("rollout_moves: record must be 64 bytes (uint8)")
@@ -649,7 +715,7 @@ def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str
         pos[:, :52] = uniq.view(np.uint8)
         pos[:, R_CUR] = 1 - mover
         res = rollout.run(player, torch.from_numpy(pos), trials, first_roll=first_roll, max_steps=max_steps,
-                          luck=luck, luck_scale=luck_scale)
+                          luck=luck, luck_scale=luck_scale, truncate=truncate)
         for i, u in zip(open_idx, np.asarray(inverse).reshape(-1)):
             results[i] = res[int(u)]
     out = []
@@ -660,6 +726,8 @@ def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str
             if luck is not None:
                 out[-1].update(equity_luck=float(scores[i]), equity_luck_stderr=0.0, luck_scale=0.0,
                                variance_ratio=1.0)
+            if truncate is not None:
+                out[-1].update(truncated_share=0.0)
         else:
             r = results[i]
             out.append(dict(move=m, submoves=decode_move(m) if m is not None else [], equity=-r["equity"],
@@ -668,6 +736,8 @@ def rollout_moves(rollout: Rollout, player, record, trials: int, first_roll: str
             if luck is not None:
                 out[-1].update(equity_luck=-r["equity_luck"], equity_luck_stderr=r["equity_luck_stderr"],
                                luck_scale=r["luck_scale"], variance_ratio=r["variance_ratio"])
+            if truncate is not None:
+                out[-1].update(truncated_share=r["truncated_share"])
     out.sort(key=lambda d: -d["equity_luck" if luck is not None else "equity"])
     return out
 
@@ -713,7 +783,8 @@ def _luck_scale(text: str):
 
 class _Parser(argparse.ArgumentParser):
     """--top-k is an error for any player but a 2ply one with weights; --luck and --cube need
-    weights; --cube goes with neither --luck nor a bearoff cut."""
+    weights; --cube goes with neither --luck nor a bearoff cut; --truncate needs a net and goes
+    with neither a bearoff cut nor --cube."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -748,6 +819,20 @@ class _Parser(argparse.ArgumentParser):
             for name in ("cube_double", "cube_pass", "cube_too_good", "cube_scale"):
                 if math.isnan(getattr(ns, name)):
                     self.error(f"--{name.replace('_', '-')} must be a number")
+        if ns.truncate is None:
+            if ns.truncate_net is not None or ns.truncate_lookahead != 0 or ns.truncate_scale != 1.0:
+                self.error("--truncate-net, --truncate-scale and --truncate-lookahead need --truncate")
+        else:
+            if ns.truncate < 1:
+                self.error("--truncate takes a number of plies >= 1")
+            if ns.net == "random" and ns.truncate_net is None:
+                self.error("--truncate needs --net with weights or --truncate-net (the games are scored by a "
+                           "net's value head)")
+            for name in ("bearoff", "bearoff1", "cube"):
+                if getattr(ns, name) not in (None, False):
+                    self.error(f"--truncate and --{name} cannot be combined")
+            if math.isnan(ns.truncate_scale):
+                self.error("--truncate-scale must be a number")
         if ns.trials < 1 or ns.batch < 1:
             self.error("--trials and --batch must be >= 1")
         return ns
@@ -795,6 +880,16 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cube-scale", type=float, default=1.0, help="points per unit of the net's value")
     ap.add_argument("--cube-cap", type=int, default=6, help="no double once the cube shows 2^CAP (0..10)")
     ap.add_argument("--jacoby", action="store_true", help="gammons count only after a double")
+    ap.add_argument("--truncate", type=int, default=None, metavar="N",
+                    help="stop a game after N plies (>= 1) and score it with a net's value head; with --luck the "
+                         "luck-adjusted estimate covers the truncated games too; not with --bearoff, --bearoff1 "
+                         "or --cube")
+    ap.add_argument("--truncate-scale", type=float, default=1.0, help="points per unit of the net's value")
+    ap.add_argument("--truncate-lookahead", type=int, default=0, choices=(0, 1),
+                    help="0: the value head on the position itself (sync-free); 1: its mean best 1-ply value "
+                         "over the 21 rolls")
+    ap.add_argument("--truncate-net", default=None, metavar="PATH",
+                    help="the state_dict whose value head scores the truncated games (default: the player's net)")
     ap.add_argument("--cube-decision", action="store_true",
                     help="per position: no double / double, take / double, pass for the side on roll with a "
                          "centred cube, and the verdict")
@@ -838,6 +933,13 @@ def main(argv=None):
                         too_good_at=args.cube_too_good, cap=args.cube_cap, jacoby=args.jacoby)
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
+    trunc = None
+    if args.truncate is not None:
+        from .search import ValueHead
+        trunc = Truncation(ValueHead(net if args.truncate_net is None else load_net(args.truncate_net, dev)),
+                           args.truncate, scale=args.truncate_scale, lookahead=args.truncate_lookahead)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
     if args.cube_decision:
         # one line per position: the three equities and the verdict; the summary counts both rollouts' games
         res = []
@@ -848,7 +950,8 @@ def main(argv=None):
             res.extend(d["rollouts"])
     else:
         res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
-                     luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff) or dbs1.get(args.bearoff1), cube=rule)
+                     luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff) or dbs1.get(args.bearoff1), cube=rule,
+                     truncate=trunc)
     dt = time.perf_counter() - t0
     for i, r in enumerate(res if not args.cube_decision else ()):
         print(json.dumps(dict(position=i, **r)), flush=True)
@@ -874,6 +977,12 @@ def main(argv=None):
                        cube_decision=args.cube_decision,
                        pass_share=sum(r["pass_games"] for r in res) / games if games else 0.0,
                        doubles_per_game=sum(r["doubles"] for r in res) / games if games else 0.0,
+                       plies_per_game=sum(r["plies_per_game"] * r["games"] for r in res) / games if games else 0.0)
+    if trunc is not None:
+        tg = sum(r["truncated_games"] for r in res)
+        summary.update(truncate=args.truncate, truncate_scale=args.truncate_scale,
+                       truncate_lookahead=args.truncate_lookahead, truncate_net=args.truncate_net,
+                       truncated_games=tg, truncated_share=tg / games if games else 0.0,
                        plies_per_game=sum(r["plies_per_game"] * r["games"] for r in res) / games if games else 0.0)
     print(json.dumps(summary), flush=True)
     return res, summary

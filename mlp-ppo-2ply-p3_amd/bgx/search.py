@@ -182,6 +182,34 @@ def roll_luck(eng: Engine, vh: ValueHead, sel: torch.Tensor | None = None, out=N
     return luck, mean, {"leaves": int(stats[0]), "jobs": int(stats[1]), "rows": int(stats[2])}
 
 
+def value_lanes(records, vh: ValueHead, sel: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The static value V(enc(X, m)) of lane records under `vh` (bgx_value_lanes):
+    the board and the mover (byte 52) of each record, the value head's own output for them --
+    what PolicyNet.act returns as its value.  `records`: an Engine (its lane records, read in
+    place) or a contiguous uint8[n, 64] tensor on the head's device.  `sel` (uint8[n] there):
+    only records with sel != 0 are evaluated and written (a stretch of lanes without a
+    selected one costs next to nothing); `out` (float32[n]) keeps the other entries as they
+    were, else they are NaN.  Sync-free and graph-capturable."""
+    L = _lib.load()
+    if isinstance(records, Engine):
+        n, dev, rp = records.batch, records.device, ctypes.c_void_p(records.lanes_ptr())
+    else:
+        if (not isinstance(records, torch.Tensor) or records.dtype != torch.uint8 or records.dim() != 2
+                or records.shape[1] != 64 or not records.is_contiguous() or not records.is_cuda):
+            raise ValueError("value_lanes: records must be an Engine or a contiguous uint8[n, 64] tensor on the GPU")
+        n, dev, rp = records.shape[0], records.device, _ptr(records)
+    if sel is not None and (not isinstance(sel, torch.Tensor) or sel.dtype != torch.uint8 or sel.device != dev
+                            or not sel.is_contiguous() or sel.numel() != n):
+        raise ValueError("value_lanes: sel must be a contiguous uint8[n] tensor on the records' device")
+    if out is None:
+        out = torch.full((n,), float("nan"), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or out.numel() != n:
+        raise ValueError("value_lanes: out must be a contiguous float32[n] tensor on the records' device")
+    check(L.bgx_value_lanes(rp, n, _ptr(vh.packed), vh.hidden, vh.bias, _ptr(sel), _ptr(out), _stream(dev)),
+          "bgx_value_lanes")
+    return out
+
+
 def two_ply_timings(eng: Engine):
     """(enumeration ms, evaluation ms) of the last two_ply call's first round,
     timed with HIP events on the caller's stream."""

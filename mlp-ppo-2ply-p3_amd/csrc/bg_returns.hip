@@ -291,3 +291,6 @@ extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, floa
 
 // the doubling cube of position rollouts: its kernels reuse bg_bearoff1.h's tally helpers
 #include "bg_cube.h"
+
+// truncated position rollouts: the same helpers again
+#include "bg_trunc.h"

@@ -2303,3 +2303,135 @@ int bgx_two_ply_timings(bgx_engine* e, float* ms2) {
 }
 
 }  // extern "C"
+
+// ---- the static value of lane records (bgx_value_lanes) ----
+// V(enc(X, m)) of the record's own board X with the one-hot of its mover m (byte 52): the leaf
+// k_luck_rows' no-move case stands for, built from the record itself.  One kernel on the
+// caller's stream, no engine, no workspace: a workgroup of W waves takes chunks of 64 W lanes,
+// packs the chunk's selected lanes in LDS (wave ballots and a W-entry prefix: lane order, so
+// the same from run to run) and evaluates ceil(selected / 64) tiles of them as k_eval_rows
+// does.  A chunk without a selected lane costs its 64 W selection bytes, and a workgroup stages
+// the weights only once it meets a selected lane: the cost follows the chunks that hold one.
+namespace {
+
+// the nibbles of four counts held as the bytes of w
+__device__ __forceinline__ uint32_t nib4(uint32_t w) {
+    return (w & 15u) | ((w >> 4) & 0xF0u) | ((w >> 8) & 0xF00u) | ((w >> 12) & 0xF000u);
+}
+__device__ __forceinline__ uint32_t nib8(uint32_t a, uint32_t b) { return nib4(a) | (nib4(b) << 16); }
+
+// The leaf of record i: both sides from the record, the "root mover" (whose one-hot feat16
+// forms, 1 - q) the record's mover.
+__device__ __forceinline__ Leaf record_leaf(const uint8_t* recs, int i, bool in) {
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    const uint4* r = (const uint4*)recs + (size_t)(in ? i : 0) * 4;
+    const uint4 a = in ? r[0] : z, b = in ? r[1] : z, c = in ? r[2] : z, d = in ? r[3] : z;
+    Leaf L;
+    L.lo[0] = (uint64_t)nib8(a.x, a.y) | ((uint64_t)nib8(a.z, a.w) << 32);
+    L.hi[0] = nib8(b.x, b.y);
+    L.lo[1] = (uint64_t)nib8(b.z, b.w) | ((uint64_t)nib8(c.x, c.y) << 32);
+    L.hi[1] = nib8(c.z, c.w);
+    L.bar[0] = d.x & 15u;          L.bar[1] = (d.x >> 8) & 15u;
+    L.off[0] = (d.x >> 16) & 15u;  L.off[1] = (d.x >> 24) & 15u;
+    L.q = 1 - (int)(d.y & 1u);
+    L.job = -1;
+    L.valid = in;
+    L.hits = 0u;
+    L.row = 0;
+    return L;
+}
+
+struct ValueLanesArgs {
+    const uint8_t* recs;
+    const uint8_t* sel;         // null: every lane
+    int n;
+    float* out;
+    const uint4* w1q;
+    const float* wvq;
+    float bv;
+};
+
+template <int NT>
+__global__ __launch_bounds__(64 * EvalShape<NT>::kWaves) void k_value_lanes(ValueLanesArgs E) {
+    constexpr int W = EvalShape<NT>::kWaves, C = 64 * W;
+    __shared__ uint4 wq[kKB * slices(NT) * 64];
+    __shared__ float wvs[slices(NT) * 8 * 64];
+    __shared__ int32_t list[C];
+    __shared__ int32_t wcnt[W];
+    const int l = lane_id(), h = l >> 5, c = l & 31, w = threadIdx.x >> 6;
+    const long long chunks = ((long long)E.n + C - 1) / C;
+    bool staged = false;
+    for (long long ch = blockIdx.x; ch < chunks; ch += gridDim.x) {
+        const long long i = ch * C + threadIdx.x;
+        const bool on = i < E.n && (!E.sel || E.sel[i] != 0);
+        const uint64_t b = __ballot(on);
+        if (l == 0) wcnt[w] = __popcll(b);
+        __syncthreads();
+        int off = 0, total = 0;                            // total: the same in every thread
+        #pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const int v = wcnt[k];
+            off += k < w ? v : 0;
+            total += v;
+        }
+        if (on) list[off + __popcll(b & ((1ull << l) - 1ull))] = (int)i;
+        if (total > 0 && !staged) {
+            stage_weights<NT>(wq, wvs, E.w1q, E.wvq);      // ends with the barrier the list needs
+            staged = true;
+        } else {
+            __syncthreads();
+        }
+        if (w * 64 < total) {                              // this wave's tile holds a row
+            Leaf L[2];
+            int lane[2];
+            #pragma unroll
+            for (int n = 0; n < 2; ++n) {
+                const int r = w * 64 + 32 * n + c;
+                lane[n] = r < total ? list[r] : -1;
+                L[n] = record_leaf(E.recs, lane[n], lane[n] >= 0);
+            }
+            int z = 0;
+            __asm__ volatile("" : "+s"(z));
+            float v[2];
+            eval_leaves<NT>(wq, wvs, L, z, E.bv, v);
+            #pragma unroll
+            for (int n = 0; n < 2; ++n)
+                if (h == 0 && lane[n] >= 0) E.out[lane[n]] = v[n];
+        }
+        __syncthreads();                                   // list and wcnt are written again
+    }
+}
+
+typedef void (*ValueLanesFn)(ValueLanesArgs);
+#define BGX_BY_NT(K) {K<1>, K<2>, K<3>, K<4>, K<5>, K<6>, K<7>, K<8>}
+const ValueLanesFn kValueLanes[8] = BGX_BY_NT(k_value_lanes);
+#undef BGX_BY_NT
+
+}  // namespace
+
+extern "C" int bgx_value_lanes(const uint8_t* records_dev, int32_t n, const float* vpacked_dev, int32_t hidden,
+                               float value_bias, const uint8_t* lane_sel_dev, float* value_out, void* stream) {
+    if (!records_dev || n <= 0 || !vpacked_dev || !value_out || bgx_value_packed_size(hidden) < 0 ||
+        ((uintptr_t)records_dev & 15) != 0)
+        return BGX_EINVAL;
+    const int NT = value_tiles16(hidden), ti = tile_index(NT);
+    const int threads = kTileKernels.threads[ti];
+    // one workgroup per chunk, at most what the device holds at once (asked once per device and
+    // width: a captured call makes no query)
+    static int resident[16][8];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+    const ValueLanesFn k = kValueLanes[ti];
+    if (resident[dev][ti] == 0) {
+        int cus = 0, occ = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, threads, 0) != hipSuccess || occ <= 0) occ = 1;
+        resident[dev][ti] = cus * occ;
+    }
+    const long long need = ((long long)n + threads - 1) / threads, cap = resident[dev][ti];
+    const ValueLanesArgs E{records_dev, lane_sel_dev, n, value_out, (const uint4*)(vpacked_dev + 4),
+                           vpacked_dev + 4 + kKB * slices(NT) * 64 * 4, value_bias};
+    hipLaunchKernelGGL(k, dim3((unsigned)(need < cap ? need : cap)), dim3(threads), 0, (hipStream_t)stream, E);
+    BGX_CK_LAUNCH();
+    return BGX_OK;
+}
