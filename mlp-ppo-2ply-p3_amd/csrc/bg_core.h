@@ -670,8 +670,9 @@ struct Gen {
         const int l = threadIdx.x & 63;
         const bool up = l >= 32;
         const int bit = l & 31, da = up ? lo : hi, db = up ? hi : lo;
-        const Kids kh = gen(s0, hi, pl, blocked), kl = gen(s0, lo, pl, blocked);
-        const Kids k1{up ? kl.bits : kh.bits, up ? kl.extra : kh.extra};
+        // one list per lane half with the half's own die: what depends only on s0 (bar,
+        // all-home and farthest-checker tests) stays wave-uniform, the rest is per-lane
+        const Kids k1 = gen(s0, da, pl, blocked);
         const bool a1 = (k1.bits >> bit) & 1u;
         Node t1;
         uint32_t e1 = 0, q2 = 0;
@@ -986,10 +987,13 @@ __device__ __forceinline__ Node node_from_bytes(int bv, int pl, uint32_t& blocke
     const uint32_t own_bar = (uint32_t)__builtin_amdgcn_readlane(bv, 48 + pl);
     const uint32_t own_off = (uint32_t)__builtin_amdgcn_readlane(bv, 50 + pl);
     s.k3 = (own_bar & 15u) | ((own_off & 15u) << 4);
-    int nh = 0;
-    if (pl == 0) { for (int q = 18; q < 24; ++q) nh += (int)((s.hi >> (4 * (q - 16))) & 15u); }
-    else { for (int q = 0; q < 6; ++q) nh += (int)((s.lo >> (4 * q)) & 15u); }
-    s.n_home = nh;
+    // home-board sum on the lanes: after the reduction lane 0 holds the nibbles of points
+    // 0..7 and lane 16 those of 16..23; the six home nibbles (PLAYER1 18..23, PLAYER2 0..5)
+    // are added as three byte pairs (each <= 30, the sum <= 15) and one lane is read
+    const uint32_t h = pl == 0 ? w >> 8 : w & 0xFFFFFFu;
+    const uint32_t h2 = (h & 0x0F0F0Fu) + ((h >> 4) & 0x0F0F0Fu);
+    const uint32_t nh = opaque(h2 + (h2 >> 8) + (h2 >> 16)) & 0xFFu;
+    s.n_home = __builtin_amdgcn_readlane((int)nh, pl == 0 ? 16 : 0);
     return s;
 }
 

@@ -128,18 +128,22 @@ struct Rng {
         return w == 0 ? blk0 : w == 1 ? blk1 : w == 2 ? blk2 : blk3;
     }
 
+    // PHILOX_ONLY: the caller's stream is known to be Philox at compile time (the MT19937
+    // code is not instantiated)
+    template <bool PHILOX_ONLY = false>
     __device__ int die() {
         used = true;
         for (;;) {
-            const uint32_t x = (mode == BGX_DICE_PHILOX ? next_philox() : next_mt()) & 7u;
+            const uint32_t x = (PHILOX_ONLY || mode == BGX_DICE_PHILOX ? next_philox() : next_mt()) & 7u;
             if (x <= 5u) return (int)x + 1;
         }
     }
 
     // write the per-lane state back
+    template <bool PHILOX_ONLY = false>
     __device__ void finish(uint64_t* ctr_out) {
         if (!used) return;
-        if (mode == BGX_DICE_PHILOX) {
+        if (PHILOX_ONLY || mode == BGX_DICE_PHILOX) {
             if (lane_id() == 0) *ctr_out = ctr;
             return;
         }
@@ -263,13 +267,18 @@ __device__ __forceinline__ int run_movegen(int bv, int pl, int r0, int r1, uint6
 // Reset / dice part of advance_lane (reset: backgammon_env.py:78-113; pass/turn:
 // :183-188 roll_dice).  Returns false when the lane needs nothing this step.
 // mt_scratch: 624 words of LDS for the MT19937 twist (MT_LANE mode only).
+// DICE: the engine's dice mode when the caller knows it at compile time (the Philox
+// instantiations of the split launch carry no MT19937 or shared-dice code), -1 = A.dice_mode.
+template <int DICE = -1>
 __device__ __forceinline__ bool roll_lane(int& bv, int gi, const Args& A, uint32_t* mt_scratch, uint64_t* ctr_io,
                                           int& r0, int& r1) {
     const int need = rd(bv, R_NEED);
     if (need == NEED_NONE) return false;
+    constexpr bool kPhilox = DICE == BGX_DICE_PHILOX;
+    const int dice_mode = DICE >= 0 ? DICE : A.dice_mode;
     Rng rng;
     bool cached = false;
-    if (A.dice_mode == BGX_DICE_PHILOX) {
+    if (dice_mode == BGX_DICE_PHILOX) {
         const uint32_t cache = (uint32_t)(*ctr_io >> 48);
         const uint64_t c = *ctr_io & kCtrMask;
         cached = need != NEED_RESET && (cache & 0x8000u) != 0u;     // the roll predicted last step
@@ -280,7 +289,7 @@ __device__ __forceinline__ bool roll_lane(int& bv, int gi, const Args& A, uint32
             if (lane_id() == 0) A.ctr[gi] = rng.ctr;
         }
     }
-    else if (A.dice_mode == BGX_DICE_MT_LANE) rng.init_mt(A.mt + (size_t)gi * kMtWords, mt_scratch);
+    else if (dice_mode == BGX_DICE_MT_LANE) rng.init_mt(A.mt + (size_t)gi * kMtWords, mt_scratch);
     if (cached) {
     } else if (need == NEED_RESET) {
         if (rd(bv, R_MATCH)) { bv = wr(bv, R_S0, 0); bv = wr(bv, R_S1, 0); bv = wr(bv, R_MATCH, 0); }
@@ -294,30 +303,30 @@ __device__ __forceinline__ bool roll_lane(int& bv, int gi, const Args& A, uint32
             if (lane_id() < 52) bv = sv;
             starter = rd(sv, R_CUR);
             r0 = rd(sv, R_ROLL0); r1 = rd(sv, R_ROLL1);
-            if (r0 == 0) { r0 = rng.die(); r1 = rng.die(); }
+            if (r0 == 0) { r0 = rng.die<kPhilox>(); r1 = rng.die<kPhilox>(); }
         } else {
             if (lane_id() < 52) bv = initial_byte(lane_id());
-            if (A.dice_mode == BGX_DICE_MT_SHARED) {
+            if (dice_mode == BGX_DICE_MT_SHARED) {
                 const uint8_t* sr = A.shared_rolls + (size_t)gi * 4;
                 r0 = (int)ufl(sr[0]); r1 = (int)ufl(sr[1]); starter = (int)ufl(sr[2]);
             } else {
                 int a, b;
-                do { a = rng.die(); b = rng.die(); } while (a == b);
+                do { a = rng.die<kPhilox>(); b = rng.die<kPhilox>(); } while (a == b);
                 starter = a < b ? 1 : 0;
-                do { r0 = rng.die(); r1 = rng.die(); } while (r0 == r1);
+                do { r0 = rng.die<kPhilox>(); r1 = rng.die<kPhilox>(); } while (r0 == r1);
             }
         }
         bv = wr(bv, R_CUR, starter);
     } else {
-        if (A.dice_mode == BGX_DICE_MT_SHARED) {
+        if (dice_mode == BGX_DICE_MT_SHARED) {
             const uint8_t* sr = A.shared_rolls + (size_t)gi * 4;
             r0 = (int)ufl(sr[0]); r1 = (int)ufl(sr[1]);
         } else {
-            r0 = rng.die(); r1 = rng.die();
+            r0 = rng.die<kPhilox>(); r1 = rng.die<kPhilox>();
         }
     }
-    rng.finish(A.ctr + gi);
-    if (A.dice_mode == BGX_DICE_PHILOX) *ctr_io = rng.ctr;
+    rng.finish<kPhilox>(A.ctr + gi);
+    if (dice_mode == BGX_DICE_PHILOX) *ctr_io = rng.ctr;
     bv = wr(bv, R_ROLL0, r0);
     bv = wr(bv, R_ROLL1, r1);
     return true;
@@ -360,11 +369,11 @@ __device__ __forceinline__ int defer_lane(int bv, int gi, const Args& A) {
 // Roll + movegen for one lane according to its `need` byte.  NO_DOUBLES (the
 // light launch of the split dispatch): a doubles roll goes to the overflow tiers,
 // so this instantiation carries only the non-doubles enumeration (registers).
-template <int LOG, int MEMO_KIND = 0, bool NO_DOUBLES = false>
+template <int LOG, int MEMO_KIND = 0, bool NO_DOUBLES = false, int DICE = -1>
 __device__ __forceinline__ int advance_lane(int bv, int gi, const Args& A, uint4* lds_tab, uint4* lds_memo,
                                             uint64_t* ctr_io) {
     int r0, r1;
-    if (!roll_lane(bv, gi, A, (uint32_t*)lds_tab, ctr_io, r0, r1)) return bv;
+    if (!roll_lane<DICE>(bv, gi, A, (uint32_t*)lds_tab, ctr_io, r0, r1)) return bv;
     if (NO_DOUBLES && r0 == r1) return defer_lane(bv, gi, A);
     return movegen_lane<LOG, MEMO_KIND, NO_DOUBLES>(bv, gi, A, r0, r1, lds_tab, lds_memo);
 }
@@ -377,6 +386,40 @@ __device__ __forceinline__ void write_obs(int bv, float* obs_row) {
         const float v = feature_at(bv, f < 198 ? f : 197, cur);
         if (f < 198) obs_row[f] = v;
     }
+}
+
+// The chosen move (four 16-bit sub-moves src | dst << 5 | hit << 10 | valid << 15, up to
+// the first without the valid bit) applied to the record on the lanes: lane l returns its
+// own new byte.  move_checker (immutable_board.py:42-89) changes only counts, so each
+// lane sums what the sub-moves do to its byte -- the mover's point p loses one checker per
+// sub-move leaving p and gains one per sub-move landing on it, the mover's bar / off bytes
+// count the bar entries / bear-offs, an opponent's point loses its blot when a sub-move
+// hits it, and the opponent's bar gains the number of hit points.  The decode runs on the
+// vector pipe too (the move is held in VGPRs): nothing here touches the scalar unit, where
+// the same work as a Node (node_from_bytes, apply() per sub-move, bytes_from_node) was a
+// dependent chain of ~40 scalar and branch instructions per sub-move.
+__device__ __forceinline__ int apply_move_bytes(int bv, uint32_t mlo, uint32_t mhi, int pl) {
+    mlo = opaque(mlo); mhi = opaque(mhi);
+    const int l = lane_id();
+    const uint32_t q = (uint32_t)(l - pl * 24);             // < 24: the mover's point q
+    const uint32_t o = (uint32_t)(l - (24 - pl * 24));      // < 24: the opponent's point o
+    constexpr uint32_t kNone = 32u;                         // no 5-bit field equals it
+    const uint32_t my_src = q < 24u ? q : (l == 48 + pl ? (uint32_t)kBar : kNone);
+    const uint32_t my_dst = q < 24u ? q : (l == 50 + pl ? (uint32_t)kOff : kNone);
+    uint32_t ok = 1u, hits = 0u;
+    int delta = 0;
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const uint32_t e = (i < 2 ? mlo : mhi) >> (16 * (i & 1));
+        ok &= e >> 15;
+        const uint32_t src = e & 31u, dst = (e >> 5) & 31u;
+        const int d = (int)(dst == my_dst) - (int)(src == my_src);
+        delta += ok ? d : 0;
+        hits |= (ok & (e >> 10)) << dst;                    // a hit's dst is a point (< 24)
+    }
+    if (o < 24u) delta -= (int)((hits >> o) & 1u);
+    if (l == 49 - pl) delta += __popc(hits);
+    return bv + delta;
 }
 
 // backgammon_env.py:115-191 up to (not including) roll/update_legal_moves.
@@ -400,18 +443,7 @@ __device__ __forceinline__ int apply_lane(int bv, int gi, int action, const Args
                 rew = -1.0f; kind = 2;
             } else {                                      // :152-188
                 const uint64_t mv = A.moves[(size_t)gi * A.max_moves + a];
-                const uint32_t mlo = ufl((uint32_t)mv), mhi = ufl((uint32_t)(mv >> 32));
-                const uint64_t m = (uint64_t)mlo | ((uint64_t)mhi << 32);
-                uint32_t blocked;
-                Node s = node_from_bytes(bv, mover, blocked);
-                for (int i = 0; i < 4; ++i) {
-                    const uint32_t e = (uint32_t)(m >> (16 * i)) & 0xFFFFu;
-                    if (!(e & 0x8000u)) break;
-                    Sub sm; sm.src = (int)(e & 31u); sm.dst = (int)((e >> 5) & 31u); sm.hit = (int)((e >> 10) & 1u);
-                    sm.enc = e;
-                    s = apply(s, sm, mover);
-                }
-                bv = bytes_from_node(bv, s, mover);
+                bv = apply_move_bytes(bv, (uint32_t)mv, (uint32_t)(mv >> 32), mover);
                 if (rd(bv, 50 + mover) == 15) {            // win (:156-182)
                     const int opp = 1 - mover;
                     const bool opp_off0 = rd(bv, 50 + opp) == 0;

@@ -39,17 +39,18 @@ using namespace bg;
 // PHASE 0: apply + advance fused (per-lane dice); 1: apply only; 2: advance only.
 // One lane's step: apply (PHASE 0/1), roll + movegen (PHASE 0/2), record, the
 // next dispatch class's pre-class byte (the order pass resolves it).
-template <int PHASE, int LOG, int MEMO, bool NO_DOUBLES = false>
+// DICE: the dice mode as a compile-time constant, or -1 = A.dice_mode (roll_lane).
+template <int PHASE, int LOG, int MEMO, bool NO_DOUBLES = false, int DICE = -1>
 __device__ __forceinline__ void step_lane(const Args& A, int gi, uint4* tab, uint4* memo, const int32_t* actions,
                                           float* obs, float* reward, uint8_t* done, int32_t* info) {
     const uint64_t t0 = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     // issue the independent loads together (record, action, dice counter)
     int bv = load_rec(A, gi);
     const int act = PHASE != 2 ? (int)ufl((uint32_t)actions[gi]) : 0;
-    uint64_t ctr = A.dice_mode == BGX_DICE_PHILOX ? A.ctr[gi] : 0;
+    uint64_t ctr = (DICE >= 0 ? DICE : A.dice_mode) == BGX_DICE_PHILOX ? A.ctr[gi] : 0;
     if (PHASE != 2) bv = apply_lane(bv, gi, act, A, reward, done, info);
     if (PHASE != 1) {
-        bv = advance_lane<LOG, MEMO == 2 ? 2 : 0, NO_DOUBLES>(bv, gi, A, tab, memo, &ctr);
+        bv = advance_lane<LOG, MEMO == 2 ? 2 : 0, NO_DOUBLES, DICE>(bv, gi, A, tab, memo, &ctr);
         if (obs) write_obs(bv, obs + (size_t)gi * 198);
     }
     store_rec(A, gi, bv);
@@ -66,7 +67,9 @@ __device__ __forceinline__ void step_lane(const Args& A, int gi, uint4* tab, uin
 // `base` offsets blockIdx into the dispatch order.  MEMO: 0 = no revisit memo,
 // 1 = separate memo tables (10 KB of LDS), 2 = memo inside the dedup table.
 // NO_DOUBLES: doubles rolls are deferred to the overflow tiers (light launch).
-template <int PHASE, int LOG, int MEMO = 1, bool NO_DOUBLES = false, int WPE = 1>
+// DICE: BGX_DICE_PHILOX for the split launch of a Philox engine (no MT19937 or shared-dice
+// code in the two kernels where the step's time goes), -1 = every mode (Args::dice_mode).
+template <int PHASE, int LOG, int MEMO = 1, bool NO_DOUBLES = false, int WPE = 1, int DICE = -1>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_step(Args A, const int32_t* actions, float* obs, float* reward, uint8_t* done,
                                              int32_t* info, int base) {
     __shared__ uint4 tab[1 << LOG];
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
     uint4* memo = MEMO == 1 ? memo_ : MEMO == 2 ? tab : nullptr;
     const int bi = (int)blockIdx.x + base;
     const int gi = A.perm ? (int)ufl((uint32_t)A.perm[bi]) : lane_of_block(A, bi);
-    step_lane<PHASE, LOG, MEMO, NO_DOUBLES>(A, gi, tab, memo, actions, obs, reward, done, info);
+    step_lane<PHASE, LOG, MEMO, NO_DOUBLES, DICE>(A, gi, tab, memo, actions, obs, reward, done, info);
 }
 
 template <int LOG>
@@ -832,15 +835,21 @@ static void launch_heavy(hipStream_t s, const Args& a, int grid, const StepIo& i
     // the doubles walks that cannot bear off use no table at all, so occupancy
     // (VGPR-bound, 4 waves/SIMD) beats a bigger table (C3: 1,024 slots + memo 242 M/s,
     // 512 slots + memo inside 284 M/s, no memo 288 M/s; measured round 2)
-    hipLaunchKernelGGL((k_step<0, 9, 0>), dim3(grid), dim3(64), 0, s, a, io.actions, io.obs, io.reward, io.done,
-                       io.info, 0);
+    // (MT_LANE engines have no order and step every lane here, with the generic kernel)
+    if (a.dice_mode == BGX_DICE_PHILOX)
+        hipLaunchKernelGGL((k_step<0, 9, 0, false, 1, BGX_DICE_PHILOX>), dim3(grid), dim3(64), 0, s, a, io.actions,
+                           io.obs, io.reward, io.done, io.info, 0);
+    else
+        hipLaunchKernelGGL((k_step<0, 9, 0>), dim3(grid), dim3(64), 0, s, a, io.actions, io.obs, io.reward, io.done,
+                           io.info, 0);
 }
 
 // The order's positions from `heavy` on: a 256-slot table, no memo, no doubles code (4 KB,
 // 49 VGPRs: the hardware wave limit, ~5x the resident waves; doubles go to the overflow tiers).
 static void launch_light(hipStream_t s, const Args& a, int heavy, const StepIo& io) {
-    hipLaunchKernelGGL((k_step<0, 8, 0, true>), dim3(a.B - heavy), dim3(64), 0, s, a, io.actions, io.obs, io.reward,
-                       io.done, io.info, heavy);
+    // (reached only with a dispatch order, which only a Philox engine has)
+    hipLaunchKernelGGL((k_step<0, 8, 0, true, 1, BGX_DICE_PHILOX>), dim3(a.B - heavy), dim3(64), 0, s, a, io.actions,
+                       io.obs, io.reward, io.done, io.info, heavy);
 }
 
 // Doubles share of the dispatch order (Philox mode): the expected doubles
