@@ -756,6 +756,82 @@ int bgx_rollout_trunc_cut(const uint8_t* records_dev, const uint8_t* starts_dev,
                           uint8_t* sel_dev, float* lane_luck_or_null, int64_t* trunc_tally_dev,
                           int64_t* active_dev, uint8_t* reset_mask_out, void* stream);
 
+/* ---- cubeful exact bearoff table (csrc/bg_bearoff_cube.h; bgx/bearoff.py, bgx/cube.py,
+ * bgx/rollout.py; no counterpart in the reference) ----
+ * The money-play equity, with an unlimited doubling cube, of every race of the two-sided table,
+ * in units of the current cube and from the view of the side on roll with configuration a
+ * against b.  No gammons: both sides have checkers off.  Three cube states as the side on roll
+ * sees them -- cen (centred), own (it owns the cube), opp (the opponent owns it) -- and
+ *   child(cen) = cen, child(own) = opp, child(opp) = own   (the state as the next roller sees it)
+ *   ND_s[a][b] = sum over r = 0..20, from 0.0f, of p_r * max over a' in succ(a, r) of
+ *                (a' empty ? 1.0f : -E_child(s)[b][a'])
+ *   E_opp[a][b] = ND_opp[a][b];  DT[a][b] = 2.0f * E_opp[a][b]
+ *   E_s[a][b] = max(ND_s[a][b], min(DT[a][b], 1.0f))   for s = cen, own
+ *   E_s[a][empty] = ND_s[a][empty] = -1;  E_s[empty][b] = ND_s[empty][b] = +1 (b not empty)
+ * with p_r, the roll order and succ those of the two-sided table; every product and sum is
+ * rounded to fp32 once, with no fma, so a numpy float32 loop gives the same bits.  The roller
+ * doubles iff min(DT, 1) > ND_s (a tie is no double), the opponent takes iff DT <= 1.
+ * bgx_bearoff_cube_create builds it from an existing database `db` (whose W, configs and
+ * successor sets it reads, and which must outlive it) on `stream` of db's device, one launch per
+ * total pip count, and synchronises the stream.  bgx_bearoff_cube_buffers: equity float[3][n][n]
+ * in the order cen, own, opp, nd float[2][n][n] in the order cen, own, configs = db's.
+ * bgx_bearoff_cube_destroy synchronises the device.
+ *
+ * bgx_bearoff_cube_lookup: one thread per 64-byte record (16-byte aligned), bgx_bearoff_lookup's
+ * record test and in_db_out.  cube_dev uint8[n] (NULL: centred at 1 on every lane) is read as the
+ * cube kernels read it (k as min(k, cap), owner 3 as 0; cap in 0..10).  With m the record's
+ * mover: k >= cap is the dead state, owner 0 cen, owner m + 1 own, otherwise opp.  For a record
+ * in the table values_out float[n][4] (16-byte aligned, may be NULL) receives
+ *   [0] nd, the mover's equity if it does not double now (ND_s; E_opp in opp),
+ *   [1] DT,  [2] e = max(nd, min(DT, 1)) with access (cen, own) and nd without,
+ *   [3] the cubeless 2 W - 1 (fp32: the product, then the difference);  dead: nd = e = [3],
+ * and flags_out uint8[n] (may be NULL) bit 0: the mover may double, bit 1: it doubles, bit 2:
+ * the opponent takes (DT <= 1), bit 3: the cube is dead.  Other records: values not written,
+ * flags 0.  The table assumes an unlimited cube below the cap: that the cap could be reached
+ * deeper inside the table is ignored.  No allocation, no synchronisation: graph-capturable.
+ *
+ * bgx_rollout_cube_bearoff_cut: bgx_rollout_bearoff_cut for cubeful rollouts.  Call it once after
+ * bgx_rollout_begin and bgx_rollout_cube_begin and after every bgx_rollout_advance; the caller
+ * runs the masked bgx_reset after it.  cube_cut_tally int64[n_groups][6]
+ * (bgx_rollout_cube_cut_field) is zeroed by the caller.  A lane with sel[i] != 0, a valid group
+ * and a record in the table, k and the state read from cube[i] as in the lookup:
+ *   v = nd when plies[i] == 0 (no cube action on a game's first ply: a start record is the
+ *       position after the decision), else e;
+ *   q = v when the record's mover is the start record's mover, else -v;
+ *   Qq = llrintf(q * 1048576.0f) clamped to +-2^20;  Yq = Qq * 2^k  (|Yq| <= 2^30);
+ *   row group[i]: GAMES += 1, PLIES += plies[i], Y += Yq, Y2_LO += Yq^2 & (2^30 - 1),
+ *   Y2_HI += Yq^2 >> 30, LOG2 += k;
+ *   games_done[i] += 1, plies[i] = 0; the lane's last game: sel[i] = 0 and active drops;
+ *   cube[i] = cube0[i]; reset_mask_out[i] = 1.
+ * Every other lane gets reset_mask_out[i] = 0.  The sums are integers: run-to-run identical; a
+ * row holds 2^33 cut games.  No allocation, no synchronisation: graph-capturable.  BGX_EINVAL
+ * for what bgx_rollout_bearoff_cut and the cube kernels reject. */
+typedef struct bgx_bearoff_cube bgx_bearoff_cube;
+typedef struct {
+    const float* equity;       /* [3][n][n] cen, own, opp */
+    const float* nd;           /* [2][n][n] cen, own */
+    const int8_t* configs;
+    int32_t n, max_checkers;
+} bgx_bearoff_cube_buffers;
+enum bgx_rollout_cube_cut_field {
+    BGX_ROLLOUT_CUBE_CUT_GAMES = 0,   /* cut games */
+    BGX_ROLLOUT_CUBE_CUT_PLIES = 1,   /* their steps */
+    BGX_ROLLOUT_CUBE_CUT_Y = 2,       /* sum of Yq (2^-20 points, from the start mover's side) */
+    BGX_ROLLOUT_CUBE_CUT_Y2_LO = 3,   /* sum of Yq^2 & (2^30 - 1) */
+    BGX_ROLLOUT_CUBE_CUT_Y2_HI = 4,   /* sum of Yq^2 >> 30: sum Yq^2 = Y2_HI 2^30 + Y2_LO (2^-40) */
+    BGX_ROLLOUT_CUBE_CUT_LOG2 = 5     /* sum of k at the cut */
+};
+int bgx_bearoff_cube_create(bgx_bearoff* db, void* stream, bgx_bearoff_cube** out);
+int bgx_bearoff_cube_buffers_get(bgx_bearoff_cube* cdb, bgx_bearoff_cube_buffers* out);
+int bgx_bearoff_cube_destroy(bgx_bearoff_cube* cdb);
+int bgx_bearoff_cube_lookup(const bgx_bearoff_cube* cdb, const uint8_t* records_dev, const uint8_t* cube_dev, int32_t n,
+                            int32_t cap, uint8_t* in_db_out, float* values_out, uint8_t* flags_out, void* stream);
+int bgx_rollout_cube_bearoff_cut(const bgx_bearoff_cube* cdb, const uint8_t* records_dev, const uint8_t* starts_dev,
+                                 const int32_t* group_dev, int32_t n, int32_t n_groups, int32_t games_per_lane,
+                                 int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev,
+                                 int64_t* cube_cut_tally_dev, int64_t* active_dev, uint8_t* reset_mask_out, int32_t cap,
+                                 const uint8_t* cube0_dev, uint8_t* cube_dev, void* stream);
+
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row
  * stride ld_logits; mask from the legal count in bytes 60-61 of each 64-byte

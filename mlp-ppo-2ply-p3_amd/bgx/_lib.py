@@ -97,6 +97,12 @@ SIGNATURES = {
     "bgx_rollout_trunc_sel": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "bgx_rollout_trunc_cut": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_float, _I32, _I32, _I32, _P, _P, _P, _P, _P,
                                              _P, _P, _P]),
+    "bgx_bearoff_cube_create": (ctypes.c_int, [_P, _P, ctypes.POINTER(_P)]),
+    "bgx_bearoff_cube_buffers_get": (ctypes.c_int, [_P, _P]),
+    "bgx_bearoff_cube_destroy": (ctypes.c_int, [_P]),
+    "bgx_bearoff_cube_lookup": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "bgx_rollout_cube_bearoff_cut": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P,
+                                                    _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),
@@ -187,6 +193,10 @@ class BgxBearoffBuffers(ctypes.Structure):
 class BgxBearoff1Buffers(ctypes.Structure):
     _fields_ = [("dist", _P), ("surv", _P), ("mean", _P), ("choice", _P), ("configs", _P), ("n", _I32),
                 ("max_checkers", _I32)]
+
+
+class BgxBearoffCubeBuffers(ctypes.Structure):
+    _fields_ = [("equity", _P), ("nd", _P), ("configs", _P), ("n", _I32), ("max_checkers", _I32)]
 
 
 _lib = None

@@ -18,6 +18,11 @@ approximate win probability (each side minimises its own mean number of rolls), 
 OneSidedPlayer and the same rollout cut.  Because the cut's values are then approximate, the
 `equity_stderr` of a rollout cut at this table measures the spread of the sample and no longer
 the error against the truth.
+
+CubefulBearoffDB (csrc/bg_bearoff_cube.h behind bgx_bearoff_cube_*) adds the doubling
+cube to the exact table: the money-play equity of every race in it with the cube centred, owned
+and the opponent's, the exact answer to "double or not, take or pass?" (lookup), and the cut of
+cubeful rollouts (Rollout.run(..., cube=rule, cube_bearoff=cdb)).
 """
 from __future__ import annotations
 
@@ -281,7 +286,192 @@ class OneSidedPlayer(BearoffPlayer):
     bearoff."""
 
 
+class CubefulBearoffDB:
+    """The cubeful exact table (csrc/bg_bearoff_cube.h behind bgx_bearoff_cube_*)
+    over an existing BearoffDB `db`, built on db's device on the current stream: for every pair
+    of its configurations the money-play equity of the side on roll in units of the current
+    cube, for the cube centred, its own and the opponent's (unlimited cube, no gammons).  It
+    answers "double or not, take or pass?" exactly for every position in the table (lookup) and
+    cuts cubeful rollouts there (Rollout.run(..., cube=rule, cube_bearoff=cdb)).  The object
+    keeps `db`, whose memory it reads."""
+
+    kind = "cubeful"
+    STATES = ("cen", "own", "opp")                 # the planes' order; nd has the first two
+    _view = BearoffDB._view
+
+    def __init__(self, db: BearoffDB):
+        if not isinstance(db, BearoffDB):
+            raise ValueError("CubefulBearoffDB: db must be a bearoff.BearoffDB")
+        self._lib, self.db, self.device = db._lib, db, db.device
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            check(self._lib.bgx_bearoff_cube_create(db.handle(), _stream(self.device), ctypes.byref(h)),
+                  "bgx_bearoff_cube_create")
+        self._h = h
+        b = _lib.BgxBearoffCubeBuffers()
+        check(self._lib.bgx_bearoff_cube_buffers_get(h, ctypes.byref(b)), "bgx_bearoff_cube_buffers_get")
+        self.n, self.K = int(b.n), int(b.max_checkers)
+        self._equity = self._view(b.equity, (3, self.n, self.n), torch.float32)
+        self._nd = self._view(b.nd, (2, self.n, self.n), torch.float32)
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self._lib.bgx_bearoff_cube_destroy(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def handle(self):
+        return self._h
+
+    def equity(self) -> torch.Tensor:
+        """E as a [3, n, n] fp32 view of the table's memory (do not write to it): plane s, row a,
+        column b = the equity of the side on roll with a against b in cube state STATES[s]."""
+        return self._equity
+
+    def nd(self) -> torch.Tensor:
+        """ND as a [2, n, n] fp32 view: the same without a double now, for cen and own."""
+        return self._nd
+
+    def configs(self) -> torch.Tensor:
+        """The index order, the cubeless database's."""
+        return self.db.configs()
+
+    def index_of(self, config) -> int:
+        return self.db.index_of(config)
+
+    def lookup(self, records: torch.Tensor, cube=None, cap: int = 6, out=None):
+        """(in_db uint8[n], values f32[n, 4], flags uint8[n]) for uint8 [n, 64] lane records on
+        the table's device (bgx_bearoff_cube_lookup): values = (nd, DT, e, cubeless 2 W - 1) of
+        the record's mover holding the cube byte cube[i] (uint8[n], cube.pack(k, owner); None:
+        centred at 1), written only where in_db is 1 (NaN elsewhere without `out`); flags bit 0:
+        the mover may double, 1: it doubles, 2: the opponent takes, 3: the cube is dead."""
+        r = records
+        if r.dim() != 2 or r.shape[1] != 64 or r.dtype != torch.uint8 or r.device != self.device:
+            raise ValueError(f"lookup: records must be uint8 [n, 64] on {self.device}, got {r.dtype} "
+                             f"{tuple(r.shape)} on {r.device}")
+        r = r.contiguous()
+        n = r.shape[0]
+        if int(cap) != cap or not 0 <= int(cap) <= 10:
+            raise ValueError(f"lookup: cap must be in 0..10, got {cap!r}")
+        if cube is not None:
+            cube = torch.as_tensor(cube)
+            if cube.shape != (n,) or cube.dtype != torch.uint8 or cube.device != self.device:
+                raise ValueError(f"lookup: cube must be uint8[{n}] on {self.device}")
+            cube = cube.contiguous()
+        if out is None:
+            out = (torch.empty(n, dtype=torch.uint8, device=self.device),
+                   torch.full((n, 4), float("nan"), dtype=torch.float32, device=self.device),
+                   torch.empty(n, dtype=torch.uint8, device=self.device))
+        in_db, values, flags = out
+        check(self._lib.bgx_bearoff_cube_lookup(self._h, _ptr(r), _ptr(cube), n, int(cap), _ptr(in_db), _ptr(values),
+                                                _ptr(flags), _stream(self.device)), "bgx_bearoff_cube_lookup")
+        return in_db, values, flags
+
+
 # ------------------------------------------------------------- host references --
+CUBE_CHILD = (0, 2, 1)              # the cube state the next roller sees: cen -> cen, own -> opp, opp -> own
+
+
+def cube_table_reference(succ, n: int, dtype=np.float32):
+    """(equity[3, n, n], nd[2, n, n]) of the cubeful table on the host, from successor sets given
+    as for table_reference, by the recurrence of include/bgx.h with every product and sum
+    rounded to `dtype` once, the rolls in order from 0: np.float32 gives the device table's bits,
+    np.float64 a reference for its rounding error."""
+    f = dtype
+    E, ND = np.zeros((3, n, n), f), np.zeros((2, n, n), f)
+    for x in (E, ND):
+        x[:, :, 0] = f(-1)
+        x[:, 0, 1:] = f(1)
+    p = ROLL_P.astype(f) if f is np.float32 else np.array([1 / 36 if a == b else 2 / 36 for a, b in ROLLS21], f)
+    flat = [[np.asarray(s, np.int64) for s in succ[a]] for a in range(n)]
+    depth = np.zeros(n, np.int64)                           # table_reference's level function
+    for a in range(1, n):
+        depth[a] = 1 + max(depth[int(x)] for s in flat[a] for x in s)
+    by_depth = [np.nonzero(depth == d)[0] for d in range(int(depth.max()) + 1)]
+    for t in range(2, 2 * len(by_depth) - 1):
+        for a in range(1, n):
+            db = t - int(depth[a])
+            if not 1 <= db < len(by_depth):
+                continue
+            bs = by_depth[db]                               # every b of this level at once
+            acc = np.zeros((3, len(bs)), f)
+            for r in range(21):
+                s = flat[a][r]
+                for st in range(3):
+                    v = np.where(s == 0, f(1), -E[CUBE_CHILD[st]][np.ix_(bs, s)]).astype(f).max(axis=1)
+                    acc[st] = (acc[st] + (p[r] * v).astype(f)).astype(f)
+            cash = np.minimum((f(2) * acc[2]).astype(f), f(1))
+            ND[0, a, bs], ND[1, a, bs] = acc[0], acc[1]
+            E[0, a, bs], E[1, a, bs], E[2, a, bs] = np.maximum(acc[0], cash), np.maximum(acc[1], cash), acc[2]
+    return E, ND
+
+
+def cube_values_reference(state, nd_s, e_opp, w):
+    """Part 1 of csrc/bg_bearoff_cube.h on arrays: (values f32[..., 4], flags uint8[...]) from
+    the cube state (0 cen, 1 own, 2 opp, 3 dead), nd_s = ND_state[a][b] (read for cen and own
+    only), e_opp = E_opp[a][b] and w = W[a][b]."""
+    f = np.float32
+    state, nd_s, e_opp, w = np.broadcast_arrays(np.asarray(state), np.asarray(nd_s, f), np.asarray(e_opp, f),
+                                                np.asarray(w, f))
+    with np.errstate(invalid="ignore", over="ignore"):
+        dt = (f(2) * e_opp).astype(f)
+        cl = ((f(2) * w).astype(f) - f(1)).astype(f)
+        access = state <= 1
+        nd = np.where(access, nd_s, np.where(state == 2, e_opp, cl)).astype(f)
+        cash = np.where(dt < f(1), dt, f(1)).astype(f)
+        doubles = access & (cash > nd)
+        takes = dt <= f(1)
+    values = np.stack([nd, dt, np.where(doubles, cash, nd).astype(f), cl], axis=-1)
+    flags = (access * 1 + doubles * 2 + takes * 4 + (state == 3) * 8).astype(np.uint8)
+    return values, flags
+
+
+def cube_state_reference(cube, cap: int, mover):
+    """(state, k) of cube bytes for the record's mover (0 / 1): k as min(k, cap), owner 3 as 0;
+    k >= cap is dead (3), owner 0 cen (0), owner mover + 1 own (1), otherwise opp (2)."""
+    c, m = np.asarray(cube).astype(np.int64), np.asarray(mover).astype(np.int64) & 1
+    k, o = np.minimum(c & 15, int(cap)), (c >> 4) & 3
+    o = np.where(o == 3, 0, o)
+    return np.where(k >= int(cap), 3, np.where(o == 0, 0, np.where(o == m + 1, 1, 2))), k
+
+
+def cube_fixed_reference(v, start_mover_on_roll, k):
+    """boc_fixed of csrc/bg_bearoff_cube.h on arrays: Yq = clamp(rint(fp32(+-v 2^20)), +-2^20) 2^k,
+    0 for a NaN (round half even)."""
+    f = np.float32
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = (np.where(start_mover_on_roll, np.asarray(v, f), -np.asarray(v, f)).astype(f) * f(1 << 20)).astype(f)
+    x = np.where(np.isnan(x), f(0), np.clip(x, -float(1 << 20), float(1 << 20)))
+    return np.rint(x).astype(np.int64) * (np.int64(1) << np.asarray(k).astype(np.int64))
+
+
+def cube_lookup_reference(records, configs, equity, nd, table, max_checkers: int, cube=None, cap: int = 6):
+    """bgx_bearoff_cube_lookup on the host: (in_db bool[n], values f32[n, 4], NaN where not in the
+    table, flags uint8[n], 0 there) for uint8 [n, 64] records, with `configs`, `equity`, `nd` as
+    CubefulBearoffDB publishes them and `table` = the cubeless W."""
+    r = np.asarray(records).astype(np.int64)
+    equity, nd = np.asarray(equity, np.float32), np.asarray(nd, np.float32)
+    in_db, _ = lookup_reference(records, configs, table, max_checkers)
+    index = {tuple(int(v) for v in c): i for i, c in enumerate(np.asarray(configs))}
+    c0, c1 = r[:, 23:17:-1], r[:, 24:30]
+    n = r.shape[0]
+    m = r[:, R_CUR] & 1
+    state, _ = cube_state_reference(np.zeros(n, np.uint8) if cube is None else cube, cap, m)
+    values, flags = np.full((n, 4), np.nan, np.float32), np.zeros(n, np.uint8)
+    table = np.asarray(table, np.float32)
+    on = np.nonzero(in_db)[0]
+    if on.size:
+        idx = np.array([(index[tuple(c0[i])], index[tuple(c1[i])]) for i in on], np.int64)
+        a, b = idx[np.arange(on.size), m[on]], idx[np.arange(on.size), 1 - m[on]]
+        st = state[on]
+        values[on], flags[on] = cube_values_reference(st, np.where(st <= 1, nd[np.minimum(st, 1), a, b], np.float32(0)),
+                                                      equity[2, a, b], table[a, b])
+    return in_db, values, flags
+
+
 def dist_reference(succ, n: int):
     """(dist f32[n, 32], surv f32[n, 32], mean f32[n], choice int32[n, 21]) of the one-sided
     table on the host, from successor sets given as index lists as for table_reference (index

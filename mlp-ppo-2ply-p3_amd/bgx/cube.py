@@ -3,7 +3,9 @@ csrc/bg_cube.h, the four bgx_rollout_cube_* entry points of include/bgx.h; bgx/r
 them in its loop).  A game is worth its cubeless 1 / 2 / 3 points times the cube, 2^k; the side
 on roll may double before it rolls when the cube is centred or its own, the opponent takes
 (k + 1, the cube is now the taker's) or passes (the game ends at 2^k).  Both decisions follow one
-threshold rule, CubeRule, on the mover's equity before the roll.
+threshold rule, CubeRule, on the mover's equity before the roll.  Where a game enters the cubeful
+exact bearoff table (bearoff.CubefulBearoffDB) it can be cut and scored with its
+exact cubeful expectation instead (cube_bearoff=; summarize_cube_bearoff).
 
     python -m bgx.rollout --net ckpt.pt --player 1ply --positions opening --trials 1296 --cube
     python -m bgx.rollout --net ckpt.pt --player 1ply --positions pos.json --cube --cube-decision
@@ -22,6 +24,11 @@ CUBE_FIELDS = ("cube_games", "cube_points", "cube_points2", "cube_log2", "pass_g
                "doubles")
 MAX_CAP = 10
 CENTRED = 0                         # the owner field: 0 centred, 1 PLAYER1, 2 PLAYER2
+# cube_cut_tally int64[n_groups][6] (include/bgx.h bgx_rollout_cube_cut_field): the games cut at
+# the cubeful bearoff table, fixed point, 2^-20 points
+CUBE_CUT_FIELDS = ("cut_games", "cut_plies", "cut_y", "cut_y2_lo", "cut_y2_hi", "cut_log2")
+CUBE_CUT_ONE = 1 << 20              # Yq = rint(q * CUBE_CUT_ONE) * 2^k
+CUBE_CUT_SPLIT = 30                 # sum Yq^2 = cut_y2_hi * 2^30 + cut_y2_lo
 
 
 def pack(k: int, owner: int) -> int:
@@ -137,6 +144,75 @@ def summarize_cube(tally_row, cube_row, unfinished: int = 0) -> dict:
     return r
 
 
+def summarize_cube_bearoff(tally_row, cube_row, cut_row, unfinished: int = 0) -> dict:
+    """summarize_cube(tally_row, cube_row, unfinished) for a run cut at the cubeful bearoff table
+    (DESIGN.md §15), with the row's 6 cut sums (CUBE_CUT_FIELDS).  A cut game's result is its
+    exact cubeful expectation y = Yq / 2^20 points.  `games` = played out + passed + cut,
+    `equity_cubeful` and `equity_cubeful_stderr` over all three kinds together, from Python
+    integers: sum y = CUBE_POINTS 2^20 + CUT_Y in units of 2^-20, sum y^2 = CUBE_POINTS2 2^40 +
+    CUT_Y2_HI 2^30 + CUT_Y2_LO in units of 2^-40, so equal results give their value exactly and a
+    standard error of 0.  `pass_share`, `doubles_per_game`, `mean_cube_log2` (CUBE_LOG2 +
+    CUT_LOG2) and `plies_per_game` (PLIES + PASS_PLIES + CUT_PLIES) are over all games; adds
+    `cut_share` = CUT_GAMES / games and the 6 sums under their names.  The cut replaces the
+    endgame's dice noise and its cube action by the expectation, so the standard error is that of
+    the mixed sample.  Raises ValueError when CUBE_GAMES != GAMES + PASS_GAMES (the cut games are
+    counted beside them)."""
+    r = summarize_cube(tally_row, cube_row, unfinished)
+    c = [int(v) for v in cut_row]
+    if len(c) != len(CUBE_CUT_FIELDS):
+        raise ValueError(f"summarize_cube_bearoff: a cut row has {len(CUBE_CUT_FIELDS)} entries, got {len(c)}")
+    cut = dict(zip(CUBE_CUT_FIELDS, c))
+    n = r["cube_games"] + cut["cut_games"]
+    s1 = r["cube_points"] * CUBE_CUT_ONE + cut["cut_y"]
+    s2 = r["cube_points2"] * CUBE_CUT_ONE ** 2 + (cut["cut_y2_hi"] << CUBE_CUT_SPLIT) + cut["cut_y2_lo"]
+
+    def per_game(v):
+        return v / n if n > 0 else 0.0
+
+    var_num = max(n * s2 - s1 * s1, 0)                   # n^2 (n - 1) 2^40 x the variance of the mean
+    r.update(cut, games=n, cut_share=per_game(cut["cut_games"]),
+             equity_cubeful=s1 / (n * CUBE_CUT_ONE) if n > 0 else 0.0,
+             equity_cubeful_stderr=math.sqrt(var_num / (n * n * (n - 1))) / CUBE_CUT_ONE if n > 1 else 0.0,
+             pass_share=per_game(r["pass_games"]), doubles_per_game=per_game(r["doubles"]),
+             mean_cube_log2=per_game(r["cube_log2"] + cut["cut_log2"]),
+             plies_per_game=per_game(r["played_out"]["plies"] + r["pass_plies"] + cut["cut_plies"]))
+    return r
+
+
+def cube_bearoff_cut_reference(records, cube, plies, games_done, sel, starts, group, n_groups: int,
+                               games_per_lane: int, cap: int, cube0, lookup) -> dict:
+    """One call of bgx_rollout_cube_bearoff_cut on the host (include/bgx.h), state in, state out.
+    `lookup`: records uint8[B, 64], cube uint8[B], cap -> (in_db bool[B], values f32[B, 4], flags),
+    e.g. bearoff.cube_lookup_reference on a table.  A selected lane with a valid group whose record
+    is in the table adds Yq = bearoff.cube_fixed_reference(nd on its first ply, else e; signed for
+    the start mover; k of its cube) to its row, counts the game and gets its starting cube back.
+    Returns dict(cut_tally int64[P, 6], mask bool[B], games_done, plies, sel uint8[B], cube
+    uint8[B], retired int = the lanes that finished their last game)."""
+    from .bearoff import cube_fixed_reference
+    from .rollout import R_CUR
+    records, starts = np.asarray(records), np.asarray(starts)
+    group = np.asarray(group).astype(np.int64)
+    B, P, G = group.shape[0], int(n_groups), int(games_per_lane)
+    cube = np.asarray(cube).astype(np.uint8).copy()
+    plies, games = np.asarray(plies).astype(np.int64).copy(), np.asarray(games_done).astype(np.int64).copy()
+    sel = np.asarray(sel).astype(np.uint8).copy()
+    in_db, values, _ = lookup(records, cube, cap)
+    m = (sel != 0) & (group >= 0) & (group < P) & np.asarray(in_db, bool)
+    k = np.minimum(cube.astype(np.int64) & 15, int(cap))
+    v = np.where(plies == 0, values[:, 0], values[:, 2]).astype(np.float32)
+    yq = cube_fixed_reference(np.where(m, v, np.float32(0)), records[:, R_CUR] == starts[:, R_CUR], k)
+    y2 = yq * yq
+    tally = np.zeros((P, len(CUBE_CUT_FIELDS)), np.int64)
+    for f, x in enumerate((np.ones(B, np.int64), plies, yq, y2 & ((1 << CUBE_CUT_SPLIT) - 1), y2 >> CUBE_CUT_SPLIT, k)):
+        np.add.at(tally[:, f], group[m], x[m])
+    games[m] += 1
+    plies[m] = 0
+    retired = m & (games >= G)
+    sel[retired] = 0
+    cube[m] = sanitise(np.asarray(cube0), cap)[m]
+    return dict(cut_tally=tally, mask=m, games_done=games, plies=plies, sel=sel, cube=cube, retired=int(retired.sum()))
+
+
 def decide_reference(cube, mover, equity, rule: CubeRule):
     """cube_decision of csrc/bg_cube.h on arrays: (action int[B]: 0 none, 1 take, 2 pass; next
     uint8[B]; access bool[B] = cube_access), without the lane selection."""
@@ -155,13 +231,17 @@ def decide_reference(cube, mover, equity, rule: CubeRule):
     return np.where(pas, 2, np.where(take, 1, 0)), nxt, access
 
 
-def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rule: CubeRule, cube0=None) -> dict:
+def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rule: CubeRule, cube0=None,
+                   cut_lookup=None) -> dict:
     """A traced cube run replayed on the host with the kernels' arithmetic (include/bgx.h
     bgx_rollout_cube_*).  `trace`: run_lanes' with cube_mover, cube_equity, done and info
     [steps, B]; the lane records are taken as not game_over, which holds between the steps of an
     auto-reset engine.  Returns dict(cube_tally int64[P, 8], tally int64[P, 8], cube uint8[steps,
     B] = the states before each decision, dsel / mask bool[steps, B], games_done int64[B],
-    active int)."""
+    active int).  `cut_lookup` (cube_bearoff_cut_reference's `lookup`): the run was cut at the
+    cubeful bearoff table (run_lanes' cube_bearoff=) -- the cut is replayed after begin on the
+    trace's cut_records0 and after every step on cut_records[t]; the result gains cut_tally
+    int64[P, 6], cut0 bool[B] and cut bool[steps, B]."""
     from .rollout import FIELDS, R_CUR
     mover = np.asarray(torch.as_tensor(trace["cube_mover"]).cpu()).astype(np.int64)
     equity = np.asarray(torch.as_tensor(trace["cube_equity"]).cpu()).astype(np.float32)
@@ -177,6 +257,17 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
     tally, ct = np.zeros((P, len(FIELDS)), np.int64), np.zeros((P, len(CUBE_FIELDS)), np.int64)
     T = done.shape[0]
     states, dsels, masks = np.zeros((T, B), np.uint8), np.zeros((T, B), bool), np.zeros((T, B), bool)
+    cut_tally, cuts = np.zeros((P, len(CUBE_CUT_FIELDS)), np.int64), np.zeros((T, B), bool)
+
+    def cut(recs):
+        nonlocal cube, plies, games
+        out = cube_bearoff_cut_reference(np.asarray(torch.as_tensor(recs).cpu()), cube, plies, games, valid & (games < G),
+                                         starts, group, P, G, cap, c0, cut_lookup)
+        cube, plies, games = out["cube"], out["plies"], out["games_done"]
+        cut_tally[:] += out["cut_tally"]
+        return out["mask"]
+
+    cut0 = cut(trace["cut_records0"]) if cut_lookup is not None else None
 
     def add(rows, lanes, values):
         for f, v in values.items():
@@ -216,12 +307,17 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
         cube = np.where(dn, c0, cube).astype(np.uint8)
         games += fin
         plies = np.where(fin, 0, plies)
-    return dict(cube_tally=ct, tally=tally, cube=states, dsel=dsels, mask=masks, games_done=games,
-                active=int((valid & (games < G)).sum()))
+        if cut_lookup is not None:
+            cuts[t] = cut(trace["cut_records"][t])
+    out = dict(cube_tally=ct, tally=tally, cube=states, dsel=dsels, mask=masks, games_done=games,
+               active=int((valid & (games < G)).sum()))
+    if cut_lookup is not None:
+        out.update(cut_tally=cut_tally, cut0=cut0, cut=cuts)
+    return out
 
 
 def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, cube=(0, CENTRED),
-                          first_roll: str = "stratified", max_steps: int = 4000) -> dict:
+                          first_roll: str = "stratified", max_steps: int = 4000, cube_bearoff=None) -> dict:
     """"Double or not, take or pass?" for the side on roll in `record` (uint8[64]: board and
     mover), holding the cube `cube` = (k, owner) with access to it.  The position is rolled out
     twice in one run, as two groups over the same start records: "no double", with the cube as
@@ -229,7 +325,10 @@ def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, 
     game's first ply, so both start after the decision asked about.  Returns `no_double`,
     `double_take` and `double_pass` = +1, the mover's equities in units of the current cube 2^k,
     each with its `_stderr`, the two rollouts' summaries (`rollouts`), and the verdict: `double`
-    iff min(double_take, 1) > no_double, `take` iff double_take <= 1."""
+    iff min(double_take, 1) > no_double, `take` iff double_take <= 1.  `cube_bearoff` (a
+    bearoff.CubefulBearoffDB): both rollouts are cut at the cubeful table
+    (Rollout.run); for a position in the table that is the exact answer, the table's nd and DT at
+    the cut's 2^-20 resolution, with standard errors of 0."""
     rec = torch.as_tensor(record).reshape(-1)
     if rec.numel() != 64 or rec.dtype != torch.uint8:
         raise ValueError("rollout_cube_decision: record must be 64 bytes (uint8)")
@@ -240,7 +339,7 @@ def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, 
                          f"the cap {rule.cap}")
     pos = torch.stack([rec.cpu(), rec.cpu()])
     res = rollout.run(player, pos, trials, first_roll=first_roll, max_steps=max_steps, cube=rule,
-                      cube_start=[(k, owner), (k + 1, 2 - mover)])
+                      cube_start=[(k, owner), (k + 1, 2 - mover)], cube_bearoff=cube_bearoff)
     unit = float(1 << k)
     nd, dt = res[0]["equity_cubeful"] / unit, res[1]["equity_cubeful"] / unit
     return dict(no_double=nd, no_double_stderr=res[0]["equity_cubeful_stderr"] / unit,

@@ -19,7 +19,9 @@ reaches every pure home-board race but whose win probability is an approximation
 --cube: money play with the doubling cube (bgx/cube.py): before its roll the side
 on roll may double by a threshold rule on a net's value, a passed double ends the game, and the
 result is the cubeful equity (cube.summarize_cube); --cube-decision answers "double or not,
-take or pass?" per position.  --truncate N: a game that has run N plies stops there and is scored by
+take or pass?" per position; --cube-bearoff K cuts the cubeful games at the cubeful exact bearoff
+table (bearoff.CubefulBearoffDB), where both the endgame's dice and its cube
+action are replaced by the exact cubeful expectation.  --truncate N: a game that has run N plies stops there and is scored by
 a net's value head (bgx/truncate.py; DESIGN.md §14), which makes the slow players affordable;
 with --luck the dice noise of the plies played goes too (summarize_truncated_luck).  The
 estimate then carries the net's own error, which no standard error shows.
@@ -332,7 +334,8 @@ class Rollout:
         self.steps = 0                  # steps of every run so far: the players' random streams go on
 
     def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
-                  trace: bool = False, luck=None, bearoff=None, cube=None, cube0=None, truncate=None):
+                  trace: bool = False, luck=None, bearoff=None, cube=None, cube0=None, truncate=None,
+                  cube_bearoff=None):
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
@@ -391,7 +394,24 @@ class Rollout:
         (truncate.TRUNC_FIELDS), and the trace gains per step trunc uint8 (the lanes truncated),
         trunc_value (NaN off them) and trunc_mover (the side on roll there).  Together with
         `luck` it is supported (summarize_truncated_luck); together with `bearoff` or `cube` it
-        raises ValueError (the three-way summaries do not exist).  None: nothing changes."""
+        raises ValueError (the three-way summaries do not exist).  None: nothing changes.
+
+        `cube_bearoff` (a bearoff.CubefulBearoffDB), with `cube`: a cubeful game
+        that reaches the cubeful table stops there and is scored with its exact cubeful
+        expectation times its cube -- the cube loop followed by [cube_bearoff_cut, reset(mask)],
+        and one cut and reset after cube_begin, so a lane that enters the table is cut before its
+        next cube decision.  A further result follows cube_tally: cube_cut_tally int64[n_groups, 6]
+        (cube.CUBE_CUT_FIELDS), and the trace gains cut, cut_records, cut0 and cut_records0 as with
+        `bearoff`.  Without `cube`, or together with `luck`, `bearoff` or `truncate`, it raises
+        ValueError.  None: nothing changes."""
+        if cube_bearoff is not None:
+            if cube is None:
+                raise ValueError("run_lanes: cube_bearoff without cube")
+            for name, other in (("luck", luck), ("bearoff", bearoff), ("truncate", truncate)):
+                if other is not None:
+                    raise ValueError(f"run_lanes: cube_bearoff together with {name} is not supported")
+            if getattr(cube_bearoff, "kind", None) != "cubeful":
+                raise ValueError("run_lanes: cube_bearoff must be a bearoff.CubefulBearoffDB")
         if truncate is not None and (bearoff is not None or cube is not None):
             raise ValueError(f"run_lanes: truncate together with {'bearoff' if bearoff is not None else 'cube'} "
                              "is not supported")
@@ -479,6 +499,31 @@ class Rollout:
 
             cut(None)
             cut_begin = (mask.clone(), rec.clone()) if trace else None
+        if cube_bearoff is not None:
+            from .cube import CUBE_CUT_FIELDS
+            if cube_bearoff.device != dev:
+                raise ValueError(f"run_lanes: the cubeful bearoff table is on {cube_bearoff.device}, the engine on {dev}")
+            cube_cut_tally = torch.zeros(P, len(CUBE_CUT_FIELDS), dtype=torch.int64, device=dev)
+            mask = torch.empty(self.B, dtype=torch.uint8, device=dev)
+            if trace:
+                tr["cut"] = torch.zeros(max_steps, self.B, dtype=torch.uint8, device=dev)
+                tr["cut_records"] = torch.zeros(max_steps, self.B, 64, dtype=torch.uint8, device=dev)
+
+            def cube_cut(step):
+                if trace:
+                    eng.records(out=rec)
+                check(L.bgx_rollout_cube_bearoff_cut(cube_bearoff.handle(), recs, _ptr(starts), _ptr(grp), self.B, P, G,
+                                                     _ptr(self.games_done), _ptr(self.plies), _ptr(self.sel),
+                                                     _ptr(cube_cut_tally), _ptr(self.active), _ptr(mask), cube.cap,
+                                                     _ptr(c0), _ptr(cstate), _stream(dev)),
+                      "bgx_rollout_cube_bearoff_cut")
+                if trace and step is not None:
+                    tr["cut"][step] = mask
+                    tr["cut_records"][step] = rec
+                eng.reset(lane_mask=mask, want_obs=False)
+
+            cube_cut(None)
+            cut_begin = (mask.clone(), rec.clone()) if trace else None
         every = (SYNC_EVERY if getattr(player, "sync_free", False) and luck is None and cube is None
                  and (truncate is None or truncate.sync_free) else 1)
         steps = 0
@@ -534,6 +579,8 @@ class Rollout:
                 tr["info"][steps] = info
             if bearoff is not None:
                 cut(steps)
+            if cube_bearoff is not None:
+                cube_cut(steps)
             if truncate is not None:
                 check(L.bgx_rollout_trunc_sel(recs, _ptr(grp), self.B, P, truncate.plies, _ptr(self.plies),
                                               _ptr(self.sel), _ptr(tsel), None, _stream(dev)), "bgx_rollout_trunc_sel")
@@ -557,10 +604,12 @@ class Rollout:
         if trace:
             tr = {n: v[:steps] for n, v in tr.items()}
             tr.update(games_done=self.games_done.clone(), active=int(self.active.item()))
-            if bearoff is not None:
+            if bearoff is not None or cube_bearoff is not None:
                 tr.update(cut0=cut_begin[0], cut_records0=cut_begin[1])
         if bearoff is not None:
             return tally, unfinished, tr, cut_tally
+        if cube_bearoff is not None:
+            return tally, unfinished, tr, cube_tally, cube_cut_tally
         if cube is not None:
             return tally, unfinished, tr, cube_tally
         if truncate is not None:
@@ -570,7 +619,7 @@ class Rollout:
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
             trace: bool = False, luck=None, luck_scale="fit", bearoff=None, cube=None, cube_start=(0, 0),
-            truncate=None):
+            truncate=None, cube_bearoff=None):
         """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
         bytes come from the layout) `trials` times with `player` (any arena player object)
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
@@ -589,7 +638,16 @@ class Rollout:
         cube.summarize_cube's.  Not together with `luck` or `bearoff` (ValueError).  `truncate` (a
         truncate.Truncation): games stop at its horizon and are scored with its
         value (run_lanes); the results are summarize_truncated's, with `luck` those of
-        summarize_truncated_luck.  Not together with `bearoff` or `cube` (ValueError)."""
+        summarize_truncated_luck.  Not together with `bearoff` or `cube` (ValueError).
+        `cube_bearoff` (a bearoff.CubefulBearoffDB), with `cube`: the cubeful cut
+        (run_lanes); the results are cube.summarize_cube_bearoff's and carry `bearoff_kind` =
+        "cubeful".  Without `cube`, or together with `luck`, `bearoff` or `truncate`: ValueError."""
+        if cube_bearoff is not None:
+            if cube is None:
+                raise ValueError("run: cube_bearoff without cube")
+            for name, other in (("luck", luck), ("bearoff", bearoff), ("truncate", truncate)):
+                if other is not None:
+                    raise ValueError(f"run: cube_bearoff together with {name} is not supported")
         if truncate is not None and (bearoff is not None or cube is not None):
             raise ValueError(f"run: truncate together with {'bearoff' if bearoff is not None else 'cube'} is not "
                              "supported")
@@ -600,7 +658,7 @@ class Rollout:
         pos = _records(positions)
         P = pos.shape[0]
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
-        total = unfinished = tr = ltotal = ttotal = None
+        total = unfinished = tr = ltotal = ttotal = cctotal = None
         if cube is not None:
             from .cube import pack, summarize_cube
             cs = np.asarray(cube_start, np.int64)
@@ -614,8 +672,10 @@ class Rollout:
             out = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck,
                                  bearoff=bearoff, cube=cube,
                                  cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None,
-                                 truncate=truncate)
+                                 truncate=truncate, cube_bearoff=cube_bearoff)
             tally, unf, tr = out[:3]
+            if cube_bearoff is not None:
+                cctotal = out[4] if cctotal is None else cctotal + out[4]
             if truncate is not None:
                 ttotal = out[-1] if ttotal is None else ttotal + out[-1]
             if luck is not None or bearoff is not None or cube is not None:
@@ -642,6 +702,12 @@ class Rollout:
             if bearoff.kind != "two-sided":
                 for r in res:
                     r["bearoff_kind"] = bearoff.kind
+        elif cube_bearoff is not None:
+            from .cube import summarize_cube_bearoff
+            crows, ccrows = ltotal.cpu().tolist(), cctotal.cpu().tolist()
+            res = [summarize_cube_bearoff(rows[p], crows[p], ccrows[p], unf[p]) for p in range(P)]
+            for r in res:
+                r["bearoff_kind"] = cube_bearoff.kind
         elif cube is not None:
             crows = ltotal.cpu().tolist()
             res = [summarize_cube(rows[p], crows[p], unf[p]) for p in range(P)]
@@ -807,6 +873,11 @@ class _Parser(argparse.ArgumentParser):
                 self.error(f"--{name.replace('_', '-')} takes a number of checkers in 1..{top}")
         if ns.cube_decision and not ns.cube:
             self.error("--cube-decision needs --cube")
+        if ns.cube_bearoff is not None:
+            if not ns.cube:
+                self.error("--cube-bearoff needs --cube")
+            if not 1 <= ns.cube_bearoff <= 8:
+                self.error("--cube-bearoff takes a number of checkers in 1..8")
         if ns.cube:
             if ns.net == "random" and ns.cube_net is None:
                 self.error("--cube needs --net with weights or --cube-net (the decisions are made on a net's "
@@ -890,6 +961,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "over the 21 rolls")
     ap.add_argument("--truncate-net", default=None, metavar="PATH",
                     help="the state_dict whose value head scores the truncated games (default: the player's net)")
+    ap.add_argument("--cube-bearoff", type=int, default=None, metavar="K",
+                    help="with --cube: stop a game at the cubeful exact bearoff table for K checkers a side (1..8) "
+                         "and score it with its exact cubeful expectation; not with --luck, --bearoff, --bearoff1 "
+                         "or --truncate")
     ap.add_argument("--cube-decision", action="store_true",
                     help="per position: no double / double, take / double, pass for the side on roll with a "
                          "centred cube, and the verdict")
@@ -933,6 +1008,12 @@ def main(argv=None):
                         too_good_at=args.cube_too_good, cap=args.cube_cap, jacoby=args.jacoby)
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
+    cdb = None
+    if args.cube_bearoff is not None:
+        from .bearoff import BearoffDB, CubefulBearoffDB
+        cdb = CubefulBearoffDB(dbs.get(args.cube_bearoff) or BearoffDB(args.cube_bearoff, device=dev))
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()                        # the table's build is not the rollout's time
     trunc = None
     if args.truncate is not None:
         from .search import ValueHead
@@ -945,13 +1026,13 @@ def main(argv=None):
         res = []
         for i in range(positions.shape[0]):
             d = rollout_cube_decision(ro, player, positions[i], args.trials, rule, first_roll=args.first_roll,
-                                      max_steps=args.max_steps)
+                                      max_steps=args.max_steps, cube_bearoff=cdb)
             print(json.dumps(dict(position=i, cube_decision=True, **d)), flush=True)
             res.extend(d["rollouts"])
     else:
         res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
                      luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff) or dbs1.get(args.bearoff1), cube=rule,
-                     truncate=trunc)
+                     truncate=trunc, cube_bearoff=cdb)
     dt = time.perf_counter() - t0
     for i, r in enumerate(res if not args.cube_decision else ()):
         print(json.dumps(dict(position=i, **r)), flush=True)
@@ -978,6 +1059,10 @@ def main(argv=None):
                        pass_share=sum(r["pass_games"] for r in res) / games if games else 0.0,
                        doubles_per_game=sum(r["doubles"] for r in res) / games if games else 0.0,
                        plies_per_game=sum(r["plies_per_game"] * r["games"] for r in res) / games if games else 0.0)
+    if cdb is not None:
+        cut = sum(r["cut_games"] for r in res)
+        summary.update(cube_bearoff=args.cube_bearoff, bearoff_kind=cdb.kind, cut_games=cut,
+                       cut_share=cut / games if games else 0.0)
     if trunc is not None:
         tg = sum(r["truncated_games"] for r in res)
         summary.update(truncate=args.truncate, truncate_scale=args.truncate_scale,
