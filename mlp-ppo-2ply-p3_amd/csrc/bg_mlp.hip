@@ -177,7 +177,8 @@ __host__ __device__ inline void views(P base, int T, int OT, P& hdr, P& w1q, P& 
 // in the same launch (the grid's first blocks), each gathering up to 32 of the
 // window's count-0 rows; its 4 waves split the output tiles (a quarter each) and
 // wave 0 merges their partial log-sum-exp / Gumbel-max states through LDS, so the
-// extra workgroups last about as long as the skipping main waves.  A window with
+// extra workgroups last about as long as the skipping main waves (GEMM1 is split the
+// same way: each wave computes one hidden tile, exchanged through LDS).  A window with
 // more than kZCap count-0 rows (never at self-play's ~5 %) keeps them on its main
 // waves, unskipped.  Outputs equal the unskipped kernel's up to the log-sum-exp's
 // summation order (the noise is keyed by (row, action)); BGX_POLICY_SKIP=0 turns
@@ -229,7 +230,9 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
     const int e1 = __builtin_bit_cast(int, hdrf[0]), e2 = __builtin_bit_cast(int, hdrf[1]);
     const int l = lane_id();
     const int j = l & 31, h = l >> 5;
-    const int wv = kW > 1 ? (int)(threadIdx.x >> 6) : 0;
+    // the wave index in a scalar register: the tile range and every fragment address
+    // derived from it stay wave-uniform for the compiler too
+    const int wv = kW > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     uint8_t* const srec = srec_[wv];
     // the extra workgroups come first in the grid: they start first
     const int n_extra = skip_on ? 2 * ((n + kZWin - 1) / kZWin) : 0;
@@ -289,32 +292,75 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
     PSTAMP(1);
     // ---- GEMM1: X1s[t] = W1s[32t.., :] . F^T + b1 * 2^e1  (= 2^e1 X1)
     f32x16 x1[T];
-    #pragma unroll
-    for (int t = 0; t < T; ++t)
-        #pragma unroll
-        for (int r = 0; r < 16; ++r) x1[t][r] = b1p[(t * 16 + r) * 64 + l];
-    // W1's fragments stream from L2 kPD k-blocks ahead of their MFMAs (a ring of
-    // registers): at one or two waves per SIMD nothing else hides the L2 latency
     constexpr int kPD = kW1Ahead;
-    uint4 wf[kPD + 1][2 * T];
-    #pragma unroll
-    for (int p = 0; p < kPD; ++p)
-        #pragma unroll
-        for (int f = 0; f < 2 * T; ++f) wf[p][f] = w1q[(p * 2 * T + f) * 64 + l];
-    #pragma unroll
-    for (int kb = 0; kb < kKB1; ++kb) {
-        if (kb + kPD < kKB1) {
+    if (kW > 1 && extra) {
+        // The four waves of an extra workgroup hold the same gathered rows: wave wv computes
+        // hidden tile wv alone (the same MFMAs in the same k order as below, so the same
+        // bits) and the tiles are exchanged through LDS, two at a time in the 8 KiB of the
+        // record copies, which are dead once every wave has generated its features.
+        f32x16 acc;
+        if (wv < T) {
             #pragma unroll
-            for (int f = 0; f < 2 * T; ++f) wf[(kb + kPD) % (kPD + 1)][f] = w1q[((kb + kPD) * 2 * T + f) * 64 + l];
+            for (int r = 0; r < 16; ++r) acc[r] = b1p[(wv * 16 + r) * 64 + l];
+            uint4 wr[kPD + 1][2];
+            #pragma unroll
+            for (int p = 0; p < kPD; ++p)
+                #pragma unroll
+                for (int f = 0; f < 2; ++f) wr[p][f] = w1q[(p * 2 * T + 2 * wv + f) * 64 + l];
+            #pragma unroll
+            for (int kb = 0; kb < kKB1; ++kb) {
+                if (kb + kPD < kKB1) {
+                    #pragma unroll
+                    for (int f = 0; f < 2; ++f)
+                        wr[(kb + kPD) % (kPD + 1)][f] = w1q[((kb + kPD) * 2 * T + 2 * wv + f) * 64 + l];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+                const f16x8 bf = feats8(myrec, kb, h);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(wr[kb % (kPD + 1)][1]), bf, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_h8(wr[kb % (kPD + 1)][0]), bf, acc, 0, 0, 0);
+            }
         }
-        __builtin_amdgcn_sched_barrier(0);
-        const f16x8 bf = feats8(myrec, kb, h);         // exact in f16: no lo part
+        float* const xs = (float*)&srec_[0][0];        // [2][16][64] floats
         #pragma unroll
-        for (int t = 0; t < T; ++t) {
-            const f16x8 ah = as_h8(wf[kb % (kPD + 1)][2 * t + 0]);
-            const f16x8 al = as_h8(wf[kb % (kPD + 1)][2 * t + 1]);
-            x1[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bf, x1[t], 0, 0, 0);
-            x1[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bf, x1[t], 0, 0, 0);
+        for (int t0 = 0; t0 < T; t0 += 2) {
+            __syncthreads();                           // features read (t0 = 0) / tiles t0 - 2.. read
+            if (wv >= t0 && wv < t0 + 2 && wv < T) {
+                #pragma unroll
+                for (int r = 0; r < 16; ++r) xs[((wv - t0) * 16 + r) * 64 + l] = acc[r];
+            }
+            __syncthreads();
+            #pragma unroll
+            for (int t = t0; t < t0 + 2 && t < T; ++t)
+                #pragma unroll
+                for (int r = 0; r < 16; ++r) x1[t][r] = xs[((t - t0) * 16 + r) * 64 + l];
+        }
+    } else {
+        #pragma unroll
+        for (int t = 0; t < T; ++t)
+            #pragma unroll
+            for (int r = 0; r < 16; ++r) x1[t][r] = b1p[(t * 16 + r) * 64 + l];
+        // W1's fragments stream from L2 kPD k-blocks ahead of their MFMAs (a ring of
+        // registers): at one or two waves per SIMD nothing else hides the L2 latency
+        uint4 wf[kPD + 1][2 * T];
+        #pragma unroll
+        for (int p = 0; p < kPD; ++p)
+            #pragma unroll
+            for (int f = 0; f < 2 * T; ++f) wf[p][f] = w1q[(p * 2 * T + f) * 64 + l];
+        #pragma unroll
+        for (int kb = 0; kb < kKB1; ++kb) {
+            if (kb + kPD < kKB1) {
+                #pragma unroll
+                for (int f = 0; f < 2 * T; ++f) wf[(kb + kPD) % (kPD + 1)][f] = w1q[((kb + kPD) * 2 * T + f) * 64 + l];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const f16x8 bf = feats8(myrec, kb, h);         // exact in f16: no lo part
+            #pragma unroll
+            for (int t = 0; t < T; ++t) {
+                const f16x8 ah = as_h8(wf[kb % (kPD + 1)][2 * t + 0]);
+                const f16x8 al = as_h8(wf[kb % (kPD + 1)][2 * t + 1]);
+                x1[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bf, x1[t], 0, 0, 0);
+                x1[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bf, x1[t], 0, 0, 0);
+            }
         }
     }
     // ReLU, then a per-wave scale 2^ex for the split of the hidden layer
@@ -365,12 +411,24 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
     const uint32_t rowkey = mix32(mix32(seed_lo ^ mix32(seed_hi + 0x9E3779B9u)) ^ step) ^ (uint32_t)grow * 0x85EBCA6Bu;
     constexpr int NF = T * 2 * 2;                      // weight fragments per output tile
     uint4 w[NF];
-    #pragma unroll
-    for (int f = 0; f < NF; ++f) w[f] = o_beg < o_end ? w2q[((size_t)o_beg * NF + f) * 64 + l] : make_uint4(0, 0, 0, 0);
+    // the tile's bias fragment (raw; * up where the accumulator starts) is fetched a
+    // tile ahead like w[]: it is the C operand of the tile's first MFMA
+    float bq[16];
+    if (o_beg < o_end) {
+        #pragma unroll
+        for (int f = 0; f < NF; ++f) w[f] = w2q[((size_t)o_beg * NF + f) * 64 + l];
+        #pragma unroll
+        for (int r = 0; r < 16; ++r) bq[r] = b2p[(o_beg * 16 + r) * 64 + l];
+    } else {
+        #pragma unroll
+        for (int f = 0; f < NF; ++f) w[f] = make_uint4(0, 0, 0, 0);
+        #pragma unroll
+        for (int r = 0; r < 16; ++r) bq[r] = 0.0f;
+    }
     for (int o = o_beg; o < o_end;) {
         f32x16 y;
         #pragma unroll
-        for (int r = 0; r < 16; ++r) y[r] = b2p[(o * 16 + r) * 64 + l] * up;
+        for (int r = 0; r < 16; ++r) y[r] = bq[r] * up;
         #pragma unroll
         for (int t = 0; t < T; ++t)
             #pragma unroll
@@ -403,6 +461,14 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
             z[r] = a < n_actions ? (a < count ? z0 : z0 + kMaskLog) : -INFINITY;
             tm = fmaxf(tm, z[r]);
         }
+        // tile nx's bias fragment, behind the log-sum-exp and the Gumbel draw below like
+        // w[] (y is dead from here; the compiler issues these right after the w[] loads:
+        // 248 VGPRs at T = 4, no scratch)
+        __asm__ volatile("" ::: "memory");
+        if (nx < o_end) {
+            #pragma unroll
+            for (int r = 0; r < 16; ++r) bq[r] = b2p[(nx * 16 + r) * 64 + l];
+        }
         const float mn = fmaxf(m, tm);
         if (mn != -INFINITY) {                         // else nothing of this lane's row so far
             float acc = 0.0f;
@@ -434,8 +500,14 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
             if (__ballot(!ok) == 0ull) {
                 next = vt;
             } else {                                   // no skip: tile o + 1 after all
+                // (o + 1 == o_s is loop-invariant: hidden from the compiler, which would keep
+                // this rare path's 20 fragment addresses in registers through the whole loop)
+                int o1 = o + 1;
+                __asm__ volatile("" : "+v"(o1));
                 #pragma unroll
-                for (int f = 0; f < NF; ++f) w[f] = w2q[((size_t)(o + 1) * NF + f) * 64 + l];
+                for (int f = 0; f < NF; ++f) w[f] = w2q[((size_t)o1 * NF + f) * 64 + l];
+                #pragma unroll
+                for (int r = 0; r < 16; ++r) bq[r] = b2p[(o1 * 16 + r) * 64 + l];
             }
         }
         o = next;
