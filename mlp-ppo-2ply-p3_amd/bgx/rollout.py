@@ -311,6 +311,249 @@ def _records(positions) -> torch.Tensor:
     return p
 
 
+def _check_modes(where: str, luck=None, bearoff=None, cube=None, truncate=None, cube_bearoff=None, cube0=None,
+                 types: bool = False) -> None:
+    """The combinations of modes that Rollout.run and run_lanes refuse, as ValueError(f"{where}: ...")
+    for the first one that applies.  `types` (run_lanes): also what only the lanes can tell --
+    a cube_bearoff that is no cubeful table, a truncate that is no Truncation, cube0 without cube --
+    each at its place in the order.  Nothing here touches the engine or the library."""
+    if cube_bearoff is not None:
+        if cube is None:
+            raise ValueError(f"{where}: cube_bearoff without cube")
+        for name, other in (("luck", luck), ("bearoff", bearoff), ("truncate", truncate)):
+            if other is not None:
+                raise ValueError(f"{where}: cube_bearoff together with {name} is not supported")
+        if types and getattr(cube_bearoff, "kind", None) != "cubeful":
+            raise ValueError(f"{where}: cube_bearoff must be a bearoff.CubefulBearoffDB")
+    if truncate is not None and (bearoff is not None or cube is not None):
+        raise ValueError(f"{where}: truncate together with {'bearoff' if bearoff is not None else 'cube'} "
+                         "is not supported")
+    if types and truncate is not None and not isinstance(truncate, Truncation):
+        raise ValueError(f"{where}: truncate must be a truncate.Truncation")
+    for a, b, x, y in (("bearoff", "luck", bearoff, luck), ("cube", "luck", cube, luck), ("cube", "bearoff", cube, bearoff)):
+        if x is not None and y is not None:
+            raise ValueError(f"{where}: {a} together with {b} is not supported")
+    if types and cube is None and cube0 is not None:
+        raise ValueError(f"{where}: cube0 without cube")
+
+
+class _Pass:
+    """What one run_lanes pass shares with its stages: the library, the engine and its lane
+    records, the device copies of starts and group, the sizes, the rollout's own per-lane state
+    (`lanes` = games_done, plies, sel as pointers; `active`), and with trace=True the trace
+    dicts (`tr` of [max_steps, B] tensors, `tr_end`) and `rec`, a scratch copy of the lane records."""
+
+    def __init__(self, ro, starts, grp, P: int, G: int, max_steps: int, trace: bool):
+        self.ro, self.L, self.eng, self.dev = ro, _lib.load(), ro.eng, ro.eng.device
+        self.B, self.P, self.G, self.max_steps = ro.B, P, G, max_steps
+        self.recs, self.stream = ctypes.c_void_p(ro.eng.lanes_ptr()), _stream(ro.eng.device)
+        self.starts, self.grp = starts, grp
+        self.lanes, self.active = (_ptr(ro.games_done), _ptr(ro.plies), _ptr(ro.sel)), _ptr(ro.active)
+        self.tr, self.tr_end = ({}, {}) if trace else (None, None)      # per step; added once at the end
+        self.rec = torch.empty(self.B, 64, dtype=torch.uint8, device=self.dev) if trace else None
+
+    def lane_buffers(self, n: int, dtype, fill=0):
+        return [torch.full((self.B,), fill, dtype=dtype, device=self.dev) for _ in range(n)]
+
+    def tally(self, fields):
+        return torch.zeros(self.P, len(fields), dtype=torch.int64, device=self.dev)
+
+    def traced(self, *fields):
+        """Per-step trace tensors [max_steps, B, ...] for (name, dtype, trailing shape...) fields."""
+        if self.tr is not None:
+            for name, dtype, *shape in fields:
+                self.tr[name] = torch.zeros(self.max_steps, self.B, *shape, dtype=dtype, device=self.dev)
+
+    def reset(self, mask):      # the masked bgx_reset: every masked lane gets its start record again
+        self.eng.reset(lane_mask=mask, want_obs=False)
+
+
+class _Stage:
+    """A mode of run_lanes: it owns its buffers, its `tally` (one more result after the trace)
+    and its trace fields, and hooks into the step loop where it needs to.  `sync_free`: the
+    stage never waits for the device, so the host may read the active-lane count rarely."""
+    sync_free = False
+    # the hooks, empty unless a stage defines them: after_begin(), before_act(step),
+    # after_step(done, info), after_advance(step)
+    after_begin = before_act = after_step = after_advance = staticmethod(lambda *args: None)
+
+
+class _LuckStage(_Stage):
+    """`luck` (a search.ValueHead; DESIGN.md "Luck adjustment"): every step first takes the luck
+    of the active lanes' rolls under that value head and adds it to their games (before act:
+    roll_luck on sel, luck_add; after the step: luck_flush; the host reads the active-lane
+    count every step, as roll_luck synchronises anyway).  The games are the same as without it.
+    Result: luck_tally int64[n_groups, 4] (LUCK_FIELDS); the trace gains the per-step luck
+    f32[steps, B] (NaN on lanes that never were active)."""
+
+    def __init__(self, c: _Pass, head):
+        self.c, self.head = c, head
+        self.tally = c.tally(LUCK_FIELDS)
+        self.buf, = c.lane_buffers(1, torch.float32, float("nan"))
+        c.ro.lane_luck.zero_()
+        c.traced(("luck", torch.float32))
+
+    def before_act(self, step):
+        from .search import roll_luck
+        c = self.c
+        roll_luck(c.eng, self.head, sel=c.ro.sel, out=(self.buf, None))
+        check(c.L.bgx_rollout_luck_add(c.recs, _ptr(c.starts), c.lanes[1], c.lanes[2], _ptr(self.buf), c.B,
+                                       _ptr(c.ro.lane_luck), c.stream), "bgx_rollout_luck_add")
+        if c.tr is not None:
+            c.tr["luck"][step] = self.buf
+
+    def after_step(self, done, info):
+        c = self.c
+        check(c.L.bgx_rollout_luck_flush(_ptr(c.starts), _ptr(c.grp), c.lanes[2], _ptr(done), _ptr(info), c.B, c.P,
+                                         _ptr(c.ro.lane_luck), _ptr(self.tally), c.stream), "bgx_rollout_luck_flush")
+
+
+class _CubeStage(_Stage):
+    """`cube` (a cube.CubeRule): money play with the doubling cube.  `cube0`
+    uint8[B] = the cube every game on the lane starts with (cube.pack(k, owner); None: centred
+    at 1 everywhere; ValueError names the first lane with an invalid byte).  After begin:
+    cube_begin; before act: cube_sel, equity, cube_decide, reset(mask); after the step:
+    cube_flush.  Before its roll, but never on a game's first ply, the side on roll may double by
+    the rule on its equity (the rule's value head or callable); a passed double ends the game at
+    the cube's value and the masked reset gives the lane its start record again.  The host reads
+    the active-lane count every step, as the equity synchronises.  Result: cube_tally
+    int64[n_groups, 8] (cube.CUBE_FIELDS); the trace gains per step cube uint8 (the state before
+    the decision), cube_mover (the side on roll there), cube_dsel (the lanes that may double),
+    cube_equity (NaN off cube_dsel) and cube_mask (the passes)."""
+
+    def __init__(self, c: _Pass, rule, cube0):
+        from .cube import CUBE_FIELDS, validate_cube0
+        self.c, self.rule = c, rule
+        self.c0 = (torch.zeros(c.B, dtype=torch.uint8, device=c.dev) if cube0 is None
+                   else torch.as_tensor(cube0).to(c.dev).contiguous())
+        if self.c0.shape != (c.B,) or self.c0.dtype != torch.uint8:
+            raise ValueError(f"run_lanes: cube0 must be uint8[{c.B}]")
+        validate_cube0(self.c0, rule.cap)
+        self.struct = rule.struct()
+        self.tally = c.tally(CUBE_FIELDS)
+        self.state, self.dsel, self.mask = c.lane_buffers(3, torch.uint8)
+        self.ebuf, self.escratch = c.lane_buffers(2, torch.float32, float("nan"))
+        c.traced(("cube", torch.uint8), ("cube_mover", torch.uint8), ("cube_dsel", torch.uint8),
+                 ("cube_equity", torch.float32), ("cube_mask", torch.uint8))
+
+    def after_begin(self):
+        c = self.c
+        check(c.L.bgx_rollout_cube_begin(_ptr(self.c0), c.B, self.rule.cap, _ptr(self.state), c.stream),
+              "bgx_rollout_cube_begin")
+
+    def before_act(self, step):
+        c, tr = self.c, self.c.tr
+        check(c.L.bgx_rollout_cube_sel(c.recs, _ptr(c.grp), c.P, c.lanes[1], c.lanes[2], _ptr(self.state), c.B,
+                                       self.rule.cap, _ptr(self.dsel), c.stream), "bgx_rollout_cube_sel")
+        eq = self.rule.equity(c.eng, self.dsel, self.escratch, self.ebuf)
+        if tr is not None:
+            c.eng.records(out=c.rec)
+            tr["cube"][step] = self.state
+            tr["cube_mover"][step] = c.rec[:, R_CUR]
+            tr["cube_dsel"][step] = self.dsel
+            tr["cube_equity"][step] = torch.where(self.dsel != 0, eq, float("nan"))
+        check(c.L.bgx_rollout_cube_decide(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(self.dsel), _ptr(eq), c.B, c.P,
+                                          c.G, self.struct, _ptr(self.c0), _ptr(self.state), *c.lanes,
+                                          _ptr(self.tally), c.active, _ptr(self.mask), c.stream),
+              "bgx_rollout_cube_decide")
+        if tr is not None:
+            tr["cube_mask"][step] = self.mask
+        c.reset(self.mask)
+
+    def after_step(self, done, info):
+        c = self.c
+        check(c.L.bgx_rollout_cube_flush(_ptr(c.starts), _ptr(c.grp), c.lanes[2], _ptr(done), _ptr(info), c.B, c.P,
+                                         self.struct, _ptr(self.c0), _ptr(self.state), _ptr(self.tally), c.stream),
+              "bgx_rollout_cube_flush")
+
+
+class _TableCutStage(_Stage):
+    """A game that reaches a bearoff table stops there: one cut and masked reset after begin
+    (after cube_begin) and one after every advance (the table's cut kernel, then the masked
+    bgx_reset gives every cut lane its start record again).  A start record that is in the table
+    itself is cut before a move is made; a lane's later games from it are cut after one ply.
+    The trace gains cut uint8[steps, B] (each step's reset mask), cut_records uint8[steps, B, 64]
+    (the records that cut saw) and cut0 / cut_records0, the same for the cut after begin.
+    `bearoff` (a bearoff.BearoffDB, DESIGN.md §11, or a bearoff.OneSidedBearoffDB, §12, which
+    cuts where both sides have a checker off; bgx_rollout_bearoff_cut / bgx_rollout_bearoff1_cut):
+    the game is scored with the table's win probability -> cut_tally int64[n_groups, 4] (CUT_FIELDS).
+    `cube_bearoff` (a bearoff.CubefulBearoffDB), with `cube`
+    (bgx_rollout_cube_bearoff_cut, which also takes the cube stage's cap, cube0 and state): a
+    cubeful game is scored with its exact cubeful expectation times its cube, and a lane that
+    enters the table is cut before its next cube decision -> after cube_tally, cube_cut_tally
+    int64[n_groups, 6] (cube.CUBE_CUT_FIELDS)."""
+    sync_free = True
+
+    def __init__(self, c: _Pass, table, cube: _CubeStage = None):
+        self.c, self.table = c, table
+        if table.kind == "cubeful":
+            from .cube import CUBE_CUT_FIELDS
+            what, fields, self.entry = "cubeful bearoff table", CUBE_CUT_FIELDS, "bgx_rollout_cube_bearoff_cut"
+            self.extra = (cube.rule.cap, _ptr(cube.c0), _ptr(cube.state))
+        else:
+            what, fields, self.entry, self.extra = "bearoff database", CUT_FIELDS, table.cut_entry, ()
+        if table.device != c.dev:
+            raise ValueError(f"run_lanes: the {what} is on {table.device}, the engine on {c.dev}")
+        self.tally = c.tally(fields)
+        self.mask = torch.empty(c.B, dtype=torch.uint8, device=c.dev)
+        c.traced(("cut", torch.uint8), ("cut_records", torch.uint8, 64))
+
+    def cut(self, step):
+        c = self.c
+        if c.tr is not None:
+            c.eng.records(out=c.rec)
+        check(getattr(c.L, self.entry)(self.table.handle(), c.recs, _ptr(c.starts), _ptr(c.grp), c.B, c.P, c.G,
+                                       *c.lanes, _ptr(self.tally), c.active, _ptr(self.mask), *self.extra, c.stream),
+              self.entry)
+        if c.tr is not None and step is not None:
+            c.tr["cut"][step] = self.mask
+            c.tr["cut_records"][step] = c.rec
+        c.reset(self.mask)
+
+    def after_begin(self):
+        self.cut(None)
+        if self.c.tr is not None:
+            self.c.tr_end.update(cut0=self.mask.clone(), cut_records0=self.c.rec.clone())
+
+    after_advance = cut
+
+
+class _TruncStage(_Stage):
+    """`truncate` (a truncate.Truncation): a game that has run truncate.plies plies
+    without ending stops there and is scored with the truncation's value of the side on roll.
+    After advance: trunc_sel, value, trunc_cut, reset(mask) -- the cut sits where the bearoff cut
+    sits, where the truncated game's luck sum is complete (the roll now in the record is added
+    only at the next step), and the masked reset gives the lane its start record again.  With a
+    value head at lookahead 0 the stage is sync-free.  `with_luck`: the luck stage runs too and
+    trunc_cut also takes and clears the truncated games' luck sums (summarize_truncated_luck).
+    Result (after luck_tally, if any): trunc_tally int64[n_groups, 7] (truncate.TRUNC_FIELDS);
+    the trace gains per step trunc uint8 (the lanes truncated), trunc_value (NaN off them) and
+    trunc_mover (the side on roll there)."""
+
+    def __init__(self, c: _Pass, truncation, with_luck: bool):
+        self.c, self.t, self.sync_free = c, truncation, truncation.sync_free
+        self.luck = _ptr(c.ro.lane_luck) if with_luck else None
+        self.tally = c.tally(TRUNC_FIELDS)
+        self.tsel, self.mask = c.lane_buffers(2, torch.uint8)
+        self.buf, self.scratch = c.lane_buffers(2, torch.float32, float("nan"))
+        c.traced(("trunc", torch.uint8), ("trunc_value", torch.float32), ("trunc_mover", torch.uint8))
+
+    def after_advance(self, step):
+        c, tr = self.c, self.c.tr
+        check(c.L.bgx_rollout_trunc_sel(c.recs, _ptr(c.grp), c.B, c.P, self.t.plies, c.lanes[1], c.lanes[2],
+                                        _ptr(self.tsel), None, c.stream), "bgx_rollout_trunc_sel")
+        tv = self.t.equity(c.eng, self.tsel, self.scratch, self.buf)
+        if tr is not None:
+            c.eng.records(out=c.rec)
+            tr["trunc"][step] = self.tsel
+            tr["trunc_value"][step] = torch.where(self.tsel != 0, tv, float("nan"))
+            tr["trunc_mover"][step] = c.rec[:, R_CUR]
+        check(c.L.bgx_rollout_trunc_cut(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(self.tsel), _ptr(tv), self.t.scale,
+                                        c.B, c.P, c.G, *c.lanes, self.luck, _ptr(self.tally), c.active,
+                                        _ptr(self.mask), c.stream), "bgx_rollout_trunc_cut")
+        c.reset(self.mask)
+
+
 class Rollout:
     """`batch` lanes of an engine of its own (auto_reset, so a finished game's lane starts
     its next one, from its start record, in the same step)."""
@@ -339,262 +582,92 @@ class Rollout:
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
-        [act, step, advance] until no lane is active or `max_steps` env steps ran; the host
-        reads the active-lane count every SYNC_EVERY steps for a sync-free player.  The
-        engine keeps the table afterwards.  Returns (tally int64[n_groups, 8], unfinished
-        int64[n_groups] = scheduled games that did not end, trace): trace (None without
-        trace=True) holds per-step [steps, B] tensors mover, action, done, info, and the final
-        games_done and active.
+        [act, merge, step, advance] until no lane is active or `max_steps` env steps ran; the
+        host reads the active-lane count every SYNC_EVERY steps when the player and every stage
+        are sync-free, else every step.  The engine keeps the table afterwards.  Returns (tally
+        int64[n_groups, 8], unfinished int64[n_groups] = scheduled games that did not end, trace)
+        followed by one tally per mode, in the stages' order below: trace (None without
+        trace=True) holds per-step [steps, B] tensors mover, action, done, info, the modes'
+        fields, and the final games_done and active.
 
-        `luck` (a search.ValueHead; DESIGN.md "Luck adjustment"): every step first takes the
-        luck of the active lanes' rolls under that value head and adds it to their games
-        (roll_luck on sel, luck_add, act, step, luck_flush, advance; the host reads the
-        active-lane count every step, as roll_luck synchronises anyway).  The games are the
-        same as without it.  A fourth result follows the trace: luck_tally int64[n_groups, 4]
-        (LUCK_FIELDS), and the trace gains the per-step luck f32[steps, B] (NaN on lanes
-        that never were active).  None: exactly the three results above.
+        Every mode is a stage (the classes above; their docstrings say what each does per step,
+        returns and traces).  The loop calls them in a fixed order -- luck, cube, table cut,
+        truncation -- after begin, before act, after the step (before advance) and after advance:
 
-        `bearoff` (a bearoff.BearoffDB, DESIGN.md §11, or a bearoff.OneSidedBearoffDB, §12,
-        which cuts where both sides have a checker off): a game that reaches the table stops
-        there -- [act, merge, step, advance, cut, reset(mask)] per step and one cut and reset
-        after begin (the table's cut, bgx_rollout_bearoff_cut or bgx_rollout_bearoff1_cut,
-        then the masked bgx_reset gives every cut lane
-        its start record again).  A start record that is in the table itself is cut before a
-        move is made; a lane's later games from it are cut after one ply.  A further result
-        follows the trace: cut_tally int64[n_groups, 4] (CUT_FIELDS), and the trace gains
-        cut uint8[steps, B] (each step's reset mask), cut_records uint8[steps, B, 64] (the
-        records that cut saw) and cut0 / cut_records0, the same for the cut after begin.
-        Together with `luck` it raises ValueError (the combined estimator needs cross sums
-        that are not kept).  None: nothing changes.
+            begin; cube_begin; cut, reset(mask)
+            [ roll_luck, luck_add;  cube_sel, equity, cube_decide, reset(mask);
+              act, merge, step;  luck_flush;  cube_flush;  advance;
+              cut, reset(mask);  trunc_sel, value, trunc_cut, reset(mask) ]
 
-        `cube` (a cube.CubeRule): money play with the doubling cube.  `cube0`
-        uint8[B] = the cube every game on the lane starts with (cube.pack(k, owner); None:
-        centred at 1 everywhere; ValueError names the first lane with an invalid byte).  Per
-        step [cube_sel, equity, cube_decide, reset(mask), act, merge, step, cube_flush,
-        advance] and cube_begin after begin: before its roll, but never on a game's first ply,
-        the side on roll may double by the rule on its equity (the rule's value head or
-        callable); a passed double ends the game at the cube's value and the masked reset
-        gives the lane its start record again.  The host reads the active-lane count every
-        step, as the equity synchronises.  A further result follows the trace: cube_tally
-        int64[n_groups, 8] (cube.CUBE_FIELDS), and the trace gains per step cube uint8 (the
-        state before the decision), cube_mover (the side on roll there), cube_dsel (the lanes
-        that may double), cube_equity (NaN off cube_dsel) and cube_mask (the passes).  Together
-        with `luck` or `bearoff` it raises ValueError: the luck of a cubeful game and cubeful
-        table values do not exist.  None: nothing changes.
+        `luck` (a search.ValueHead): the luck of every roll, summed per game -> luck_tally.
+        `bearoff` (a bearoff.BearoffDB or OneSidedBearoffDB): games stop at the table -> cut_tally.
+        `cube` (a cube.CubeRule), `cube0` (uint8[B] start cubes): the doubling cube -> cube_tally.
+        `truncate` (a truncate.Truncation): games stop at a horizon, scored by a value -> trunc_tally.
+        `cube_bearoff` (a bearoff.CubefulBearoffDB), with `cube`: cubeful games stop at the cubeful
+        table -> cube_tally, cube_cut_tally.
+        Each None: nothing changes; all None: exactly the three results above.
 
-        `truncate` (a truncate.Truncation): a game that has run truncate.plies
-        plies without ending stops there and is scored with the truncation's value of the side
-        on roll.  Per step [roll_luck, luck_add,] act, merge, step, [luck_flush,] advance,
-        trunc_sel, value, trunc_cut, reset(mask): the cut sits where the bearoff cut sits, where
-        the truncated game's luck sum is complete (the roll now in the record is added only at
-        the next step), and the masked reset gives the lane its start record again.  With a
-        sync-free player, a value head at lookahead 0 and no luck the host keeps reading the
-        active-lane count every SYNC_EVERY steps; else every step.  A further result follows
-        the trace -- with `luck`, it follows luck_tally --: trunc_tally int64[n_groups, 7]
-        (truncate.TRUNC_FIELDS), and the trace gains per step trunc uint8 (the lanes truncated),
-        trunc_value (NaN off them) and trunc_mover (the side on roll there).  Together with
-        `luck` it is supported (summarize_truncated_luck); together with `bearoff` or `cube` it
-        raises ValueError (the three-way summaries do not exist).  None: nothing changes.
-
-        `cube_bearoff` (a bearoff.CubefulBearoffDB), with `cube`: a cubeful game
-        that reaches the cubeful table stops there and is scored with its exact cubeful
-        expectation times its cube -- the cube loop followed by [cube_bearoff_cut, reset(mask)],
-        and one cut and reset after cube_begin, so a lane that enters the table is cut before its
-        next cube decision.  A further result follows cube_tally: cube_cut_tally int64[n_groups, 6]
-        (cube.CUBE_CUT_FIELDS), and the trace gains cut, cut_records, cut0 and cut_records0 as with
-        `bearoff`.  Without `cube`, or together with `luck`, `bearoff` or `truncate`, it raises
-        ValueError.  None: nothing changes."""
-        if cube_bearoff is not None:
-            if cube is None:
-                raise ValueError("run_lanes: cube_bearoff without cube")
-            for name, other in (("luck", luck), ("bearoff", bearoff), ("truncate", truncate)):
-                if other is not None:
-                    raise ValueError(f"run_lanes: cube_bearoff together with {name} is not supported")
-            if getattr(cube_bearoff, "kind", None) != "cubeful":
-                raise ValueError("run_lanes: cube_bearoff must be a bearoff.CubefulBearoffDB")
-        if truncate is not None and (bearoff is not None or cube is not None):
-            raise ValueError(f"run_lanes: truncate together with {'bearoff' if bearoff is not None else 'cube'} "
-                             "is not supported")
-        if truncate is not None and not isinstance(truncate, Truncation):
-            raise ValueError("run_lanes: truncate must be a truncate.Truncation")
-        if luck is not None and bearoff is not None:
-            raise ValueError("run_lanes: bearoff together with luck is not supported")
-        if cube is not None and luck is not None:
-            raise ValueError("run_lanes: cube together with luck is not supported")
-        if cube is not None and bearoff is not None:
-            raise ValueError("run_lanes: cube together with bearoff is not supported")
-        if cube is None and cube0 is not None:
-            raise ValueError("run_lanes: cube0 without cube")
+        Together: `truncate` with `luck` IS supported (..., luck_tally, trunc_tally;
+        summarize_truncated_luck) and `cube_bearoff` needs `cube`.  Every other pair raises
+        ValueError (_check_modes): `bearoff` with `luck` needs cross sums that are not kept, the
+        luck of a cubeful game and cubeful values of the cubeless table do not exist (`cube` with
+        `luck` or `bearoff`), nor do three-way summaries (`truncate` or `cube_bearoff` with others)."""
+        _check_modes("run_lanes", luck, bearoff, cube, truncate, cube_bearoff, cube0, types=True)
         max_steps, G, P = int(max_steps), int(games_per_lane), int(n_groups)
         if max_steps < 0 or G < 0 or P <= 0:
             raise ValueError(f"run_lanes: max_steps {max_steps}, games_per_lane {G} must be >= 0, n_groups {P} > 0")
         if trace and self.B * max_steps > TRACE_LIMIT:
             raise ValueError(f"run_lanes: trace=True holds batch x max_steps = {self.B * max_steps} entries per "
                              f"field; the limit is {TRACE_LIMIT} (it is for tests and small batches)")
-        L, eng, dev = _lib.load(), self.eng, self.eng.device
+        eng, dev = self.eng, self.eng.device
         starts = torch.as_tensor(starts)
         grp = torch.as_tensor(group).to(device=dev, dtype=torch.int32).contiguous()
         if grp.shape != (self.B,) or bool((grp >= P).any()):
             raise ValueError(f"run_lanes: group must be int32[{self.B}] with entries below n_groups = {P}")
-        recs = ctypes.c_void_p(eng.lanes_ptr())
-        tally = torch.zeros(P, 8, dtype=torch.int64, device=dev)
-        state = (_ptr(self.games_done), _ptr(self.plies), _ptr(self.sel), _ptr(tally), _ptr(self.active))
         eng.set_starts(starts)              # validated where the records live (the host, from run())
-        starts = starts.to(dev).contiguous()    # the kernels' copy: the start movers
+        # the kernels' copy of starts: the start movers
+        c = _Pass(self, starts.to(dev).contiguous(), grp, P, G, max_steps, trace)
+        L, tr, rec = c.L, c.tr, c.rec
+        tally = torch.zeros(P, 8, dtype=torch.int64, device=dev)
         eng.reset(want_obs=False)
-        check(L.bgx_rollout_begin(recs, _ptr(starts), _ptr(grp), self.B, P, G, *state, _stream(dev)),
-              "bgx_rollout_begin")
-        if cube is not None:
-            from .cube import CUBE_FIELDS, validate_cube0
-            c0 = (torch.zeros(self.B, dtype=torch.uint8, device=dev) if cube0 is None
-                  else torch.as_tensor(cube0).to(dev).contiguous())
-            if c0.shape != (self.B,) or c0.dtype != torch.uint8:
-                raise ValueError(f"run_lanes: cube0 must be uint8[{self.B}]")
-            validate_cube0(c0, cube.cap)
-            rule = cube.struct()
-            cube_tally = torch.zeros(P, len(CUBE_FIELDS), dtype=torch.int64, device=dev)
-            cstate, dsel, cmask = (torch.zeros(self.B, dtype=torch.uint8, device=dev) for _ in range(3))
-            ebuf, escratch = (torch.full((self.B,), float("nan"), dtype=torch.float32, device=dev) for _ in range(2))
-            check(L.bgx_rollout_cube_begin(_ptr(c0), self.B, cube.cap, _ptr(cstate), _stream(dev)),
-                  "bgx_rollout_cube_begin")
-        if luck is not None:
-            from .search import roll_luck
-            luck_tally = torch.zeros(P, len(LUCK_FIELDS), dtype=torch.int64, device=dev)
-            lbuf = torch.full((self.B,), float("nan"), dtype=torch.float32, device=dev)
-            self.lane_luck.zero_()
-        if truncate is not None:
-            trunc_tally = torch.zeros(P, len(TRUNC_FIELDS), dtype=torch.int64, device=dev)
-            tsel, tmask = (torch.zeros(self.B, dtype=torch.uint8, device=dev) for _ in range(2))
-            tbuf, tscratch = (torch.full((self.B,), float("nan"), dtype=torch.float32, device=dev) for _ in range(2))
-        tr = None
-        if trace:
-            tr = {n: torch.zeros(max_steps, self.B, dtype=dt, device=dev)
-                  for n, dt in (("mover", torch.uint8), ("action", torch.int32), ("done", torch.uint8),
-                                ("info", torch.int32)) + ((("luck", torch.float32),) if luck is not None else ())
-                  + ((("cube", torch.uint8), ("cube_mover", torch.uint8), ("cube_dsel", torch.uint8),
-                      ("cube_equity", torch.float32), ("cube_mask", torch.uint8)) if cube is not None else ())
-                  + ((("trunc", torch.uint8), ("trunc_value", torch.float32), ("trunc_mover", torch.uint8))
-                     if truncate is not None else ())}
-            rec = torch.empty(self.B, 64, dtype=torch.uint8, device=dev)
-        if bearoff is not None:
-            if bearoff.device != dev:
-                raise ValueError(f"run_lanes: the bearoff database is on {bearoff.device}, the engine on {dev}")
-            cut_tally = torch.zeros(P, len(CUT_FIELDS), dtype=torch.int64, device=dev)
-            mask = torch.empty(self.B, dtype=torch.uint8, device=dev)
-            if trace:
-                tr["cut"] = torch.zeros(max_steps, self.B, dtype=torch.uint8, device=dev)
-                tr["cut_records"] = torch.zeros(max_steps, self.B, 64, dtype=torch.uint8, device=dev)
-
-            def cut(step):
-                if trace:
-                    eng.records(out=rec)
-                check(getattr(L, bearoff.cut_entry)(bearoff.handle(), recs, _ptr(starts), _ptr(grp), self.B, P, G,
-                                                    _ptr(self.games_done), _ptr(self.plies), _ptr(self.sel),
-                                                    _ptr(cut_tally), _ptr(self.active), _ptr(mask), _stream(dev)),
-                      bearoff.cut_entry)
-                if trace and step is not None:
-                    tr["cut"][step] = mask
-                    tr["cut_records"][step] = rec
-                eng.reset(lane_mask=mask, want_obs=False)
-
-            cut(None)
-            cut_begin = (mask.clone(), rec.clone()) if trace else None
-        if cube_bearoff is not None:
-            from .cube import CUBE_CUT_FIELDS
-            if cube_bearoff.device != dev:
-                raise ValueError(f"run_lanes: the cubeful bearoff table is on {cube_bearoff.device}, the engine on {dev}")
-            cube_cut_tally = torch.zeros(P, len(CUBE_CUT_FIELDS), dtype=torch.int64, device=dev)
-            mask = torch.empty(self.B, dtype=torch.uint8, device=dev)
-            if trace:
-                tr["cut"] = torch.zeros(max_steps, self.B, dtype=torch.uint8, device=dev)
-                tr["cut_records"] = torch.zeros(max_steps, self.B, 64, dtype=torch.uint8, device=dev)
-
-            def cube_cut(step):
-                if trace:
-                    eng.records(out=rec)
-                check(L.bgx_rollout_cube_bearoff_cut(cube_bearoff.handle(), recs, _ptr(starts), _ptr(grp), self.B, P, G,
-                                                     _ptr(self.games_done), _ptr(self.plies), _ptr(self.sel),
-                                                     _ptr(cube_cut_tally), _ptr(self.active), _ptr(mask), cube.cap,
-                                                     _ptr(c0), _ptr(cstate), _stream(dev)),
-                      "bgx_rollout_cube_bearoff_cut")
-                if trace and step is not None:
-                    tr["cut"][step] = mask
-                    tr["cut_records"][step] = rec
-                eng.reset(lane_mask=mask, want_obs=False)
-
-            cube_cut(None)
-            cut_begin = (mask.clone(), rec.clone()) if trace else None
-        every = (SYNC_EVERY if getattr(player, "sync_free", False) and luck is None and cube is None
-                 and (truncate is None or truncate.sync_free) else 1)
+        check(L.bgx_rollout_begin(c.recs, _ptr(c.starts), _ptr(grp), self.B, P, G, *c.lanes, _ptr(tally), c.active,
+                                  c.stream), "bgx_rollout_begin")
+        c.traced(("mover", torch.uint8), ("action", torch.int32), ("done", torch.uint8), ("info", torch.int32))
+        table = bearoff if bearoff is not None else cube_bearoff
+        luck_stage = _LuckStage(c, luck) if luck is not None else None
+        cube_stage = _CubeStage(c, cube, cube0) if cube is not None else None
+        cut_stage = _TableCutStage(c, table, cube_stage) if table is not None else None
+        trunc_stage = _TruncStage(c, truncate, luck is not None) if truncate is not None else None
+        stages = [s for s in (luck_stage, cube_stage, cut_stage, trunc_stage) if s is not None]
+        for s in stages:
+            s.after_begin()
+        every = SYNC_EVERY if getattr(player, "sync_free", False) and all(s.sync_free for s in stages) else 1
         steps = 0
         active = int(self.active.item())
         while active > 0 and steps < max_steps:
-            if luck is not None:
-                roll_luck(eng, luck, sel=self.sel, out=(lbuf, None))
-                check(L.bgx_rollout_luck_add(recs, _ptr(starts), _ptr(self.plies), _ptr(self.sel), _ptr(lbuf), self.B,
-                                             _ptr(self.lane_luck), _stream(dev)), "bgx_rollout_luck_add")
-                if trace:
-                    tr["luck"][steps] = lbuf
-            if cube is not None:
-                check(L.bgx_rollout_cube_sel(recs, _ptr(grp), P, _ptr(self.plies), _ptr(self.sel), _ptr(cstate), self.B,
-                                             cube.cap, _ptr(dsel), _stream(dev)), "bgx_rollout_cube_sel")
-                eq = cube.equity(eng, dsel, escratch, ebuf)
-                if trace:
-                    eng.records(out=rec)
-                    tr["cube"][steps] = cstate
-                    tr["cube_mover"][steps] = rec[:, R_CUR]
-                    tr["cube_dsel"][steps] = dsel
-                    tr["cube_equity"][steps] = torch.where(dsel != 0, eq, float("nan"))
-                check(L.bgx_rollout_cube_decide(recs, _ptr(starts), _ptr(grp), _ptr(dsel), _ptr(eq), self.B, P, G, rule,
-                                                _ptr(c0), _ptr(cstate), _ptr(self.games_done), _ptr(self.plies),
-                                                _ptr(self.sel), _ptr(cube_tally), _ptr(self.active), _ptr(cmask),
-                                                _stream(dev)), "bgx_rollout_cube_decide")
-                if trace:
-                    tr["cube_mask"][steps] = cmask
-                eng.reset(lane_mask=cmask, want_obs=False)
+            for s in stages:
+                s.before_act(steps)
             act = player.act(eng, self.sel, self.steps)
             if (not isinstance(act, torch.Tensor) or act.dtype != torch.int32 or act.device != dev
                     or not act.is_contiguous() or act.numel() != self.B):
                 raise ValueError("a player's act must return a contiguous int32[B] tensor on the engine's device")
             # actions = sel ? act : 0 (the arena's merge with one player on both sides)
             check(L.bgx_arena_merge(_ptr(self.sel), _ptr(self.sel), _ptr(act), _ptr(act), self.B,
-                                    _ptr(self.actions), _stream(dev)), "bgx_arena_merge")
+                                    _ptr(self.actions), c.stream), "bgx_arena_merge")
             if trace:
                 eng.records(out=rec)
                 tr["mover"][steps] = rec[:, R_CUR]
                 tr["action"][steps] = self.actions
             _, _, done, info = eng.step(self.actions, want_obs=False, want_info=True)
-            if luck is not None:
-                check(L.bgx_rollout_luck_flush(_ptr(starts), _ptr(grp), _ptr(self.sel), _ptr(done), _ptr(info), self.B,
-                                               P, _ptr(self.lane_luck), _ptr(luck_tally), _stream(dev)),
-                      "bgx_rollout_luck_flush")
-            if cube is not None:
-                check(L.bgx_rollout_cube_flush(_ptr(starts), _ptr(grp), _ptr(self.sel), _ptr(done), _ptr(info), self.B, P,
-                                               rule, _ptr(c0), _ptr(cstate), _ptr(cube_tally), _stream(dev)),
-                      "bgx_rollout_cube_flush")
-            check(L.bgx_rollout_advance(recs, _ptr(starts), _ptr(grp), _ptr(done), _ptr(info), self.B, P, G,
-                                        *state, _stream(dev)), "bgx_rollout_advance")
+            for s in stages:
+                s.after_step(done, info)
+            check(L.bgx_rollout_advance(c.recs, _ptr(c.starts), _ptr(grp), _ptr(done), _ptr(info), self.B, P, G,
+                                        *c.lanes, _ptr(tally), c.active, c.stream), "bgx_rollout_advance")
             if trace:
                 tr["done"][steps] = done
                 tr["info"][steps] = info
-            if bearoff is not None:
-                cut(steps)
-            if cube_bearoff is not None:
-                cube_cut(steps)
-            if truncate is not None:
-                check(L.bgx_rollout_trunc_sel(recs, _ptr(grp), self.B, P, truncate.plies, _ptr(self.plies),
-                                              _ptr(self.sel), _ptr(tsel), None, _stream(dev)), "bgx_rollout_trunc_sel")
-                tv = truncate.equity(eng, tsel, tscratch, tbuf)
-                if trace:
-                    eng.records(out=rec)
-                    tr["trunc"][steps] = tsel
-                    tr["trunc_value"][steps] = torch.where(tsel != 0, tv, float("nan"))
-                    tr["trunc_mover"][steps] = rec[:, R_CUR]
-                check(L.bgx_rollout_trunc_cut(recs, _ptr(starts), _ptr(grp), _ptr(tsel), _ptr(tv), truncate.scale,
-                                              self.B, P, G, _ptr(self.games_done), _ptr(self.plies), _ptr(self.sel),
-                                              _ptr(self.lane_luck) if luck is not None else None, _ptr(trunc_tally),
-                                              _ptr(self.active), _ptr(tmask), _stream(dev)), "bgx_rollout_trunc_cut")
-                eng.reset(lane_mask=tmask, want_obs=False)
+            for s in stages:
+                s.after_advance(steps)
             steps += 1
             self.steps += 1
             if steps % every == 0 or steps == max_steps:
@@ -603,19 +676,8 @@ class Rollout:
         unfinished = torch.zeros(P, dtype=torch.int64, device=dev).index_add_(0, grp.clamp(min=0).long(), left)
         if trace:
             tr = {n: v[:steps] for n, v in tr.items()}
-            tr.update(games_done=self.games_done.clone(), active=int(self.active.item()))
-            if bearoff is not None or cube_bearoff is not None:
-                tr.update(cut0=cut_begin[0], cut_records0=cut_begin[1])
-        if bearoff is not None:
-            return tally, unfinished, tr, cut_tally
-        if cube_bearoff is not None:
-            return tally, unfinished, tr, cube_tally, cube_cut_tally
-        if cube is not None:
-            return tally, unfinished, tr, cube_tally
-        if truncate is not None:
-            return ((tally, unfinished, tr, trunc_tally) if luck is None
-                    else (tally, unfinished, tr, luck_tally, trunc_tally))
-        return (tally, unfinished, tr) if luck is None else (tally, unfinished, tr, luck_tally)
+            tr.update(c.tr_end, games_done=self.games_done.clone(), active=int(self.active.item()))
+        return (tally, unfinished, tr) + tuple(s.tally for s in stages)
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
             trace: bool = False, luck=None, luck_scale="fit", bearoff=None, cube=None, cube_start=(0, 0),
@@ -625,42 +687,26 @@ class Rollout:
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
         (the rest is reported as `unfinished`); standard openings again afterwards.  Returns
         the list of the positions' results (summarize); with trace=True also the last
-        pass's trace with its group, starts and games_per_lane.  `luck` (a search.ValueHead):
-        the luck-adjusted rollout (run_lanes); the results are summarize_luck's, with
-        `luck_scale` ("fit" or a float) as its scale.  `bearoff` (a bearoff.BearoffDB or
-        bearoff.OneSidedBearoffDB): the rollout cut at the bearoff table (run_lanes); the results
-        are summarize_bearoff's.  With the one-sided table they also carry
-        `bearoff_kind` = "one-sided": its cut values are approximations, so `equity_stderr` is
-        the sample's spread and no longer measures the error against the truth.  Not together
-        with `luck` (ValueError).  `cube` (a cube.CubeRule): money play with the
-        doubling cube (run_lanes); every game starts with the cube `cube_start` = (k, owner),
-        owner 0 centred, 1 PLAYER1, 2 PLAYER2, or one such pair per position; the results are
-        cube.summarize_cube's.  Not together with `luck` or `bearoff` (ValueError).  `truncate` (a
-        truncate.Truncation): games stop at its horizon and are scored with its
-        value (run_lanes); the results are summarize_truncated's, with `luck` those of
-        summarize_truncated_luck.  Not together with `bearoff` or `cube` (ValueError).
-        `cube_bearoff` (a bearoff.CubefulBearoffDB), with `cube`: the cubeful cut
-        (run_lanes); the results are cube.summarize_cube_bearoff's and carry `bearoff_kind` =
-        "cubeful".  Without `cube`, or together with `luck`, `bearoff` or `truncate`: ValueError."""
-        if cube_bearoff is not None:
-            if cube is None:
-                raise ValueError("run: cube_bearoff without cube")
-            for name, other in (("luck", luck), ("bearoff", bearoff), ("truncate", truncate)):
-                if other is not None:
-                    raise ValueError(f"run: cube_bearoff together with {name} is not supported")
-        if truncate is not None and (bearoff is not None or cube is not None):
-            raise ValueError(f"run: truncate together with {'bearoff' if bearoff is not None else 'cube'} is not "
-                             "supported")
-        if luck is not None and bearoff is not None:
-            raise ValueError("run: bearoff together with luck is not supported")
-        if cube is not None and (luck is not None or bearoff is not None):
-            raise ValueError(f"run: cube together with {'luck' if luck is not None else 'bearoff'} is not supported")
+        pass's trace with its group, starts and games_per_lane.  The modes are run_lanes' (its
+        stages; the combinations it refuses raise ValueError here too, before anything runs):
+        `luck` (a search.ValueHead): the results are summarize_luck's, with `luck_scale` ("fit" or a
+        float) as its scale.  `bearoff` (a bearoff.BearoffDB or bearoff.OneSidedBearoffDB): the
+        results are summarize_bearoff's; with the one-sided table they also carry `bearoff_kind` =
+        "one-sided": its cut values are approximations, so `equity_stderr` is the sample's spread
+        and no longer measures the error against the truth.  `cube` (a cube.CubeRule; DESIGN.md
+        §13): every game starts with the cube `cube_start` = (k, owner), owner 0 centred, 1
+        PLAYER1, 2 PLAYER2, or one such pair per position; the results are cube.summarize_cube's.
+        `truncate` (a truncate.Truncation): the results are summarize_truncated's,
+        with `luck` those of summarize_truncated_luck.  `cube_bearoff` (a bearoff.CubefulBearoffDB;
+        DESIGN.md §15), with `cube`: the results are cube.summarize_cube_bearoff's and carry
+        `bearoff_kind` = "cubeful"."""
+        _check_modes("run", luck, bearoff, cube, truncate, cube_bearoff)
         pos = _records(positions)
         P = pos.shape[0]
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
-        total = unfinished = tr = ltotal = ttotal = cctotal = None
+        totals = tr = None
         if cube is not None:
-            from .cube import pack, summarize_cube
+            from .cube import pack
             cs = np.asarray(cube_start, np.int64)
             if cs.shape not in ((2,), (P, 2)):
                 raise ValueError(f"run: cube_start must be (k, owner) or one pair per position, got shape {cs.shape}")
@@ -669,51 +715,37 @@ class Rollout:
             grp = torch.from_numpy(group[k])
             starts = pos[grp.clamp(min=0).long()].clone()          # idle lanes: a valid record, never counted
             starts[:, R_ROLL0:R_ROLL1 + 1] = torch.from_numpy(roll[k])
-            out = self.run_lanes(player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck,
-                                 bearoff=bearoff, cube=cube,
-                                 cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None,
-                                 truncate=truncate, cube_bearoff=cube_bearoff)
-            tally, unf, tr = out[:3]
-            if cube_bearoff is not None:
-                cctotal = out[4] if cctotal is None else cctotal + out[4]
-            if truncate is not None:
-                ttotal = out[-1] if ttotal is None else ttotal + out[-1]
-            if luck is not None or bearoff is not None or cube is not None:
-                ltotal = out[3] if ltotal is None else ltotal + out[3]
-            total = tally if total is None else total + tally
-            unfinished = unf if unfinished is None else unfinished + unf
+            tally, unf, tr, *extra = self.run_lanes(
+                player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck, bearoff=bearoff, cube=cube,
+                cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None, truncate=truncate,
+                cube_bearoff=cube_bearoff)
+            sums = [tally, unf] + extra                            # the modes' tallies in run_lanes' order
+            totals = sums if totals is None else [a + b for a, b in zip(totals, sums)]
             if trace:
                 tr.update(group=grp, starts=starts, games_per_lane=G)
         self.eng.set_starts(None)
-        rows, unf = total.cpu().tolist(), unfinished.cpu().tolist()
-        if truncate is not None:
-            trows = ttotal.cpu().tolist()
-            if luck is not None:
-                lrows = ltotal.cpu().tolist()
-                res = [summarize_truncated_luck(rows[p], lrows[p], trows[p], luck_scale, unf[p]) for p in range(P)]
-            else:
-                res = [summarize_truncated(rows[p], trows[p], unf[p]) for p in range(P)]
-        elif luck is not None:
-            lrows = ltotal.cpu().tolist()
-            res = [summarize_luck(rows[p], lrows[p], luck_scale, unf[p]) for p in range(P)]
-        elif bearoff is not None:
-            crows = ltotal.cpu().tolist()
-            res = [summarize_bearoff(rows[p], crows[p], unf[p]) for p in range(P)]
-            if bearoff.kind != "two-sided":
-                for r in res:
-                    r["bearoff_kind"] = bearoff.kind
-        elif cube_bearoff is not None:
-            from .cube import summarize_cube_bearoff
-            crows, ccrows = ltotal.cpu().tolist(), cctotal.cpu().tolist()
-            res = [summarize_cube_bearoff(rows[p], crows[p], ccrows[p], unf[p]) for p in range(P)]
+        rows, unf, *extra = (t.cpu().tolist() for t in totals)
+        summary = _summary(luck, bearoff, cube, truncate, cube_bearoff)
+        scale = () if luck is None else (luck_scale,)
+        res = [summary(rows[p], *(e[p] for e in extra), *scale, unf[p]) for p in range(P)]
+        table = bearoff if bearoff is not None else cube_bearoff
+        if table is not None and table.kind != "two-sided":
             for r in res:
-                r["bearoff_kind"] = cube_bearoff.kind
-        elif cube is not None:
-            crows = ltotal.cpu().tolist()
-            res = [summarize_cube(rows[p], crows[p], unf[p]) for p in range(P)]
-        else:
-            res = [summarize(rows[p], unf[p]) for p in range(P)]
+                r["bearoff_kind"] = table.kind
         return (res, tr) if trace else res
+
+
+def _summary(luck, bearoff, cube, truncate, cube_bearoff):
+    """The summary of a position's rows by the modes of the run (after _check_modes): a function
+    (tally_row, *the modes' rows in run_lanes' order, [luck_scale with luck,] unfinished)."""
+    if cube is not None:
+        from .cube import summarize_cube, summarize_cube_bearoff
+        return summarize_cube_bearoff if cube_bearoff is not None else summarize_cube
+    if truncate is not None:
+        return summarize_truncated_luck if luck is not None else summarize_truncated
+    if luck is not None:
+        return summarize_luck
+    return summarize_bearoff if bearoff is not None else summarize
 
 
 def exact_score(after52, mover: int) -> int:

@@ -129,6 +129,7 @@ BO_HD int bo_successors(uint32_t pack, int r0, int r1, BoSet& s) {
 
 #if !defined(BGX_BEAROFF_HOST_ONLY) && !defined(BGX_BEAROFF_PART1_ONLY)
 // ======================================================================== part 2 ==
+#include "bg_rollout.h"
 
 // The object behind the C ABI's opaque bgx_bearoff*: device buffers, fixed after creation.
 struct bgx_bearoff {
@@ -363,30 +364,18 @@ __global__ __launch_bounds__(256) void k_bo_cut(const uint8_t* __restrict__ recs
             const float w = W[(size_t)idx[m] * n + idx[1 - m]];
             const float q = rec.at(R_CUR) == (int)starts[(size_t)i * 64 + R_CUR] ? w : __fsub_rn(1.0f, w);
             pq = min(max(llrintf(__fmul_rn(q, 1048576.0f)), 0ll), 1048576ll);
-            pl = plies[i];
-            plies[i] = 0;
-            const int gd = games_done[i] + 1;
-            games_done[i] = gd;
-            retired = gd >= G;
-            if (retired) sel[i] = 0;
+            retired = end_game(i, G, games_done, plies, sel, &pl);
         }
     }
     if (i < n_rec) mask[i] = cut ? 1 : 0;
-    // every thread of the wave reaches the ballots
-    uint64_t rest = __ballot(cut);
-    while (rest) {
-        const int lead = __ffsll((unsigned long long)rest) - 1;
-        const int gl = __shfl(g, lead, 64);
-        const bool mine = cut && g == gl;
-        const uint64_t m = __ballot(mine);
+    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
         const long long v = mine ? pq : 0;
         int64_t* row = cut_tally + (size_t)gl * 4;
         tally_add(row, BGX_ROLLOUT_CUT_GAMES, (long long)__popcll(m));
         tally_add(row, BGX_ROLLOUT_CUT_PLIES, wave_sum(mine ? pl : 0));
         tally_add(row, BGX_ROLLOUT_CUT_P, wave_sum(v));
         tally_add(row, BGX_ROLLOUT_CUT_P2, wave_sum(v * v));
-        rest &= ~m;
-    }
+    });
     tally_add(active, 0, -count(retired));
 }
 

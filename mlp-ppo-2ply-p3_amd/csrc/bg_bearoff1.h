@@ -129,6 +129,7 @@ struct B1Argmin {
 
 #include "bg_engine.h"
 #include "bg_host.h"
+#include "bg_rollout.h"
 
 // The object behind the C ABI's opaque bgx_bearoff1*: device buffers, fixed after creation.
 struct bgx_bearoff1 {
@@ -335,22 +336,8 @@ __global__ __launch_bounds__(256) void k_b1_act(const uint8_t* __restrict__ recs
     act[i] = arg;
 }
 
-// ---- rollout cut (bgx_rollout_bearoff1_cut): k_bo_cut's bookkeeping on this table's value ----
-// (the four helpers are bg_engine.hip's, which keeps them in its unnamed namespace)
-__device__ __forceinline__ void tally_add(int64_t* tally, int field, long long v) {
-    if (v != 0 && lane_id() == 0) atomicAdd((unsigned long long*)tally + field, (unsigned long long)v);
-}
-__device__ __forceinline__ long long count(bool p) { return (long long)__popcll(__ballot(p)); }
-__device__ __forceinline__ long long wave_sum(long long v) {
-    #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int rollout_group(const int32_t* group, int i, int n_groups) {
-    const int g = group[i];
-    return g >= 0 && g < n_groups ? g : -1;
-}
-
+// ---- rollout cut (bgx_rollout_bearoff1_cut): k_bo_cut on this table's value (end_game and
+// for_each_group, bg_rollout.h) ----
 // A selected lane with a valid group whose record is in the table with checkers of both sides
 // off (the test's value 1: the game can only be a single one) ends its game here.
 __global__ __launch_bounds__(256) void k_b1_cut(const uint8_t* __restrict__ recs, const uint8_t* __restrict__ starts,
@@ -374,30 +361,18 @@ __global__ __launch_bounds__(256) void k_b1_cut(const uint8_t* __restrict__ recs
             const float w = b1_win(dist + (size_t)idx[m] * kB1T, surv + (size_t)idx[1 - m] * kB1T);
             const float q = rec.at(R_CUR) == (int)starts[(size_t)i * 64 + R_CUR] ? w : sub_rn(1.0f, w);
             pq = min(max(llrintf(mul_rn(q, 1048576.0f)), 0ll), 1048576ll);
-            pl = plies[i];
-            plies[i] = 0;
-            const int gd = games_done[i] + 1;
-            games_done[i] = gd;
-            retired = gd >= G;
-            if (retired) sel[i] = 0;
+            retired = end_game(i, G, games_done, plies, sel, &pl);
         }
     }
     if (i < n_rec) mask[i] = cut ? 1 : 0;
-    // every thread of the wave reaches the ballots
-    uint64_t rest = __ballot(cut);
-    while (rest) {
-        const int lead = __ffsll((unsigned long long)rest) - 1;
-        const int gl = __shfl(g, lead, 64);
-        const bool mine = cut && g == gl;
-        const uint64_t m = __ballot(mine);
+    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
         const long long v = mine ? pq : 0;
         int64_t* row = cut_tally + (size_t)gl * 4;
         tally_add(row, BGX_ROLLOUT_CUT_GAMES, (long long)__popcll(m));
         tally_add(row, BGX_ROLLOUT_CUT_PLIES, wave_sum(mine ? pl : 0));
         tally_add(row, BGX_ROLLOUT_CUT_P, wave_sum(v));
         tally_add(row, BGX_ROLLOUT_CUT_P2, wave_sum(v * v));
-        rest &= ~m;
-    }
+    });
     tally_add(active, 0, -count(retired));
 }
 

@@ -13,7 +13,7 @@
 // Part 2 (device): the build -- one launch per total pip count, one thread per (a, b) that walks
 // a's successor lists once for all three states -- then the lookup and the cubeful rollout cut,
 // one thread per lane record, and their C entry points.  It reuses bg_cube.h's byte decoding,
-// bg_bearoff1.h's B1Rec and tally helpers and bg_returns.hip's mul_rn / add_rn / sub_rn.
+// bg_bearoff1.h's B1Rec, bg_rollout.h's helpers and bg_returns.hip's mul_rn / add_rn / sub_rn.
 // BGX_CUBE_PART1_ONLY (the host test program tools/cube_bearoff_host.cpp, any C++ compiler) takes
 // part 1 alone.
 #pragma once
@@ -70,6 +70,7 @@ CUBE_HD long long boc_fixed(float v, bool start_mover_on_roll, int k) {
 #include <vector>
 
 #include "bg_debug.h"
+#include "bg_rollout.h"
 
 // The object behind the C ABI's opaque bgx_bearoff_cube*: device buffers, fixed after creation.
 // W, succ_off and succ stay the cubeless database's, which must outlive this object.
@@ -210,7 +211,7 @@ __global__ __launch_bounds__(256) void k_boc_lookup(const uint8_t* __restrict__ 
 }
 
 // ---- the cubeful rollout cut (bgx_rollout_cube_bearoff_cut), after bgx_rollout_begin +
-// bgx_rollout_cube_begin and after every bgx_rollout_advance: k_bo_cut's bookkeeping with the
+// bgx_rollout_cube_begin and after every bgx_rollout_advance: k_bo_cut (end_game, for_each_group) with the
 // cubeful expectation, scaled by the lane's cube, as the game's result ----
 __global__ __launch_bounds__(256) void k_boc_cut(const uint8_t* __restrict__ recs, const uint8_t* __restrict__ starts,
                                                  const int32_t* __restrict__ group, int n_rec, int n_groups, int G,
@@ -233,25 +234,14 @@ __global__ __launch_bounds__(256) void k_boc_cut(const uint8_t* __restrict__ rec
             const uint8_t c = cube[i];
             float v[4];
             boc_read(E, ND, W, n, idx, rec.at(R_CUR) & 1, c, cap, v);
-            pl = plies[i];
+            retired = end_game(i, G, games_done, plies, sel, &pl);
             kk = cube_k(c, cap);
             yq = boc_fixed(pl == 0 ? v[0] : v[2], rec.at(R_CUR) == (int)starts[(size_t)i * 64 + R_CUR], (int)kk);
-            plies[i] = 0;
-            const int gd = games_done[i] + 1;
-            games_done[i] = gd;
-            retired = gd >= G;
-            if (retired) sel[i] = 0;
             cube[i] = cube_sanitise(cube0[i], cap);
         }
     }
     if (i < n_rec) mask[i] = cut ? 1 : 0;
-    // every thread of the wave reaches the ballots
-    uint64_t rest = __ballot(cut);
-    while (rest) {
-        const int lead = __ffsll((unsigned long long)rest) - 1;
-        const int gl = __shfl(g, lead, 64);
-        const bool mine = cut && g == gl;
-        const uint64_t m = __ballot(mine);
+    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
         const long long y = mine ? yq : 0, y2 = y * y;
         int64_t* row = cut_tally + (size_t)gl * 6;
         tally_add(row, BGX_ROLLOUT_CUBE_CUT_GAMES, (long long)__popcll(m));
@@ -260,8 +250,7 @@ __global__ __launch_bounds__(256) void k_boc_cut(const uint8_t* __restrict__ rec
         tally_add(row, BGX_ROLLOUT_CUBE_CUT_Y2_LO, wave_sum(y2 & ((1ll << 30) - 1)));
         tally_add(row, BGX_ROLLOUT_CUBE_CUT_Y2_HI, wave_sum(y2 >> 30));
         tally_add(row, BGX_ROLLOUT_CUBE_CUT_LOG2, wave_sum(mine ? kk : 0));
-        rest &= ~m;
-    }
+    });
     tally_add(active, 0, -count(retired));
 }
 

@@ -7,8 +7,8 @@
 // rule in one function.  A state byte holds k in bits 0-3 (the cube shows 2^k) and the owner in
 // bits 4-5 (0 centred, 1 PLAYER1 = mover byte 0, 2 PLAYER2).  So that every kernel is defined on
 // any byte, k reads as min(k, cap) and owner 3 as 0.
-// Part 2 (device): the four kernels, one thread per lane, and their C entry points.  They reuse
-// the four helpers bg_bearoff1.h defines (tally_add, count, wave_sum, rollout_group).  No LDS, no
+// Part 2 (device): the four kernels, one thread per lane, and their C entry points.  They use
+// bg_rollout.h's helpers (tally_add, count, wave_sum, for_each_group, end_game).  No LDS, no
 // scratch.  BGX_CUBE_PART1_ONLY (the host test program tools/cube_host.cpp, any C++ compiler)
 // takes part 1 alone.
 #pragma once
@@ -64,6 +64,7 @@ CUBE_HD int cube_decision(uint8_t c, int cap, int mover, float scale, float equi
 // ======================================================================== part 2 ==
 #include "bg_engine.h"
 #include "bg_host.h"
+#include "bg_rollout.h"
 
 namespace {
 
@@ -90,8 +91,8 @@ __global__ __launch_bounds__(256) void k_cube_sel(const uint8_t* __restrict__ re
     dsel[i] = d ? 1 : 0;
 }
 
-// The decision on the dsel lanes: a pass ends the game at the cube's value (bookkeeping as
-// k_b1_cut's: the game is counted, the lane masked for the reset), a take turns the cube.
+// The decision on the dsel lanes: a pass ends the game at the cube's value (end_game: the game
+// is counted; the lane is masked for the reset), a take turns the cube.
 __global__ __launch_bounds__(256) void k_cube_decide(const uint8_t* __restrict__ recs, const uint8_t* __restrict__ starts,
                                                      const int32_t* __restrict__ group,
                                                      const uint8_t* __restrict__ dsel, const float* __restrict__ equity,
@@ -115,25 +116,14 @@ __global__ __launch_bounds__(256) void k_cube_decide(const uint8_t* __restrict__
         if (pass) {
             kk = cube_k(c, rule.cap);
             y = m == (int)(starts[(size_t)i * 64 + R_CUR] & 1) ? (1ll << kk) : -(1ll << kk);
-            pl = plies[i];
-            plies[i] = 0;
-            const int gd = games_done[i] + 1;
-            games_done[i] = gd;
-            retired = gd >= G;
-            if (retired) sel[i] = 0;
+            retired = end_game(i, G, games_done, plies, sel, &pl);
             cube[i] = cube_sanitise(cube0[i], rule.cap);
         } else if (dbl) {
             cube[i] = next;
         }
     }
     if (i < n) mask[i] = pass ? 1 : 0;
-    // every thread of the wave reaches the ballots
-    uint64_t rest = __ballot(dbl);
-    while (rest) {
-        const int lead = __ffsll((unsigned long long)rest) - 1;
-        const int gl = __shfl(g, lead, 64);
-        const bool mine = dbl && g == gl;
-        const uint64_t md = __ballot(mine);
+    for_each_group(dbl, g, [&](int gl, bool mine, uint64_t md) {
         const bool pm = mine && pass;
         const long long np = count(pm), v = pm ? y : 0;
         int64_t* row = cube_tally + (size_t)gl * 8;
@@ -145,8 +135,7 @@ __global__ __launch_bounds__(256) void k_cube_decide(const uint8_t* __restrict__
         tally_add(row, BGX_ROLLOUT_CUBE_PASS_PLIES, wave_sum(pm ? pl : 0));
         tally_add(row, BGX_ROLLOUT_CUBE_PASS_WON, count(pm && y > 0));
         tally_add(row, BGX_ROLLOUT_CUBE_DOUBLES, (long long)__popcll(md));
-        rest &= ~md;
-    }
+    });
     tally_add(active, 0, -count(retired));
 }
 
@@ -162,8 +151,8 @@ __global__ __launch_bounds__(256) void k_cube_flush(const uint8_t* __restrict__ 
     const bool on = i < n && sel[i] != 0;
     const int g = on ? rollout_group(group, i, n_groups) : -1;
     const bool dn = on && done[i] != 0;
-    const int inf = dn ? info[i] : 0;
-    const int winner = ((inf >> 8) & 0xFF) - 1, score = min(max((inf >> 16) & 0xFF, 1), 3);
+    int winner, score;
+    result_of(dn ? info[i] : 0, &winner, &score);
     const bool fin = dn && g >= 0 && winner >= 0;
     long long y = 0, kk = 0;
     if (fin) {
@@ -172,20 +161,14 @@ __global__ __launch_bounds__(256) void k_cube_flush(const uint8_t* __restrict__ 
         y = winner == (int)(starts[(size_t)i * 64 + R_CUR] & 1) ? (s << kk) : -(s << kk);
     }
     if (dn) cube[i] = cube_sanitise(cube0[i], rule.cap);
-    uint64_t rest = __ballot(fin);
-    while (rest) {
-        const int lead = __ffsll((unsigned long long)rest) - 1;
-        const int gl = __shfl(g, lead, 64);
-        const bool mine = fin && g == gl;
-        const uint64_t m = __ballot(mine);
+    for_each_group(fin, g, [&](int gl, bool mine, uint64_t m) {
         const long long v = mine ? y : 0;
         int64_t* row = cube_tally + (size_t)gl * 8;
         tally_add(row, BGX_ROLLOUT_CUBE_GAMES, (long long)__popcll(m));
         tally_add(row, BGX_ROLLOUT_CUBE_POINTS, wave_sum(v));
         tally_add(row, BGX_ROLLOUT_CUBE_POINTS2, wave_sum(v * v));
         tally_add(row, BGX_ROLLOUT_CUBE_LOG2, wave_sum(mine ? kk : 0));
-        rest &= ~m;
-    }
+    });
 }
 
 bool cube_rule_ok(const bgx_cube_rule& r) {

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "bg_engine.h"
+#include "bg_rollout.h"
 #include "bg_debug.h"
 #include "bg_host.h"
 #include <map>
@@ -518,11 +519,7 @@ __global__ __launch_bounds__(256) void k_copy_regions(CopyRegions R) {
 // neither player and is not counted: counting exactly G games per lane keeps the result
 // unbiased, where a fixed step budget would over-represent short games.
 // The tally fields are integer sums, so the order of the additions does not matter: each
-// wave counts its lanes with ballots and adds once per field (64-bit atomic add).
-__device__ __forceinline__ void tally_add(int64_t* tally, int field, long long v) {
-    if (v != 0 && lane_id() == 0) atomicAdd((unsigned long long*)tally + field, (unsigned long long)v);
-}
-__device__ __forceinline__ long long count(bool p) { return (long long)__popcll(__ballot(p)); }
+// wave counts its lanes with ballots and adds once per field (tally_add, count: bg_rollout.h).
 
 // sel_a / sel_b of lane i for its current position: the mover's seat in the lane's game g
 __device__ __forceinline__ void select_lane(const uint8_t* recs, int i, int g, bool active, uint8_t* sel_a,
@@ -627,25 +624,7 @@ __global__ __launch_bounds__(256) void k_check_starts(const uint8_t* __restrict_
     if (!ok) atomicOr(err, 4);
 }
 
-// ---- position rollouts (DESIGN.md "Start positions and rollouts"; bgx/rollout.py drives it) ----
-// Bookkeeping of rollouts on an engine whose start table holds the positions: lane i plays
-// G games of position group[i] (one player acts for both sides), every game from the
-// lane's start record again (the engine's auto-reset refills it in the step that ends the
-// game).  State, plain arrays of the caller:
-//   group int32[n]        position of the lane in [0, n_groups); anything else = idle lane
-//   games_done int32[n]   finished, counted games of the lane (active while < G)
-//   plies int32[n]        steps of the lane's current game
-//   sel uint8[n]          the lane is active (lane selection of bgx_one_ply_sel / bgx_two_ply_sel)
-//   tally int64[n_groups][8]  bgx_rollout_field; win = won by the start record's mover
-//   active int64[1]       active lanes remaining
-// PLIES is added at the game's end with the game, so the atomics are per finished game.
-// Lanes of one group are usually neighbours: a wave adds once per (group, field) it holds
-// finishers of.  Integer adds commute: the tallies are the same from run to run.
-__device__ __forceinline__ int rollout_group(const int32_t* group, int i, int n_groups) {
-    const int g = group[i];
-    return g >= 0 && g < n_groups ? g : -1;
-}
-
+// ---- position rollouts: the accounting arrays and the helpers are bg_rollout.h's ----
 // tally and active are zero already (the entry point's memsets, ordered before this kernel)
 __global__ __launch_bounds__(256) void k_rollout_begin(const int32_t* group, int n, int n_groups, int G,
                                                        int32_t* games_done, int32_t* plies, uint8_t* sel,
@@ -668,41 +647,26 @@ __global__ __launch_bounds__(256) void k_rollout_advance(const uint8_t* starts, 
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool in = i < n;
     const int g = in ? rollout_group(group, i, n_groups) : -1;
-    int gd = g >= 0 ? games_done[i] : G;
-    const bool on = g >= 0 && gd < G;
-    const int inf = on ? info[i] : 0;
-    const int winner = ((inf >> 8) & 0xFF) - 1, score = min(max((inf >> 16) & 0xFF, 1), 3);
+    const bool on = g >= 0 && games_done[i] < G;
+    int winner, score;
+    result_of(on ? info[i] : 0, &winner, &score);
     const bool fin = on && done[i] != 0 && winner >= 0;
-    const int p = on ? plies[i] + 1 : 0;
+    long long p = 0;
     int field = 0;
     bool retired = false;
-    if (on) {
-        plies[i] = fin ? 0 : p;
-        if (fin) {
-            const bool won = winner == (int)(starts[(size_t)i * 64 + R_CUR] & 1);
-            field = (won ? BGX_ROLLOUT_WIN1 : BGX_ROLLOUT_LOSS1) + score - 1;
-            games_done[i] = ++gd;
-            retired = gd >= G;
-            if (retired) sel[i] = 0;
-        }
+    if (on) plies[i] += 1;                              // the step's own ply counts for the game it ends
+    if (fin) {
+        const bool won = winner == (int)(starts[(size_t)i * 64 + R_CUR] & 1);
+        field = (won ? BGX_ROLLOUT_WIN1 : BGX_ROLLOUT_LOSS1) + score - 1;
+        retired = end_game(i, G, games_done, plies, sel, &p);
     }
-    // the wave's finishers, one group at a time (every thread of the wave reaches the ballots)
-    uint64_t rest = __ballot(fin);
-    while (rest) {
-        const int lead = __ffsll((unsigned long long)rest) - 1;
-        const int gl = __shfl(g, lead, 64);
-        const bool mine = fin && g == gl;
-        const uint64_t m = __ballot(mine);
-        int ps = mine ? p : 0;
-        #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ps += __shfl_xor(ps, o, 64);
+    for_each_group(fin, g, [&](int gl, bool mine, uint64_t m) {
         int64_t* row = tally + (size_t)gl * 8;
         tally_add(row, BGX_ROLLOUT_GAMES, (long long)__popcll(m));
-        tally_add(row, BGX_ROLLOUT_PLIES, (long long)ps);
+        tally_add(row, BGX_ROLLOUT_PLIES, wave_sum(mine ? p : 0));
         #pragma unroll
         for (int f = BGX_ROLLOUT_WIN1; f <= BGX_ROLLOUT_LOSS3; ++f) tally_add(row, f, count(mine && field == f));
-        rest &= ~m;
-    }
+    });
     tally_add(active, 0, -count(retired));
 }
 
@@ -720,12 +684,6 @@ __global__ __launch_bounds__(256) void k_rollout_luck_add(const uint8_t* recs, c
     lane_luck[i] += recs[(size_t)i * 64 + R_CUR] == starts[(size_t)i * 64 + R_CUR] ? l : -l;
 }
 
-__device__ __forceinline__ long long wave_sum(long long v) {
-    #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // After the step, before k_rollout_advance (sel is still the step's selection): a counted
 // game (k_rollout_advance's rule) adds its luck in 2^-16 fixed point to its group's row and
 // zeroes the lane's sum; any other done of a selected lane only zeroes it.  Per wave, one
@@ -738,31 +696,23 @@ __global__ __launch_bounds__(256) void k_rollout_luck_flush(const uint8_t* start
     const bool on = i < n && sel[i] != 0;
     const int g = on ? rollout_group(group, i, n_groups) : -1;
     const bool dn = on && done[i] != 0;
-    const int inf = dn ? info[i] : 0;
-    const int winner = ((inf >> 8) & 0xFF) - 1, score = min(max((inf >> 16) & 0xFF, 1), 3);
+    int winner, score;
+    result_of(dn ? info[i] : 0, &winner, &score);
     const bool fin = dn && g >= 0 && winner >= 0;
     long long lq = 0, res = 0;
     if (fin) {
-        float x = lane_luck[i] * 65536.0f;
-        x = isfinite(x) ? fminf(fmaxf(x, -2097152.0f), 2097152.0f) : 0.0f;
-        lq = llrintf(x);
+        lq = luck_q(lane_luck[i]);
         res = winner == (int)(starts[(size_t)i * 64 + R_CUR] & 1) ? score : -score;
     }
     if (dn) lane_luck[i] = 0.0f;
-    uint64_t rest = __ballot(fin);
-    while (rest) {
-        const int lead = __ffsll((unsigned long long)rest) - 1;
-        const int gl = __shfl(g, lead, 64);
-        const bool mine = fin && g == gl;
-        const uint64_t m = __ballot(mine);
+    for_each_group(fin, g, [&](int gl, bool mine, uint64_t m) {
         const long long v = mine ? lq : 0;
         int64_t* row = luck_tally + (size_t)gl * 4;
         tally_add(row, BGX_ROLLOUT_LUCK, wave_sum(v));
         tally_add(row, BGX_ROLLOUT_LUCK2, wave_sum(v * v));
         tally_add(row, BGX_ROLLOUT_RESLUCK, wave_sum(mine ? res * lq : 0));
         tally_add(row, BGX_ROLLOUT_LUCK_GAMES, (long long)__popcll(m));
-        rest &= ~m;
-    }
+    });
 }
 
 // murmur3's 64-bit finalizer
@@ -998,7 +948,7 @@ static int step_debug_dump(bgx_engine* e, hipStream_t s) {
     return BGX_OK;
 }
 
-// the bearoff database: its kernels and entry points (they use the rollout helpers above)
+// the bearoff database: its kernels and entry points (they use bg_rollout.h's helpers)
 #include "bg_bearoff.h"
 
 extern "C" {

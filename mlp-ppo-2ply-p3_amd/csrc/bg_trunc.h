@@ -4,8 +4,8 @@
 //
 // Part 1 (plain C++, host and device): the one function that turns a value into the game's
 // fixed-point result.
-// Part 2 (device): the two kernels, one thread per lane, and their C entry points.  They reuse
-// the four helpers bg_bearoff1.h defines (tally_add, count, wave_sum, rollout_group).  No LDS, no
+// Part 2 (device): the two kernels, one thread per lane, and their C entry points.  They use
+// bg_rollout.h's helpers (tally_add, count, wave_sum, for_each_group, end_game).  No LDS, no
 // scratch.  BGX_TRUNC_PART1_ONLY (the host test program tools/trunc_host.cpp, any C++ compiler)
 // takes part 1 alone.
 #pragma once
@@ -40,6 +40,7 @@ TRUNC_HD long long trunc_value_q(float scale, float v, bool same) {
 // ======================================================================== part 2 ==
 #include "bg_engine.h"
 #include "bg_host.h"
+#include "bg_rollout.h"
 
 namespace {
 
@@ -60,8 +61,8 @@ __global__ __launch_bounds__(256) void k_trunc_sel(const uint8_t* __restrict__ r
     if (cnt) tally_add(cnt, 0, c);
 }
 
-// The truncation on the tsel lanes: the game is counted at its value (bookkeeping as k_b1_cut's)
-// together with the luck it gathered, and the lane is masked for the reset.
+// The truncation on the tsel lanes: the game is counted at its value (end_game) together with
+// the luck it gathered, and the lane is masked for the reset.
 __global__ __launch_bounds__(256) void k_trunc_cut(const uint8_t* __restrict__ recs, const uint8_t* __restrict__ starts,
                                                    const int32_t* __restrict__ group,
                                                    const uint8_t* __restrict__ tsel, const float* __restrict__ value,
@@ -78,26 +79,13 @@ __global__ __launch_bounds__(256) void k_trunc_cut(const uint8_t* __restrict__ r
         const bool same = recs[(size_t)i * 64 + R_CUR] == starts[(size_t)i * 64 + R_CUR];
         vq = trunc_value_q(scale, value[i], same);
         if (lane_luck) {
-            float x = lane_luck[i] * 65536.0f;                     // bgx_rollout_luck_flush's Lq
-            x = isfinite(x) ? fminf(fmaxf(x, -2097152.0f), 2097152.0f) : 0.0f;
-            lq = llrintf(x);
+            lq = luck_q(lane_luck[i]);                             // bgx_rollout_luck_flush's Lq
             lane_luck[i] = 0.0f;
         }
-        pl = plies[i];
-        plies[i] = 0;
-        const int gd = games_done[i] + 1;
-        games_done[i] = gd;
-        retired = gd >= G;
-        if (retired) sel[i] = 0;
+        retired = end_game(i, G, games_done, plies, sel, &pl);
     }
     if (i < n) mask[i] = cut ? 1 : 0;
-    // every thread of the wave reaches the ballots
-    uint64_t rest = __ballot(cut);
-    while (rest) {
-        const int lead = __ffsll((unsigned long long)rest) - 1;
-        const int gl = __shfl(g, lead, 64);
-        const bool mine = cut && g == gl;
-        const uint64_t m = __ballot(mine);
+    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
         const long long v = mine ? vq : 0, l = mine ? lq : 0;
         int64_t* row = trunc_tally + (size_t)gl * 7;
         tally_add(row, BGX_ROLLOUT_TRUNC_GAMES, (long long)__popcll(m));
@@ -107,8 +95,7 @@ __global__ __launch_bounds__(256) void k_trunc_cut(const uint8_t* __restrict__ r
         tally_add(row, BGX_ROLLOUT_TRUNC_LUCK, wave_sum(l));
         tally_add(row, BGX_ROLLOUT_TRUNC_LUCK2, wave_sum(l * l));
         tally_add(row, BGX_ROLLOUT_TRUNC_VLUCK, wave_sum(v * l));
-        rest &= ~m;
-    }
+    });
     tally_add(active, 0, -count(retired));
 }
 
