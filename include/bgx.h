@@ -707,6 +707,84 @@ int bgx_rollout_cube_flush(const uint8_t* starts_dev, const int32_t* group_dev, 
                            bgx_cube_rule rule, const uint8_t* cube0_dev, uint8_t* cube_dev, int64_t* cube_tally_dev,
                            void* stream);
 
+/* ---- the doubling cube in the head-to-head arena, money play (csrc/bg_arena_cube.h;
+ * bgx/arena.py; no counterpart in the reference) ----
+ * The rule of the block above in two halves, each taken by a different party: the side on roll
+ * offers a double by its own rule on its own equity, the other side answers by its own rule on
+ * its own estimate of the doubler's equity.  Beside the state of bgx_arena_begin (games_done,
+ * sel_a, sel_b, tally) the caller owns cube uint8[n], the state byte of the lane's current game
+ * (as above; every arena game starts centred at 1, byte 0), plies int32[n], the steps of the
+ * lane's current game, and cube_tally int64[16] (bgx_arena_cube_field).  rule_a / rule_b are A's
+ * and B's bgx_cube_rule; cap and jacoby belong to the game, so the two must agree on them.  Seat
+ * rule as in the arena: in game g of lane i, A is PLAYER1 iff ((i + g) & 1) == 0.
+ * Per step: cube_sel; A's equity on dsel_a and B's on dsel_b; cube_offer; B's equity on off_a and
+ * A's on off_b (the doubler's equity, the mover's view, as the responder estimates it);
+ * cube_respond; bgx_reset with the mask; cube_reseat; the players' act; bgx_arena_merge; bgx_step;
+ * cube_flush; bgx_arena_advance.  cube_begin once after bgx_arena_begin.
+ * bgx_arena_cube_begin: cube = 0, plies = 0, cube_tally = 0.
+ * bgx_arena_cube_sel: dsel_x_out[i] = 1 when sel_x[i] != 0, plies[i] > 0 (no cube action on a
+ * game's first ply), the record is not game_over (byte 55), k < cap and the cube is centred or
+ * owned by the record's mover; else 0 (x = a, b).
+ * bgx_arena_cube_offer: off_a_out[i] = 1 when dsel_a[i] != 0, the cube is open to the record's
+ * mover (cube_sel's test of the cube itself, made again: a dsel of another origin cannot take
+ * the cube past the cap) and, with e = rule_a.scale * eq_a[i] in fp32 (one product),
+ * rule_a.double_at <= e <= rule_a.too_good_at (a NaN never doubles); else 0.  off_b_out likewise
+ * from dsel_b, eq_b and rule_b.  DOUBLES_A += the off_a lanes, DOUBLES_B += the off_b lanes.
+ * bgx_arena_cube_respond: on a lane with off_a[i] != 0 B answers: it passes iff rule_b.scale *
+ * eq_b[i] > rule_b.pass_at (a NaN takes); on a lane with off_b[i] != 0 (and off_a[i] == 0) A
+ * answers by rule_a on eq_a[i].  Only active lanes (games_done[i] < games_per_lane) whose cube is
+ * open to the record's mover m are answered.  Take: k += 1, owner = 2 - m (the taker).  Pass: the
+ * game ends worth y = +(1 << k) to A when A doubled, -(1 << k) when B did; CUBE_GAMES += 1,
+ * CUBE_POINTS_A += y, CUBE_POINTS2 += y * y, CUBE_WINS_A += (y > 0), CUBE_LOG2 += k,
+ * PASS_GAMES += 1, PASS_PLIES += plies[i], PASSES_A += 1 when A gave up, else PASSES_B += 1;
+ * games_done[i] += 1, plies[i] = 0, cube[i] = 0, sel_a[i] = sel_b[i] = 0 (until the reseat); the
+ * lane's last game: tally[BGX_ARENA_ACTIVE] drops; reset_mask_out[i] = 1.  Every other lane gets
+ * reset_mask_out[i] = 0.  The caller then runs bgx_reset with the mask.
+ * bgx_arena_cube_reseat: after that reset.  A lane with reset_mask[i] != 0 and games_done[i] <
+ * games_per_lane gets sel_a / sel_b from the new record's mover and the new g = games_done[i].
+ * bgx_arena_cube_flush: after bgx_step and BEFORE bgx_arena_advance, with the step's done and
+ * info, while games_done[i] is still the finished game's g.  For a lane with sel_a[i] or sel_b[i]
+ * set (an active lane): a done with a winner is scored at the cube, s = info's game_score, or 1
+ * when jacoby != 0 and k == 0, y = +-(s << k) from A's side: CUBE_GAMES += 1, CUBE_POINTS_A += y,
+ * CUBE_POINTS2 += y * y, CUBE_WINS_A += (y > 0), CUBE_LOG2 += k; then cube[i] = 0, plies[i] = 0.
+ * Any other done only resets cube and plies; a lane without a done gets plies[i] += 1.
+ * The plain tally keeps counting the games played to the end only, as a rollout's does (its
+ * PLIES counts every step of an active lane).  CUBE_GAMES == tally[BGX_ARENA_GAMES] + PASS_GAMES
+ * and PASS_GAMES == PASSES_A + PASSES_B; |y| <= 3 * 2^10; all sums are integers, hence
+ * run-to-run identical.  Plain kernels, one thread per lane, no allocation and no
+ * synchronisation: graph-capturable.  BGX_EINVAL for n <= 0, games_per_lane < 0, a NULL pointer,
+ * cap outside 0..10, a NaN in a rule's scale, double_at or pass_at (too_good_at may be +inf), or
+ * rules that differ in cap or jacoby. */
+enum bgx_arena_cube_field {
+    BGX_ARENA_CUBE_GAMES = 0,        /* games that ended, played out or passed */
+    BGX_ARENA_CUBE_POINTS_A = 1,     /* sum of y, points from A's side */
+    BGX_ARENA_CUBE_POINTS2 = 2,      /* sum of y^2 */
+    BGX_ARENA_CUBE_WINS_A = 3,       /* games with y > 0 */
+    BGX_ARENA_CUBE_LOG2 = 4,         /* sum of k at the game's end */
+    BGX_ARENA_CUBE_PASS_GAMES = 5,   /* games ended by a passed double */
+    BGX_ARENA_CUBE_PASS_PLIES = 6,   /* their steps */
+    BGX_ARENA_CUBE_PASSES_A = 7,     BGX_ARENA_CUBE_PASSES_B = 8,   /* the side that gave up */
+    BGX_ARENA_CUBE_DOUBLES_A = 9,    BGX_ARENA_CUBE_DOUBLES_B = 10  /* doubles offered; 11..15 stay zero */
+};
+int bgx_arena_cube_begin(int32_t n, uint8_t* cube_dev, int32_t* plies_dev, int64_t* cube_tally_dev, void* stream);
+int bgx_arena_cube_sel(const uint8_t* records_dev, const uint8_t* sel_a_dev, const uint8_t* sel_b_dev,
+                       const int32_t* plies_dev, const uint8_t* cube_dev, int32_t n, int32_t cap, uint8_t* dsel_a_out,
+                       uint8_t* dsel_b_out, void* stream);
+int bgx_arena_cube_offer(const uint8_t* records_dev, const uint8_t* dsel_a_dev, const uint8_t* dsel_b_dev,
+                         const float* eq_a_dev, const float* eq_b_dev, bgx_cube_rule rule_a, bgx_cube_rule rule_b,
+                         const uint8_t* cube_dev, int32_t n, uint8_t* off_a_out, uint8_t* off_b_out,
+                         int64_t* cube_tally_dev, void* stream);
+int bgx_arena_cube_respond(const uint8_t* records_dev, const uint8_t* off_a_dev, const uint8_t* off_b_dev,
+                           const float* eq_a_dev, const float* eq_b_dev, bgx_cube_rule rule_a, bgx_cube_rule rule_b,
+                           int32_t n, int32_t games_per_lane, uint8_t* cube_dev, int32_t* plies_dev,
+                           int32_t* games_done_dev, uint8_t* sel_a_dev, uint8_t* sel_b_dev, int64_t* tally_dev,
+                           int64_t* cube_tally_dev, uint8_t* reset_mask_out, void* stream);
+int bgx_arena_cube_reseat(const uint8_t* records_dev, const uint8_t* reset_mask_dev, int32_t n, int32_t games_per_lane,
+                          const int32_t* games_done_dev, uint8_t* sel_a_dev, uint8_t* sel_b_dev, void* stream);
+int bgx_arena_cube_flush(const uint8_t* sel_a_dev, const uint8_t* sel_b_dev, const uint8_t* done_dev,
+                         const int32_t* info_dev, const int32_t* games_done_dev, int32_t n, int32_t jacoby, int32_t cap,
+                         uint8_t* cube_dev, int32_t* plies_dev, int64_t* cube_tally_dev, void* stream);
+
 /* ---- truncated position rollouts (csrc/bg_trunc.h; bgx/rollout.py; no
  * counterpart in the reference) ----
  * A game that has run `horizon` plies without ending stops there and is scored with a value of

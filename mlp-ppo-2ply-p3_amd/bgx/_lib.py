@@ -94,6 +94,13 @@ SIGNATURES = {
     "bgx_rollout_cube_decide": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, BgxCubeRule, _P, _P, _P, _P, _P, _P,
                                                _P, _P, _P]),
     "bgx_rollout_cube_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, BgxCubeRule, _P, _P, _P, _P]),
+    "bgx_arena_cube_begin": (ctypes.c_int, [_I32, _P, _P, _P, _P]),
+    "bgx_arena_cube_sel": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "bgx_arena_cube_offer": (ctypes.c_int, [_P, _P, _P, _P, _P, BgxCubeRule, BgxCubeRule, _P, _I32, _P, _P, _P, _P]),
+    "bgx_arena_cube_respond": (ctypes.c_int, [_P, _P, _P, _P, _P, BgxCubeRule, BgxCubeRule, _I32, _I32, _P, _P, _P, _P,
+                                              _P, _P, _P, _P, _P]),
+    "bgx_arena_cube_reseat": (ctypes.c_int, [_P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "bgx_arena_cube_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P]),
     "bgx_rollout_trunc_sel": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P]),
     "bgx_rollout_trunc_cut": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_float, _I32, _I32, _I32, _P, _P, _P, _P, _P,
                                              _P, _P, _P]),

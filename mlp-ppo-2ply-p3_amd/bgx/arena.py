@@ -12,6 +12,15 @@ Seat rule: in game g of lane i, A sits as PLAYER1 iff ((i + g) & 1) == 0, so wit
 batch A holds each seat in exactly half of all games.  A lane that has finished its G
 games keeps stepping with action 0, belongs to neither player and is not counted: exactly
 G games per lane keeps the estimate unbiased (a step budget would favour short games).
+
+--cube: money play with the doubling cube (csrc/bg_arena_cube.h): every game
+starts with the cube centred at 1; before its roll, but never on a game's first ply, the side
+on roll may double by its own CubeRule on its own net's equity, and the other side takes or
+passes by its own.  The result is A's cubeful points per game beside the played-out games' plain
+result.
+
+    python -m bgx.arena --a new.pt --b old.pt --max-steps 4000 --cube --cube-lookahead-a 0 \\
+        --cube-lookahead-b 0 --cube-double-a 0.35
 """
 from __future__ import annotations
 
@@ -20,6 +29,7 @@ import ctypes
 import json
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -30,6 +40,9 @@ from .engine import Engine, R_CUR, R_NM0, R_NM1, _ptr, _stream
 FIELDS = ("games", "wins_a", "wins_b", "points_a", "points_b", "gammons_a", "gammons_b", "backgammons_a",
           "backgammons_b", "games_a_p1", "wins_a_p1", "wins_p1", "plies", "active_lanes")
 ACTIVE = FIELDS.index("active_lanes")
+# cube_tally int64[16] (include/bgx.h bgx_arena_cube_field); entries 11..15 stay zero
+CUBE_FIELDS = ("cube_games", "cube_points_a", "cube_points2", "cube_wins_a", "cube_log2", "pass_games", "pass_plies",
+               "passes_a", "passes_b", "doubles_a", "doubles_b")
 TRACE_LIMIT = 1 << 22           # trace=True: batch x max_steps entries per traced field
 SYNC_EVERY = 16                 # sync-free players: steps between host reads of the active-lane count
 
@@ -37,17 +50,198 @@ SYNC_EVERY = 16                 # sync-free players: steps between host reads of
 def summarize(tally, steps: int, unfinished: int) -> dict:
     """The arena result from the 16 tally entries: the fields by name, `steps`,
     `unfinished_lanes`, A's win rate with its binomial standard error and A's points per
-    game (points_a - points_b) / games.  No games: the rates are 0."""
+    game (points_a - points_b) / games with its standard error `ppg_stderr`, exact from the
+    integers: a game's result is +-1 / 2 / 3, singles = wins - gammons - backgammons, so the sum of
+    squares is singles + 4 gammons + 9 backgammons and ppg_stderr = sqrt((sum of squares - games
+    ppg^2) / (games - 1) / games).  No games: the rates are 0; one game: ppg_stderr is 0."""
     t = [int(v) for v in tally]
     if len(t) < len(FIELDS):
         raise ValueError(f"summarize: the tally has {len(t)} entries, needs {len(FIELDS)}")
     r = dict(zip(FIELDS, t))
     g = r["games"]
     p = r["wins_a"] / g if g > 0 else 0.0
+    s1 = r["points_a"] - r["points_b"]
+    s2 = sum(r[f"wins_{x}"] + 3 * r[f"gammons_{x}"] + 8 * r[f"backgammons_{x}"] for x in "ab")
+    r.update(ppg_stderr=math.sqrt(max(g * s2 - s1 * s1, 0) / (g * g * (g - 1))) if g > 1 else 0.0)
     r.update(steps=int(steps), unfinished_lanes=int(unfinished), win_rate_a=p,
              ppg_a=(r["points_a"] - r["points_b"]) / g if g > 0 else 0.0,
              win_rate_stderr=math.sqrt(max(p * (1.0 - p), 0.0) / g) if g > 0 else 0.0)
     return r
+
+
+def summarize_cube(tally, cube_tally, steps: int, unfinished: int) -> dict:
+    """The cubeful arena result from the plain tally (the games played to the end) and the 16
+    cube sums (CUBE_FIELDS), in fp64 from the integers as cube.summarize_cube does: `games`
+    (played out + passed), `ppg_cubeful_a` = CUBE_POINTS_A / games, A's points per game at the
+    cube, `ppg_cubeful_stderr` = sqrt((CUBE_POINTS2 - games ppg^2) / (games - 1) / games),
+    `win_rate_cubeful_a` = CUBE_WINS_A / games (a pass is a win for the doubler), `pass_share`,
+    `doubles_per_game_a` / `_b` (doubles the side offered), `take_share_a` / `_b` (of the doubles
+    offered TO the side, the share it took: 1 - PASSES_x / DOUBLES_other; 0 without one),
+    `mean_cube_log2` (the mean k at the game's end), the 11 sums under their names, `steps`,
+    `unfinished_lanes` and `played_out` = summarize(tally, ...): the plain result of the games
+    played to the end -- no estimate of cubeless strength, as the passed games are missing from
+    it.  No games: the rates are 0; one game: the standard error is 0.  Raises ValueError when
+    CUBE_GAMES != GAMES + PASS_GAMES or PASS_GAMES != PASSES_A + PASSES_B."""
+    played = summarize(tally, steps, unfinished)
+    c = [int(v) for v in cube_tally]
+    if len(c) < len(CUBE_FIELDS):
+        raise ValueError(f"summarize_cube: the cube tally has {len(c)} entries, needs {len(CUBE_FIELDS)}")
+    r = dict(zip(CUBE_FIELDS, c))
+    n = r["cube_games"]
+    if n != played["games"] + r["pass_games"]:
+        raise ValueError(f"summarize_cube: the cube tally counts {n} games, the plain tally {played['games']} and "
+                         f"{r['pass_games']} passed")
+    if r["pass_games"] != r["passes_a"] + r["passes_b"]:
+        raise ValueError(f"summarize_cube: {r['pass_games']} passed games, but A gave up {r['passes_a']} and B "
+                         f"{r['passes_b']}")
+
+    def per_game(v):
+        return v / n if n > 0 else 0.0
+
+    def take_share(offered, passed):
+        return 1.0 - passed / offered if offered > 0 else 0.0
+
+    var_num = max(n * r["cube_points2"] - r["cube_points_a"] ** 2, 0)      # n^2 (n - 1) x the variance of the mean
+    r.update(games=n, ppg_cubeful_a=per_game(r["cube_points_a"]),
+             ppg_cubeful_stderr=math.sqrt(var_num / (n * n * (n - 1))) if n > 1 else 0.0,
+             win_rate_cubeful_a=per_game(r["cube_wins_a"]), pass_share=per_game(r["pass_games"]),
+             doubles_per_game_a=per_game(r["doubles_a"]), doubles_per_game_b=per_game(r["doubles_b"]),
+             take_share_a=take_share(r["doubles_b"], r["passes_a"]),
+             take_share_b=take_share(r["doubles_a"], r["passes_b"]),
+             mean_cube_log2=per_game(r["cube_log2"]), steps=int(steps), unfinished_lanes=int(unfinished),
+             played_out=played)
+    return r
+
+
+# --------------------------------------------------------------------- cube --
+class _ZeroEquity:
+    """The equity of a side without a rule: zeros, never read past the thresholds at +inf."""
+    sync_free = True
+
+    def __init__(self):
+        self.z = None
+
+    def __call__(self, eng, dsel):
+        if self.z is None or self.z.numel() != eng.batch or self.z.device != eng.device:
+            self.z = torch.zeros(eng.batch, dtype=torch.float32, device=eng.device)
+        return self.z
+
+
+class ArenaCube:
+    """The doubling cube of an arena match: `rule_a` and `rule_b`, A's and B's
+    cube.CubeRule, each with its own value and thresholds.  A doubles by rule_a on rule_a's
+    equity, B takes or passes by rule_b on rule_b's equity of the same position, and the other
+    way round.  Either may be None: that side never doubles and takes every double (a CubeRule
+    on a zero callable with double_at = pass_at = +inf, so the kernels need no special case).
+    `cap` and `jacoby` belong to the game: both rules must agree on them (ValueError); a None
+    side takes the other's, two None sides the CubeRule defaults."""
+
+    def __init__(self, rule_a=None, rule_b=None):
+        from .cube import CubeRule
+        for r in (rule_a, rule_b):
+            if r is not None and not isinstance(r, CubeRule):
+                raise ValueError("ArenaCube: a rule must be a cube.CubeRule or None")
+        if rule_a is not None and rule_b is not None and (rule_a.cap, rule_a.jacoby) != (rule_b.cap, rule_b.jacoby):
+            raise ValueError(f"ArenaCube: cap and jacoby belong to the game, but A's rule has {rule_a.cap}, "
+                             f"{rule_a.jacoby} and B's {rule_b.cap}, {rule_b.jacoby}")
+        game = {}
+        for r in (rule_a, rule_b):
+            if r is not None:
+                game = dict(cap=r.cap, jacoby=r.jacoby)
+
+        def never():
+            return CubeRule(_ZeroEquity(), double_at=math.inf, pass_at=math.inf, **game)
+
+        self.has_a, self.has_b = rule_a is not None, rule_b is not None
+        self.rule_a = rule_a if rule_a is not None else never()
+        self.rule_b = rule_b if rule_b is not None else never()
+        self.cap, self.jacoby = self.rule_a.cap, self.rule_a.jacoby
+        self.sync_free = self.rule_a.sync_free and self.rule_b.sync_free
+
+
+def arena_cube_reference(trace, batch: int, games_per_lane: int, rule_a, rule_b) -> dict:
+    """A traced cube match (Arena.play(trace=True, cube=...)) replayed on the host with the
+    kernels' fp32 arithmetic (include/bgx.h bgx_arena_cube_*).  Read from the trace, [steps, B]
+    each: cube_mover (the side on roll before the decision), eq_offer (the equity the side on roll
+    decided on), eq_resp (the doubler's equity as the other side estimated it), done and info; the
+    lane records are taken as not game_over, which holds between the steps of an auto-reset
+    engine.  `rule_a` / `rule_b`: the CubeRules (None as in ArenaCube).  Returns dict(tally
+    int64[16], cube_tally int64[16], games_done int64[B], and [steps, B] each: cube uint8 = the
+    states before each decision, dsel / offer uint8 (0 none, 1 A, 2 B), passed bool)."""
+    from .cube import sanitise, unpack
+    ac = ArenaCube(rule_a, rule_b)
+    ra, rb = ac.rule_a, ac.rule_b
+    f = np.float32
+
+    def arr(k, dt):
+        return np.asarray(torch.as_tensor(trace[k]).cpu()).astype(dt)
+
+    mover, done, info = arr("cube_mover", np.int64), arr("done", np.int64), arr("info", np.int64)
+    eq_offer, eq_resp = arr("eq_offer", f), arr("eq_resp", f)
+    B, G, cap, T = int(batch), int(games_per_lane), ac.cap, done.shape[0]
+    lane = np.arange(B, dtype=np.int64)
+    cube, plies, games = np.zeros(B, np.uint8), np.zeros(B, np.int64), np.zeros(B, np.int64)
+    tally, ct = np.zeros(16, np.int64), np.zeros(16, np.int64)
+    states, dsels, offers = np.zeros((T, B), np.uint8), np.zeros((T, B), np.uint8), np.zeros((T, B), np.uint8)
+    passes = np.zeros((T, B), bool)
+    F_, C_ = {k: i for i, k in enumerate(FIELDS)}, {k: i for i, k in enumerate(CUBE_FIELDS)}
+    for t in range(T):
+        states[t] = cube
+        active = games < G
+        m = mover[t] & 1
+        a_moves = (m == 0) == (((lane + games) & 1) == 0)
+        k, o = unpack(sanitise(cube, cap))
+        access = (k < cap) & ((o == 0) | (o == m + 1))
+        d = active & (plies > 0) & access
+        dsel_a, dsel_b = d & a_moves, d & ~a_moves
+        dsels[t] = dsel_a + 2 * dsel_b
+        with np.errstate(invalid="ignore", over="ignore"):
+            ea, eb = (f(ra.scale) * eq_offer[t]).astype(f), (f(rb.scale) * eq_offer[t]).astype(f)
+            off_a = dsel_a & (ea >= f(ra.double_at)) & (ea <= f(ra.too_good_at))
+            off_b = dsel_b & (eb >= f(rb.double_at)) & (eb <= f(rb.too_good_at))
+            # B answers A's double by B's rule, A answers B's by A's
+            gives_up = np.where(off_a, (f(rb.scale) * eq_resp[t]).astype(f) > f(rb.pass_at),
+                                (f(ra.scale) * eq_resp[t]).astype(f) > f(ra.pass_at))
+        offers[t] = off_a + 2 * off_b
+        off = off_a | off_b
+        pas, take = off & gives_up, off & ~gives_up
+        passes[t] = pas
+        y = np.where(off_a, 1, -1) * (1 << k)
+        ct[C_["doubles_a"]] += off_a.sum()
+        ct[C_["doubles_b"]] += off_b.sum()
+        for name, v in (("cube_games", 1), ("cube_points_a", y), ("cube_points2", y * y), ("cube_wins_a", y > 0),
+                        ("cube_log2", k), ("pass_games", 1), ("pass_plies", plies), ("passes_a", off_b),
+                        ("passes_b", off_a)):
+            ct[C_[name]] += np.broadcast_to(np.asarray(v, np.int64), (B,))[pas].sum()
+        games = games + pas
+        plies = np.where(pas, 0, plies)
+        cube = np.where(pas, 0, np.where(take, (k + 1) | ((2 - m) << 4), cube)).astype(np.uint8)
+        # the step, cube_flush and advance
+        active = games < G
+        winner, score = ((info[t] >> 8) & 0xFF) - 1, (info[t] >> 16) & 0xFF
+        dn = active & (done[t] != 0)
+        fin = dn & (winner >= 0)
+        a_p1 = ((lane + games) & 1) == 0
+        a_won = fin & ((winner == 0) == a_p1)
+        b_won = fin & ~a_won
+        k = np.minimum(cube.astype(np.int64) & 15, cap)
+        s = np.where(ac.jacoby & (k == 0), 1, np.clip(score, 1, 3))
+        y = np.where(a_won, 1, -1) * (s << k)
+        for name, v in (("cube_games", 1), ("cube_points_a", y), ("cube_points2", y * y), ("cube_wins_a", y > 0),
+                        ("cube_log2", k)):
+            ct[C_[name]] += np.broadcast_to(np.asarray(v, np.int64), (B,))[fin].sum()
+        pts = np.where((score >= 1) & (score <= 3), score, 0)
+        for name, v in (("games", fin), ("wins_a", a_won), ("wins_b", b_won), ("points_a", a_won * pts),
+                        ("points_b", b_won * pts), ("gammons_a", a_won & (score == 2)),
+                        ("gammons_b", b_won & (score == 2)), ("backgammons_a", a_won & (score == 3)),
+                        ("backgammons_b", b_won & (score == 3)), ("games_a_p1", fin & a_p1),
+                        ("wins_a_p1", a_won & a_p1), ("wins_p1", fin & (winner == 0)), ("plies", active)):
+            tally[F_[name]] += int(np.asarray(v, np.int64).sum())
+        cube = np.where(dn, 0, cube).astype(np.uint8)
+        plies = np.where(dn, 0, plies + active)
+        games = games + fin
+    tally[ACTIVE] = int((games < G).sum())
+    return dict(tally=tally, cube_tally=ct, games_done=games, cube=states, dsel=dsels, offer=offers, passed=passes)
 
 
 # ------------------------------------------------------------------ players --
@@ -170,6 +364,7 @@ class Arena:
         self.sel_b = torch.zeros(self.B, dtype=torch.uint8, device=dev)
         self.tally = torch.zeros(16, dtype=torch.int64, device=dev)
         self.actions = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.cube_state = None          # play(cube=...): the cube stage's arrays, made on first use
 
     def _act(self, player, sel, step):
         a = player.act(self.eng, sel, step)
@@ -178,12 +373,29 @@ class Arena:
             raise ValueError("a player's act must return a contiguous int32[B] tensor on the engine's device")
         return a
 
-    def play(self, a, b, max_steps: int, trace: bool = False):
+    def _equity(self, rule, sel, out):
+        e = rule.equity(self.eng, sel, self.cube_state["scratch"], out)
+        if (not isinstance(e, torch.Tensor) or e.dtype != torch.float32 or e.device != self.eng.device
+                or not e.is_contiguous() or e.numel() != self.B):
+            raise ValueError("a cube rule's equity must be a contiguous float32[B] tensor on the engine's device")
+        return e
+
+    def play(self, a, b, max_steps: int, trace: bool = False, cube=None):
         """begin; then [a.act, b.act, merge, step, advance] until no lane is active or
         `max_steps` env steps ran (weak greedy players can shuffle for thousands of steps:
         the result then reports `unfinished_lanes` instead of hanging).  Returns the
         result dict (summarize); with trace=True also a dict of per-step [steps, B]
-        tensors: mover, n_moves, action, owner (0 none, 1 A, 2 B), done, info."""
+        tensors: mover, n_moves, action, owner (0 none, 1 A, 2 B), done, info.
+
+        `cube` (an ArenaCube): money play with the doubling cube.  Each step is
+        then [cube_sel; A's equity on dsel_a, B's on dsel_b; cube_offer; B's equity on off_a, A's
+        on off_b; cube_respond; reset(mask); cube_reseat; a.act, b.act, merge, step; cube_flush;
+        advance].  The host reads the active-lane count every SYNC_EVERY steps only when both
+        players and both rules are sync-free.  The result is summarize_cube's; the trace gains
+        cube (the state before the decision), cube_mover (the side on roll there), dsel and offer
+        (0 none, 1 A, 2 B), eq_offer (the equity the side on roll decided on, NaN off dsel),
+        eq_resp (the doubler's equity as the other side sees it, NaN off offer) and passed.
+        cube=None is exactly the path and result without the argument."""
         max_steps = int(max_steps)
         if max_steps < 0:
             raise ValueError(f"play: max_steps {max_steps} must be >= 0")
@@ -193,6 +405,8 @@ class Arena:
         L, eng, dev = _lib.load(), self.eng, self.eng.device
         recs = ctypes.c_void_p(eng.lanes_ptr())
         state = (_ptr(self.games_done), _ptr(self.sel_a), _ptr(self.sel_b), _ptr(self.tally))
+        if cube is not None and not isinstance(cube, ArenaCube):
+            raise ValueError("play: cube must be an ArenaCube or None")
         eng.reset(want_obs=False)
         check(L.bgx_arena_begin(recs, self.B, self.G, *state, _stream(dev)), "bgx_arena_begin")
         tr = None
@@ -202,9 +416,56 @@ class Arena:
                                 ("owner", torch.uint8), ("done", torch.uint8), ("info", torch.int32))}
             rec = torch.empty(self.B, 64, dtype=torch.uint8, device=dev)
         every = SYNC_EVERY if getattr(a, "sync_free", False) and getattr(b, "sync_free", False) else 1
+        if cube is not None:
+            if not cube.sync_free:
+                every = 1
+            if self.cube_state is None:
+                u8 = lambda: torch.zeros(self.B, dtype=torch.uint8, device=dev)         # noqa: E731
+                f32 = lambda: torch.zeros(self.B, dtype=torch.float32, device=dev)      # noqa: E731
+                self.cube_state = dict(cube=u8(), plies=torch.zeros(self.B, dtype=torch.int32, device=dev),
+                                       tally=torch.zeros(16, dtype=torch.int64, device=dev), dsel_a=u8(), dsel_b=u8(),
+                                       off_a=u8(), off_b=u8(), mask=u8(), eq_a=f32(), eq_b=f32(), er_a=f32(),
+                                       er_b=f32(), scratch=f32())
+            cs = self.cube_state
+            ra, rb, st = cube.rule_a.struct(), cube.rule_b.struct(), _stream(dev)
+            cstate = (_ptr(cs["cube"]), _ptr(cs["plies"]))
+            check(L.bgx_arena_cube_begin(self.B, *cstate, _ptr(cs["tally"]), st), "bgx_arena_cube_begin")
+            if trace:
+                tr.update({k: torch.zeros(max_steps, self.B, dtype=dt, device=dev)
+                           for k, dt in (("cube", torch.uint8), ("cube_mover", torch.uint8), ("dsel", torch.uint8),
+                                         ("offer", torch.uint8), ("eq_offer", torch.float32),
+                                         ("eq_resp", torch.float32), ("passed", torch.uint8))})
         steps = 0
         active = int(self.tally[ACTIVE].item())
         while active > 0 and steps < max_steps:
+            if cube is not None:
+                check(L.bgx_arena_cube_sel(recs, _ptr(self.sel_a), _ptr(self.sel_b), cstate[1], cstate[0], self.B,
+                                           cube.cap, _ptr(cs["dsel_a"]), _ptr(cs["dsel_b"]), st), "bgx_arena_cube_sel")
+                if trace:
+                    eng.records(out=rec)
+                    tr["cube"][steps] = cs["cube"]
+                    tr["cube_mover"][steps] = rec[:, R_CUR]
+                    tr["dsel"][steps] = cs["dsel_a"] + 2 * cs["dsel_b"]
+                eq_a = self._equity(cube.rule_a, cs["dsel_a"], cs["eq_a"])
+                eq_b = self._equity(cube.rule_b, cs["dsel_b"], cs["eq_b"])
+                check(L.bgx_arena_cube_offer(recs, _ptr(cs["dsel_a"]), _ptr(cs["dsel_b"]), _ptr(eq_a), _ptr(eq_b), ra, rb,
+                                             cstate[0], self.B, _ptr(cs["off_a"]), _ptr(cs["off_b"]), _ptr(cs["tally"]),
+                                             st), "bgx_arena_cube_offer")
+                # the doubler's equity as the other side sees it: B's on A's doubles, A's on B's
+                er_b = self._equity(cube.rule_b, cs["off_a"], cs["er_b"])
+                er_a = self._equity(cube.rule_a, cs["off_b"], cs["er_a"])
+                check(L.bgx_arena_cube_respond(recs, _ptr(cs["off_a"]), _ptr(cs["off_b"]), _ptr(er_a), _ptr(er_b), ra, rb,
+                                               self.B, self.G, *cstate, *state[:3], _ptr(self.tally), _ptr(cs["tally"]),
+                                               _ptr(cs["mask"]), st), "bgx_arena_cube_respond")
+                if trace:
+                    nan = float("nan")
+                    tr["offer"][steps] = cs["off_a"] + 2 * cs["off_b"]
+                    tr["eq_offer"][steps] = torch.where(cs["dsel_a"] != 0, eq_a, torch.where(cs["dsel_b"] != 0, eq_b, nan))
+                    tr["eq_resp"][steps] = torch.where(cs["off_a"] != 0, er_b, torch.where(cs["off_b"] != 0, er_a, nan))
+                    tr["passed"][steps] = cs["mask"]
+                eng.reset(lane_mask=cs["mask"], want_obs=False)
+                check(L.bgx_arena_cube_reseat(recs, _ptr(cs["mask"]), self.B, self.G, *state[:3], st),
+                      "bgx_arena_cube_reseat")
             act_a = self._act(a, self.sel_a, steps)
             act_b = self._act(b, self.sel_b, steps)
             check(L.bgx_arena_merge(_ptr(self.sel_a), _ptr(self.sel_b), _ptr(act_a), _ptr(act_b), self.B,
@@ -216,6 +477,10 @@ class Arena:
                 tr["action"][steps] = self.actions
                 tr["owner"][steps] = self.sel_a + 2 * self.sel_b
             _, _, done, info = eng.step(self.actions, want_obs=False, want_info=True)
+            if cube is not None:
+                check(L.bgx_arena_cube_flush(_ptr(self.sel_a), _ptr(self.sel_b), _ptr(done), _ptr(info), state[0],
+                                             self.B, int(cube.jacoby), cube.cap, *cstate, _ptr(cs["tally"]), st),
+                      "bgx_arena_cube_flush")
             check(L.bgx_arena_advance(recs, _ptr(done), _ptr(info), self.B, self.G, *state, _stream(dev)),
                   "bgx_arena_advance")
             if trace:
@@ -225,7 +490,10 @@ class Arena:
             if steps % every == 0 or steps == max_steps:
                 active = int(self.tally[ACTIVE].item())
         tally = self.tally.cpu().tolist()
-        res = summarize(tally, steps, tally[ACTIVE])
+        if cube is not None:
+            res = summarize_cube(tally, cs["tally"].cpu().tolist(), steps, tally[ACTIVE])
+        else:
+            res = summarize(tally, steps, tally[ACTIVE])
         if trace:
             return res, {k: v[:steps] for k, v in tr.items()}
         return res
@@ -265,8 +533,13 @@ def make_player(kind: str, net, seed: int = 0, top_k=None, margin=None):
     raise ValueError(f"player kind must be one of {PLAYER_KINDS}, got {kind!r}")
 
 
+CUBE_SIDE_DEFAULTS = {"cube_double": 0.40, "cube_pass": 0.50, "cube_too_good": math.inf, "cube_scale": 1.0,
+                      "cube_net": None, "cube_lookahead": 1}
+
+
 class _Parser(argparse.ArgumentParser):
-    """The move-filter options are an error for any player but a 2ply one with weights."""
+    """The move-filter options are an error for any player but a 2ply one with weights; a cube
+    option is an error without --cube, a side's cube option for a `random` side (it has no rule)."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -287,6 +560,26 @@ class _Parser(argparse.ArgumentParser):
             k = getattr(ns, f"bearoff1_{side}")
             if k is not None and not 1 <= k <= 15:
                 self.error(f"--bearoff1-{side} takes a number of checkers in 1..15")
+        for side in "ab":
+            given = [k for k in CUBE_SIDE_DEFAULTS if getattr(ns, f"{k}_{side}") is not None]
+            flags = ", ".join("--" + k.replace("_", "-") + "-" + side for k in given)
+            if given and not ns.cube:
+                self.error(f"{flags} need --cube")
+            if given and getattr(ns, side) == "random":
+                self.error(f"{flags}: a random side has no cube rule")
+            for k in ("cube_double", "cube_pass", "cube_scale", "cube_too_good"):
+                v = getattr(ns, f"{k}_{side}")
+                if v is not None and math.isnan(v):
+                    self.error(f"--{k.replace('_', '-')}-{side} is NaN")
+            for k, v in CUBE_SIDE_DEFAULTS.items():
+                if getattr(ns, f"{k}_{side}") is None:
+                    setattr(ns, f"{k}_{side}", v)
+        if not ns.cube and (ns.jacoby or ns.cube_cap is not None):
+            self.error("--jacoby / --cube-cap need --cube")
+        if ns.cube_cap is None:
+            ns.cube_cap = 6
+        if not 0 <= ns.cube_cap <= 10:
+            self.error("--cube-cap takes a number in 0..10")
         return ns
 
 
@@ -313,7 +606,47 @@ def build_parser() -> argparse.ArgumentParser:
         ap.add_argument(f"--bearoff1-{side}", type=int, default=None, metavar="K",
                         help=f"player {side.upper()} moves by the one-sided bearoff table for K checkers a side "
                              f"(1..15) in every pure home-board race; inside --bearoff-{side}'s table that one plays")
+    ap.add_argument("--cube", action="store_true",
+                    help="money play with the doubling cube: each side doubles, takes and passes by its own rule on "
+                         "its own net's equity; the result is A's cubeful points per game")
+    ap.add_argument("--cube-cap", type=int, default=None, help="no double once the cube shows 2^cap (0..10; default 6)")
+    ap.add_argument("--jacoby", action="store_true", help="a game that ends with the cube centred at 1 counts 1 point")
+    for side in "ab":
+        S = side.upper()
+        ap.add_argument(f"--cube-double-{side}", type=float, default=None,
+                        help=f"{S} doubles from this equity on (default 0.40)")
+        ap.add_argument(f"--cube-pass-{side}", type=float, default=None,
+                        help=f"{S} passes a double above this equity of the doubler (default 0.50)")
+        ap.add_argument(f"--cube-too-good-{side}", type=float, default=None,
+                        help=f"{S} plays on undoubled above this equity (default inf)")
+        ap.add_argument(f"--cube-scale-{side}", type=float, default=None,
+                        help=f"points per unit of {S}'s value (default 1.0)")
+        ap.add_argument(f"--cube-net-{side}", default=None, metavar="PATH",
+                        help=f"the net whose value head gives {S}'s equity (default: {S}'s own weights)")
+        ap.add_argument(f"--cube-lookahead-{side}", type=int, default=None, choices=[0, 1],
+                        help=f"{S}'s equity: 0 the head's static value (sync-free), 1 its mean best 1-ply value over "
+                             "the 21 rolls (default)")
     return ap
+
+
+def cube_from_args(args, nets, device):
+    """The ArenaCube of a parsed command line (None without --cube): a side with weights gets a
+    CubeRule on its --cube-net-x, else its own net; a random side has no rule."""
+    if not args.cube:
+        return None
+    from .cube import CubeRule
+    from .search import ValueHead
+    rules = []
+    for side, net in zip("ab", nets):
+        if net is None:
+            rules.append(None)
+            continue
+        path = getattr(args, f"cube_net_{side}")
+        vh = ValueHead(net if path is None else load_net(path, device))
+        rules.append(CubeRule(vh, scale=getattr(args, f"cube_scale_{side}"), double_at=getattr(args, f"cube_double_{side}"),
+                              pass_at=getattr(args, f"cube_pass_{side}"), too_good_at=getattr(args, f"cube_too_good_{side}"),
+                              cap=args.cube_cap, jacoby=args.jacoby, lookahead=getattr(args, f"cube_lookahead_{side}")))
+    return ArenaCube(*rules)
 
 
 def main(argv=None):
@@ -338,7 +671,8 @@ def main(argv=None):
     arena =Arena(args.batch, args.games_per_lane, seed=args.seed, dice=args.dice, max_moves=max_moves, device=dev)
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    res = arena.play(players[0], players[1], max_steps=args.max_steps)
+    cube = cube_from_args(args, nets, dev)
+    res = arena.play(players[0], players[1], max_steps=args.max_steps, cube=cube)
     dt = time.perf_counter() - t0
     res.update(a=args.a, b=args.b, player_a="random" if nets[0] is None else args.player_a,
                player_b="random" if nets[1] is None else args.player_b, batch=args.batch,
@@ -346,6 +680,10 @@ def main(argv=None):
                top_k_a=args.top_k_a, top_k_b=args.top_k_b, margin_a=args.margin_a, margin_b=args.margin_b,
                bearoff_a=args.bearoff_a, bearoff_b=args.bearoff_b,
                **{k: v for k, v in (("bearoff1_a", args.bearoff1_a), ("bearoff1_b", args.bearoff1_b)) if v is not None},
+               **({"cube": True, "cube_cap": args.cube_cap, "jacoby": args.jacoby,
+                   **{f"{k}_{side}": None if getattr(args, f"{k}_{side}") == math.inf else getattr(args, f"{k}_{side}")
+                      for side, n in zip("ab", nets) if n is not None for k in CUBE_SIDE_DEFAULTS}}
+                  if args.cube else {}),
                games_per_s=res["games"] / dt if dt > 0 else 0.0,
                env_steps_per_s=res["steps"] * args.batch / dt if dt > 0 else 0.0)
     print(json.dumps(res), flush=True)

@@ -74,10 +74,16 @@ class CubeRule:
     engine's device with the mover's equity (entries off dsel are ignored).  `scale` plays the
     part of the luck adjustment's c: it turns the value's unit into points.  The rule presumes a
     mover's-view value (positive = good for the side on roll), which is what `--returns selfplay`
-    trains; a net trained on another target gives decisions that mean nothing."""
+    trains; a net trained on another target gives decisions that mean nothing.
+
+    `lookahead` (a ValueHead's only): 1, the default, is the roll_luck mean above, which
+    synchronises the host on every call; 0 is the head's own output for the position, the mover's
+    static value (bgx_value_lanes on the selected lanes: sync-free and graph-capturable).
+    `sync_free`: the equity never waits for the device -- a head with lookahead 0, or a callable
+    that declares it (its own attribute sync_free)."""
 
     def __init__(self, value, scale: float = 1.0, double_at: float = 0.40, pass_at: float = 0.50,
-                 too_good_at: float = math.inf, cap: int = 6, jacoby: bool = False):
+                 too_good_at: float = math.inf, cap: int = 6, jacoby: bool = False, lookahead: int = 1):
         from .search import ValueHead
         if not isinstance(value, ValueHead) and not callable(value):
             raise ValueError("CubeRule: value must be a search.ValueHead or a callable f(eng, dsel)")
@@ -86,7 +92,11 @@ class CubeRule:
                 raise ValueError(f"CubeRule: {name} is NaN")
         if int(cap) != cap or not 0 <= int(cap) <= MAX_CAP:
             raise ValueError(f"CubeRule: cap must be in 0..{MAX_CAP}, got {cap!r}")
+        if isinstance(lookahead, bool) or lookahead not in (0, 1):
+            raise ValueError(f"CubeRule: lookahead must be 0 or 1, got {lookahead!r}")
         self.value, self.is_head = value, isinstance(value, ValueHead)
+        self.lookahead = int(lookahead)
+        self.sync_free = self.lookahead == 0 if self.is_head else bool(getattr(value, "sync_free", False))
         self.scale, self.double_at, self.pass_at = float(scale), float(double_at), float(pass_at)
         self.too_good_at, self.cap, self.jacoby = float(too_good_at), int(cap), bool(jacoby)
         # equity calls so far and, with a value head, the lanes they covered (rows) and the leaves
@@ -98,6 +108,9 @@ class CubeRule:
     def equity(self, eng, dsel: torch.Tensor, scratch: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
         """The mover's equity on the dsel lanes, float32[B] on the engine's device."""
         self.totals["calls"] += 1
+        if self.is_head and self.lookahead == 0:
+            from .search import value_lanes
+            return value_lanes(eng, self.value, sel=dsel, out=out)
         if self.is_head:
             from .search import roll_luck
             stats = roll_luck(eng, self.value, sel=dsel, out=(scratch, out))[2]

@@ -595,11 +595,14 @@ class PPOTrainer:
         torch.save(self.net.state_dict(), path)
 
     def evaluate(self, opponent="random", player: str = "policy", batch: int = 4096, games_per_lane: int = 2,
-                 max_steps: int = 4000, opponent_player: str = "policy", top_k=None, margin=None):
+                 max_steps: int = 4000, opponent_player: str = "policy", top_k=None, margin=None, cube=False):
         """The current weights as player A of a head-to-head match (bgx.arena) against
         `opponent`: "random", a PolicyNet or the path of a saved state_dict (playing as
         `opponent_player`).  `player`: how A decides ("policy" sample, "greedy" argmax,
         "1ply", "2ply"; `top_k` / `margin`: the 2ply player's move filter, search.two_ply).
+        `cube`: True plays money games with the doubling cube, each side by a
+        default cube.CubeRule on its own weights' value head (a random opponent has no rule); an
+        arena.ArenaCube is used as given.  The result is then arena.summarize_cube's.
         Returns the arena's result dict.  Training is not disturbed: the
         match runs on an engine and seeds of its own (the k-th evaluation of a trainer is
         seeded from (seed, k)), the players pack the weights into buffers of their own, and
@@ -616,7 +619,24 @@ class PPOTrainer:
         a = AR.make_player(player, self.net, seed=base + 1, top_k=top_k, margin=margin)
         b = AR.make_player(opponent_player, opponent, seed=base + 2)
         ar = AR.Arena(batch, games_per_lane, seed=base, dice="philox", max_moves=self.A, device=self.dev)
-        return ar.play(a, b, max_steps=max_steps)
+        if cube is True:
+            from .cube import CubeRule
+            from .search import ValueHead
+            cube = AR.ArenaCube(CubeRule(ValueHead(self.net)),
+                                None if opponent is None or isinstance(opponent, str) else CubeRule(ValueHead(opponent)))
+        return ar.play(a, b, max_steps=max_steps, cube=cube or None)
+
+
+def eval_metrics(ev: dict) -> dict:
+    """An evaluation's entries of the metrics line.  With the cube (arena.summarize_cube's result)
+    eval_win_rate and eval_ppg are those of the games played to the end, eval_games counts every
+    game, and eval_ppg_cubeful and eval_pass_share are added."""
+    plain = ev.get("played_out", ev)
+    m = {"eval_win_rate": plain["win_rate_a"], "eval_ppg": plain["ppg_a"], "eval_games": ev["games"],
+         "eval_unfinished": ev["unfinished_lanes"]}
+    if "played_out" in ev:
+        m.update(eval_ppg_cubeful=ev["ppg_cubeful_a"], eval_pass_share=ev["pass_share"])
+    return m
 
 
 def main():
@@ -643,6 +663,8 @@ def main():
                     help="--eval-player 2ply: search only the top-k 1-ply moves (the move filter)")
     ap.add_argument("--eval-margin", type=float, default=None,
                     help="--eval-player 2ply: ... within this 1-ply value of the best move")
+    ap.add_argument("--eval-cube", action="store_true",
+                    help="evaluate at money play with the doubling cube: adds eval_ppg_cubeful and eval_pass_share")
     args = ap.parse_args()
     if (args.eval_top_k is not None or args.eval_margin is not None) and args.eval_player != "2ply":
         ap.error("--eval-top-k / --eval-margin need --eval-player 2ply")
@@ -666,9 +688,8 @@ def main():
         if args.eval_every > 0 and (u + 1) % args.eval_every == 0:
             ev = tr.evaluate(args.eval_opponent, player=args.eval_player, batch=args.eval_batch,
                              games_per_lane=args.eval_games, max_steps=args.eval_max_steps,
-                             top_k=args.eval_top_k, margin=args.eval_margin)
-            m.update({"eval_win_rate": ev["win_rate_a"], "eval_ppg": ev["ppg_a"], "eval_games": ev["games"],
-                      "eval_unfinished": ev["unfinished_lanes"]})
+                             top_k=args.eval_top_k, margin=args.eval_margin, cube=args.eval_cube)
+            m.update(eval_metrics(ev))
         if tr.rank == 0:
             print(json.dumps(m), flush=True)
             if args.metrics:

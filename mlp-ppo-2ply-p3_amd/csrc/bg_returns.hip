@@ -297,3 +297,6 @@ extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, floa
 
 // the cubeful exact bearoff table: bg_cube.h's byte decoding, bg_bearoff1.h's records and helpers
 #include "bg_bearoff_cube.h"
+
+// the doubling cube of the head-to-head arena: bg_cube.h's rule in two halves, the same helpers
+#include "bg_arena_cube.h"
