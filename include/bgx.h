@@ -70,25 +70,27 @@ enum bgx_dice_mode {
 int bgx_engine_create(int device, int32_t batch, int32_t max_moves, uint64_t seed, int32_t dice_mode,
                       int32_t auto_reset, int32_t match_length, bgx_engine** out);
 /* Order `stream` after every piece of a step still running on the engine's own
- * side streams (the next step's dispatch order): a HIP graph capture of steps
+ * side streams (the next step's order pass): a HIP graph capture of steps
  * calls it before capturing and as its last captured call, so the graph holds no
  * work it does not join. */
 int bgx_engine_join(bgx_engine* e, void* stream);
 /* Test accessor of the dispatch order (Philox engines; never on a step's path): joins a
- * pending order into `stream`, copies the order perm (int32[batch], launch position ->
- * lane), the resolved cost classes (uint8[batch], 0 = heaviest .. 4) and the Philox
- * counters with their roll-cache bits (uint64[batch]) to HOST buffers, and synchronises
- * the stream.  Any pointer may be NULL.  BGX_EINVAL for perm / classes when the engine
+ * pending order pass into `stream`, copies the order perm (int32[batch], launch position ->
+ * lane) the next step will use, the resolved cost classes (uint8[batch], 0 = heaviest .. 4)
+ * and the Philox counters with their roll-cache bits (uint64[batch]) to HOST buffers, and
+ * synchronises the stream.  A step or reset leaves the classes; the order itself is laid
+ * out at the start of the next bgx_step (with that step's actions), so for perm the call
+ * runs that pass's perm-only form on `stream` -- the next step computes the same either way.  Any pointer may be NULL.  BGX_EINVAL for perm / classes when the engine
  * has no order (MT dice, BGX_ORDER 0) or has not built one yet (before the first reset). */
 int bgx_engine_order(bgx_engine* e, int32_t* perm_host, uint8_t* cls_host, uint64_t* ctr_host, void* stream);
 /* Where a Philox step's light launch (the non-predicted-doubles rest of the dispatch
- * order) and the next step's dispatch order run: fork = 1 (default) on the engine's
+ * order) and the next step's order pass (classes and counts) run: fork = 1 (default) on the engine's
  * side stream, fork-joined on events beside the heavy launch; fork = 0 on the caller's
  * stream after it.  Same results either way.  A HIP graph of fork = 0 steps is one
  * linear chain: several such engines on their own streams then map one-to-one onto
  * the hardware queues (bench.py C3: 4 shards), where forked graphs' internal streams
  * share queues with the other shards' and serialise them.
- * Turning the fork off joins a pending dispatch order into `stream`. */
+ * Turning the fork off joins a pending order pass into `stream`. */
 int bgx_engine_set_fork(bgx_engine* e, int32_t fork, void* stream);
 int bgx_engine_destroy(bgx_engine* e);
 

@@ -172,8 +172,10 @@ struct Args {
     int cap_main;             // bgx_movegen's main-table cap (cap_fast<9>; tests: BGX_MOVEGEN_CAP)
     // dispatch order (Philox mode): each step leaves its lane's pre-class byte in pre;
     // k_order_count resolves it with the lane's next roll into the cost class cls, and
-    // k_order_scatter turns the classes into perm (heaviest first) for the next launch.
+    // k_step_gather, at the start of the next step, turns the classes into perm (heaviest
+    // first) and lays each lane's step block at its dispatch position.
     int32_t* perm;            // blockIdx -> lane, or null (identity)
+    const uint8_t* blk;       // [B][kBlkBytes] step blocks by dispatch position (this step's split launch), or null
     uint8_t* cls;             // [B] predicted cost class (written by k_order_count), or null
     uint8_t* pre;             // [B] pre-class byte (pre_class), written by k_step / k_reset; null with cls
     int xcd;                  // B % 128 == 0: XCD-aware dispatch (16-lane runs per XCD, bg_engine.hip k_order_*)
@@ -194,6 +196,15 @@ __device__ __forceinline__ int lane_of_block(const Args& A, int bi) {
 }
 
 constexpr int kClasses = 5;
+
+// Step block of dispatch position p (k_step_gather writes it, the split launch's wave
+// blockIdx + base = p starts from it), 32 bytes, aligned:
+//   int32 lane | int32 action as passed | uint64 chosen move |
+//   uint64 Philox counter with its cache bits | 8 bytes of zero
+// The chosen move is moves[lane][a], a = action < 0 ? action + max_moves : action, when
+// 0 <= a < max_moves, else 0; whether a is a legal index is the step wave's decision
+// (apply_lane checks it against the record's move count and ignores the move otherwise).
+constexpr int kBlkBytes = 32;
 
 // Philox counters (the low 48 bits) carry in bits 48-63 the lane's next roll as
 // the order pass after the previous step predicted it (predict_class): valid << 15 |
@@ -423,8 +434,10 @@ __device__ __forceinline__ int apply_move_bytes(int bv, uint32_t mlo, uint32_t m
 }
 
 // backgammon_env.py:115-191 up to (not including) roll/update_legal_moves.
+// HAVE_MV: the chosen move comes with the call (the step block's header) instead of from the move list.
+template <bool HAVE_MV = false>
 __device__ __forceinline__ int apply_lane(int bv, int gi, int action, const Args& A, float* reward, uint8_t* done,
-                                          int32_t* info) {
+                                          int32_t* info, uint64_t chosen = 0) {
     const int mover = rd(bv, R_CUR);
     int winner = -1, score = 0, kind = 0, dn = 0;
     float rew = 0.0f;
@@ -442,7 +455,7 @@ __device__ __forceinline__ int apply_lane(int bv, int gi, int action, const Args
             if (a < 0 || a >= n) {                        // :143-149 invalid action
                 rew = -1.0f; kind = 2;
             } else {                                      // :152-188
-                const uint64_t mv = A.moves[(size_t)gi * A.max_moves + a];
+                const uint64_t mv = HAVE_MV ? chosen : A.moves[(size_t)gi * A.max_moves + a];
                 bv = apply_move_bytes(bv, (uint32_t)mv, (uint32_t)(mv >> 32), mover);
                 if (rd(bv, 50 + mover) == 15) {            // win (:156-182)
                     const int opp = 1 - mover;
@@ -514,9 +527,13 @@ struct bgx_engine {
     bg::Args a{};
     uint4* slow_tables{nullptr};
     int slow_waves{bg::kSlowWaves};
-    int32_t* perm{nullptr};        // dispatch order for k_step (Philox mode), built by k_order
-    bool perm_valid{false};
-    int32_t* order_cnt{nullptr};   // k_order_count -> k_order_scatter, [B/256+1][8 sub-lists][kClasses]
+    int32_t* perm{nullptr};        // dispatch order for k_step (Philox mode), built by k_step_gather
+    uint8_t* blk{nullptr};         // [B][kBlkBytes] step blocks by dispatch position (engines with an order)
+    // the order's second pass is due: set by every k_order_count launch (step and reset),
+    // cleared when bgx_step runs k_step_gather, which the same step's count pass follows --
+    // so it is set before and after every step (a captured step replays beside eager ones)
+    bool gather_due{false};
+    int32_t* order_cnt{nullptr};   // k_order_count -> k_step_gather, [B/256+1][8 sub-lists][kClasses]
     hipStream_t step_side{nullptr};    // the light launch beside the heavy one, and the next dispatch order
     hipEvent_t step_ev[4]{};         // fork, light done, heavy done, dispatch order done
     bool order_pending{false};         // the next step's launches wait for step_ev[3] (join_order)
@@ -545,9 +562,9 @@ struct bgx_engine {
     bool use_valid{false};             // use_ev marks the last call (false: none yet, or it was captured)
 };
 
-// Stream s waits for a dispatch order still running on the side stream (the order pass of
-// the last forked step: it writes perm, cls, the counters' roll cache and the other set of
-// overflow counters).  Only the calls that read or rewrite those join; the rest run beside it.
+// Stream s waits for a count pass still running on the side stream (the order pass of
+// the last forked step: it writes cls, the block counts, the counters' roll cache and the
+// other set of overflow counters).  Only the calls that read or rewrite those join; the rest run beside it.
 inline hipError_t join_order(bgx_engine* e, hipStream_t s) {
     if (!e->order_pending) return hipSuccess;
     const hipError_t err = hipStreamWaitEvent(s, e->step_ev[3], 0);

@@ -41,15 +41,41 @@ using namespace bg;
 // One lane's step: apply (PHASE 0/1), roll + movegen (PHASE 0/2), record, the
 // next dispatch class's pre-class byte (the order pass resolves it).
 // DICE: the dice mode as a compile-time constant, or -1 = A.dice_mode (roll_lane).
-template <int PHASE, int LOG, int MEMO, bool NO_DOUBLES = false, int DICE = -1>
-__device__ __forceinline__ void step_lane(const Args& A, int gi, uint4* tab, uint4* memo, const int32_t* actions,
+// BLK (the split launch of a step with a dispatch order): `at` is the wave's dispatch
+// position, and the lane, its action, the chosen move and the counter are in the step block
+// k_step_gather laid there, addressed by blockIdx alone; the record follows from the lane:
+// two levels of loads.  Otherwise `at` is the lane and the chain is (perm ->) lane ->
+// record, action, counter -> move: three.  Every store goes to the lane's own arrays.
+template <int PHASE, int LOG, int MEMO, bool NO_DOUBLES = false, int DICE = -1, bool BLK = false>
+__device__ __forceinline__ void step_lane(const Args& A, int at, uint4* tab, uint4* memo, const int32_t* actions,
                                           float* obs, float* reward, uint8_t* done, int32_t* info) {
     const uint64_t t0 = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-    // issue the independent loads together (record, action, dice counter)
-    int bv = load_rec(A, gi);
-    const int act = PHASE != 2 ? (int)ufl((uint32_t)actions[gi]) : 0;
-    uint64_t ctr = (DICE >= 0 ? DICE : A.dice_mode) == BGX_DICE_PHILOX ? A.ctr[gi] : 0;
-    if (PHASE != 2) bv = apply_lane(bv, gi, act, A, reward, done, info);
+    int gi = at, bv, act;
+    uint64_t ctr, chosen = 0;
+    if (BLK) {
+        const uint8_t* b = A.blk + (size_t)at * kBlkBytes;
+        // the header through the constant address space (no kernel of the launch writes the
+        // blocks): wave-uniform, so its six words are scalar loads
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        const uintptr_t hp = (uintptr_t)b;
+        const u32x4 h = *(const __attribute__((address_space(4))) u32x4*)hp;
+        const u32x2 c = *(const __attribute__((address_space(4))) u32x2*)(hp + 16);
+        // the lane in a register of its own: it lives to the wave's end, and left in the
+        // loaded four-register tuple it cost the heavy kernel 26 more SGPR spills (measured
+        // with the record in the block as well, profiles/step_block)
+        asm volatile("s_mov_b32 %0, %1" : "=s"(gi) : "s"(h.x));
+        bv = load_rec(A, gi);
+        act = (int)h.y;
+        chosen = (uint64_t)h.z | ((uint64_t)h.w << 32);
+        ctr = (uint64_t)c.x | ((uint64_t)c.y << 32);
+    } else {
+        // issue the independent loads together (record, action, dice counter)
+        bv = load_rec(A, gi);
+        act = PHASE != 2 ? (int)ufl((uint32_t)actions[gi]) : 0;
+        ctr = (DICE >= 0 ? DICE : A.dice_mode) == BGX_DICE_PHILOX ? A.ctr[gi] : 0;
+    }
+    if (PHASE != 2) bv = apply_lane<BLK>(bv, gi, act, A, reward, done, info, chosen);
     if (PHASE != 1) {
         bv = advance_lane<LOG, MEMO == 2 ? 2 : 0, NO_DOUBLES, DICE>(bv, gi, A, tab, memo, &ctr);
         if (obs) write_obs(bv, obs + (size_t)gi * 198);
@@ -70,15 +96,16 @@ __device__ __forceinline__ void step_lane(const Args& A, int gi, uint4* tab, uin
 // NO_DOUBLES: doubles rolls are deferred to the overflow tiers (light launch).
 // DICE: BGX_DICE_PHILOX for the split launch of a Philox engine (no MT19937 or shared-dice
 // code in the two kernels where the step's time goes), -1 = every mode (Args::dice_mode).
-template <int PHASE, int LOG, int MEMO = 1, bool NO_DOUBLES = false, int WPE = 1, int DICE = -1>
+// BLK: the wave starts from the step block of its dispatch position (A.blk, step_lane).
+template <int PHASE, int LOG, int MEMO = 1, bool NO_DOUBLES = false, int WPE = 1, int DICE = -1, bool BLK = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_step(Args A, const int32_t* actions, float* obs, float* reward, uint8_t* done,
                                              int32_t* info, int base) {
     __shared__ uint4 tab[1 << LOG];
     __shared__ uint4 memo_[MEMO == 1 ? kMemoSlots : 1];
     uint4* memo = MEMO == 1 ? memo_ : MEMO == 2 ? tab : nullptr;
     const int bi = (int)blockIdx.x + base;
-    const int gi = A.perm ? (int)ufl((uint32_t)A.perm[bi]) : lane_of_block(A, bi);
-    step_lane<PHASE, LOG, MEMO, NO_DOUBLES, DICE>(A, gi, tab, memo, actions, obs, reward, done, info);
+    const int at = BLK ? bi : A.perm ? (int)ufl((uint32_t)A.perm[bi]) : lane_of_block(A, bi);
+    step_lane<PHASE, LOG, MEMO, NO_DOUBLES, DICE, BLK>(A, at, tab, memo, actions, obs, reward, done, info);
 }
 
 template <int LOG>
@@ -165,13 +192,36 @@ __global__ __launch_bounds__(kCountThreads) void k_order_count(const uint8_t* pr
     if (t < kXcd * kClasses) cnt[blockIdx.x * kXcd * kClasses + t] = sc[t / kClasses][t % kClasses];
 }
 
-// pass 2: position (within the lane's sub-list) = (lanes of lower classes) +
-// (class-c lanes of earlier blocks) + (class-c lanes earlier in this block)
-__global__ __launch_bounds__(1024) void k_order_scatter(const uint8_t* cls, const int32_t* cnt, int32_t* perm, int B,
-                                                        int ncnt, int xcd) {
-    constexpr int NC = kXcd * kClasses, STRIPES = 1024 / NC, PER = 1024 / kCountThreads;
-    __shared__ int tot[NC], pre[NC], wsum[16][4][kClasses];
+// pass 2, at the start of the next step (bgx_step, which knows the actions by then):
+// position (within the lane's sub-list) = (lanes of lower classes) + (class-c lanes of
+// earlier blocks) + (class-c lanes earlier in this block), written to perm; and with
+// BLOCKS the lane's step block (kBlkBytes: lane, action, chosen move, counter) laid at that
+// position, so the step wave of dispatch position p starts from blk[p] where it would chase
+// perm[p] -> action / counter of the lane -> the move.  Here those levels are in flight for
+// a whole block of lanes at once.  Without BLOCKS (the accessor bgx_engine_order between
+// two steps) only perm is written.  A block of kGatherThreads lanes (pass 1's block: one
+// count row each); thread t resolves lane b * kGatherThreads + t and writes its block with
+// two 16-byte stores.
+constexpr int kGatherThreads = kCountThreads;
+template <bool BLOCKS>
+__global__ __launch_bounds__(kGatherThreads) void k_step_gather(const uint8_t* cls, const int32_t* cnt, int32_t* perm,
+                                                                int B, int ncnt, int xcd, const uint64_t* moves,
+                                                                const uint64_t* ctr, const int32_t* actions,
+                                                                int max_moves, uint8_t* blk) {
+    constexpr int T = kGatherThreads, NC = kXcd * kClasses, STRIPES = T / NC, PER = T / kCountThreads;
+    __shared__ int tot[NC], pre[NC], wsum[T / 64][4][kClasses];
     const int t = threadIdx.x, b = blockIdx.x, w = t >> 6, l = t & 63;
+    const int i = b * T + t;
+    // the loads nothing here orders: the lane's action and counter, then the move the
+    // action names -- read only inside the lane's own list
+    int act = 0;
+    uint64_t cv = 0, mv = 0;
+    if (BLOCKS && i < B) {
+        act = actions[i];
+        cv = ctr[i];
+        const int a = act < 0 ? act + max_moves : act;
+        if (a >= 0 && a < max_moves) mv = moves[(size_t)i * max_moves + a];
+    }
     if (t < NC) { tot[t] = 0; pre[t] = 0; }
     __syncthreads();
     // the 40 counters summed over pass 1's ncnt blocks (PER of them per block of this
@@ -187,7 +237,6 @@ __global__ __launch_bounds__(1024) void k_order_scatter(const uint8_t* cls, cons
         if (a_tot) atomicAdd(&tot[k], a_tot);
         if (a_pre) atomicAdd(&pre[k], a_pre);
     }
-    const int i = b * 1024 + t;
     const int c = order_class(cls, i, B);
     const int s = xcd ? (l >> 4) : 0;                 // the lane's 16-lane run within the wave
     const uint64_t seg = xcd ? (0xFFFFull << (16 * s)) : ~0ull;
@@ -199,13 +248,19 @@ __global__ __launch_bounds__(1024) void k_order_scatter(const uint8_t* cls, cons
         if (l < 4) wsum[w][l][k] = __popcll(m & (xcd ? (0xFFFFull << (16 * l)) : (l == 0 ? ~0ull : 0ull)));
     }
     __syncthreads();
-    if (c < kClasses) {
+    if (c < kClasses) {                                   // (padding past B: no position, no block)
         const int x = xcd ? ((4 * w + s) & 7) : 0;
         int pos = pre[x * kClasses + c] + rank;
         for (int k = 0; k < c; ++k) pos += tot[x * kClasses + k];
         // earlier waves of this block holding runs of the same sub-list: w' = w (mod 2)
         for (int v = xcd ? (w & 1) : 0; v < w; v += xcd ? 2 : 1) pos += wsum[v][s][c];
-        perm[xcd ? pos * kXcd + x : pos] = i;
+        const int p = xcd ? pos * kXcd + x : pos;
+        perm[p] = i;
+        if (BLOCKS) {
+            uint4* o = (uint4*)(blk + (size_t)p * kBlkBytes);
+            o[0] = make_uint4((uint32_t)i, (uint32_t)act, (uint32_t)mv, (uint32_t)(mv >> 32));
+            o[1] = make_uint4((uint32_t)cv, (uint32_t)(cv >> 32), 0u, 0u);
+        }
     }
 }
 
@@ -760,14 +815,27 @@ long long bgx_dbg_int(const char* name, long long dflt) {
 // 512-slot dedup table
 #define LAUNCH_LOG(K, grid, s, ...) hipLaunchKernelGGL(K<9>, grid, dim3(64), 0, s, __VA_ARGS__)
 
-static void launch_order(bgx_engine* e, hipStream_t s) {
-    const int nblk = (e->a.B + 1023) / 1024, ncnt = (e->a.B + kCountThreads - 1) / kCountThreads;
+// The order's first pass, at the end of a step or reset: classes, roll cache, block counts.
+// Its second pass (launch_gather) is due from here until the next bgx_step runs it.
+static void launch_count(bgx_engine* e, hipStream_t s) {
+    const int ncnt = (e->a.B + kCountThreads - 1) / kCountThreads;
     hipLaunchKernelGGL(k_order_count, dim3(ncnt), dim3(kCountThreads), 0, s, e->a.pre, e->a.cls, e->a.ctr, e->a.key0, e->a.key1,
                        e->order_cnt, e->a.B, e->ovf_base + 4 * (e->ovf_parity ^ 1), e->a.xcd);
     e->ovf_next_zeroed = true;
-    hipLaunchKernelGGL(k_order_scatter, dim3(nblk), dim3(1024), 0, s, e->a.cls, e->order_cnt, e->perm, e->a.B, ncnt,
-                       e->a.xcd);
-    e->perm_valid = true;
+    e->gather_due = true;
+}
+
+// The order's second pass on stream s, which has joined the count pass: perm, and with
+// `actions` (bgx_step) the step blocks of the step that follows on s.
+static void launch_gather(bgx_engine* e, hipStream_t s, const int32_t* actions) {
+    const Args& A = e->a;
+    const int nblk = (A.B + kGatherThreads - 1) / kGatherThreads, ncnt = (A.B + kCountThreads - 1) / kCountThreads;
+    if (actions)
+        hipLaunchKernelGGL(k_step_gather<true>, dim3(nblk), dim3(kGatherThreads), 0, s, A.cls, e->order_cnt, e->perm, A.B,
+                           ncnt, A.xcd, A.moves, A.ctr, actions, A.max_moves, e->blk);
+    else
+        hipLaunchKernelGGL(k_step_gather<false>, dim3(nblk), dim3(kGatherThreads), 0, s, A.cls, e->order_cnt, e->perm, A.B,
+                           ncnt, A.xcd, nullptr, nullptr, nullptr, 0, nullptr);
 }
 
 // bgx_step's device arguments
@@ -786,7 +854,10 @@ static void launch_heavy(hipStream_t s, const Args& a, int grid, const StepIo& i
     // (VGPR-bound, 4 waves/SIMD) beats a bigger table (C3: 1,024 slots + memo 242 M/s,
     // 512 slots + memo inside 284 M/s, no memo 288 M/s; measured round 2)
     // (MT_LANE engines have no order and step every lane here, with the generic kernel)
-    if (a.dice_mode == BGX_DICE_PHILOX)
+    if (a.blk)                                    // with a dispatch order: from the step blocks
+        hipLaunchKernelGGL((k_step<0, 9, 0, false, 1, BGX_DICE_PHILOX, true>), dim3(grid), dim3(64), 0, s, a, io.actions,
+                           io.obs, io.reward, io.done, io.info, 0);
+    else if (a.dice_mode == BGX_DICE_PHILOX)
         hipLaunchKernelGGL((k_step<0, 9, 0, false, 1, BGX_DICE_PHILOX>), dim3(grid), dim3(64), 0, s, a, io.actions,
                            io.obs, io.reward, io.done, io.info, 0);
     else
@@ -797,8 +868,8 @@ static void launch_heavy(hipStream_t s, const Args& a, int grid, const StepIo& i
 // The order's positions from `heavy` on: a 256-slot table, no memo, no doubles code (4 KB,
 // 49 VGPRs: the hardware wave limit, ~5x the resident waves; doubles go to the overflow tiers).
 static void launch_light(hipStream_t s, const Args& a, int heavy, const StepIo& io) {
-    // (reached only with a dispatch order, which only a Philox engine has)
-    hipLaunchKernelGGL((k_step<0, 8, 0, true, 1, BGX_DICE_PHILOX>), dim3(a.B - heavy), dim3(64), 0, s, a, io.actions,
+    // (reached only with a dispatch order, which only a Philox engine has: from the step blocks)
+    hipLaunchKernelGGL((k_step<0, 8, 0, true, 1, BGX_DICE_PHILOX, true>), dim3(a.B - heavy), dim3(64), 0, s, a, io.actions,
                        io.obs, io.reward, io.done, io.info, heavy);
 }
 
@@ -850,6 +921,7 @@ static std::vector<EngineBuf> engine_bufs(bgx_engine* e, bool stamps, bool order
         {(void**)&e->slow_tables, (size_t)kSlowWaves * ((size_t)16 << kLogSlotsSlow), false},
         {(void**)&A.stamps, stamps ? B * 16 : 0, false},
         {(void**)&e->perm, order ? B * 4 : 0, false},
+        {(void**)&e->blk, order ? B * kBlkBytes : 0, false},
         {(void**)&A.cls, order ? B : 0, true},
         {(void**)&A.pre, order ? B : 0, true},
         {(void**)&e->order_cnt, order ? (B / kCountThreads + 1) * kXcd * kClasses * 4 : 0, false},
@@ -885,7 +957,7 @@ static void step_shared_dice(const Args& A, const StepIo& io, hipStream_t s) {
 static int order_on_side(bgx_engine* e, hipStream_t s) {
     BGX_CK(hipEventRecord(e->step_ev[2], s));
     BGX_CK(hipStreamWaitEvent(e->step_side, e->step_ev[2], 0));
-    launch_order(e, e->step_side);
+    launch_count(e, e->step_side);
     BGX_CK(hipEventRecord(e->step_ev[3], e->step_side));
     e->order_pending = true;
     return BGX_OK;
@@ -899,7 +971,15 @@ static int order_on_side(bgx_engine* e, hipStream_t s) {
 // that a serializing tool (profiler) or a shared hardware queue could deadlock.
 static int step_lane_dice(bgx_engine* e, const StepIo& io, hipStream_t s) {
     Args a = e->a;
-    a.perm = e->perm_valid ? e->perm : nullptr;
+    // the order's second pass, due since the last step's or reset's count pass (which the
+    // caller's EngineCall has joined): perm and this step's blocks, from the actions of
+    // this call and the records, move lists and counters as they stand now on s
+    if (a.cls && e->gather_due) {
+        launch_gather(e, s, io.actions);
+        e->gather_due = false;
+        a.perm = e->perm;
+        a.blk = e->blk;
+    }
     const int heavy = a.perm ? heavy_grid(a.B, a.xcd != 0) : a.B;
     if (heavy < a.B && e->step_fork) {
         if (!e->step_side) {
@@ -919,7 +999,7 @@ static int step_lane_dice(bgx_engine* e, const StepIo& io, hipStream_t s) {
     } else {
         launch_heavy(s, a, heavy, io);
         if (heavy < a.B) launch_light(s, a, heavy, io);
-        if (a.cls) launch_order(e, s);
+        if (a.cls) launch_count(e, s);
     }
     return BGX_OK;
 }
@@ -1004,12 +1084,18 @@ int bgx_engine_join(bgx_engine* e, void* stream) {
 int bgx_engine_order(bgx_engine* e, int32_t* perm_host, uint8_t* cls_host, uint64_t* ctr_host, void* stream) {
     if (!e) return BGX_EINVAL;
     // no dispatch order (not Philox, or BGX_ORDER 0), or none built yet (before the first reset / step)
-    if ((perm_host || cls_host) && (!e->a.cls || !e->perm_valid)) return BGX_EINVAL;
+    if ((perm_host || cls_host) && (!e->a.cls || !e->gather_due)) return BGX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const size_t B = (size_t)e->a.B;
     {
-        EngineCall call(e, s, true);         // the last step's dispatch order, on the side stream
+        EngineCall call(e, s, true);         // the last step's count pass, on the side stream
         BGX_CK(call.err);
+        // the second pass is due (the next step runs it with its actions): the same kernel
+        // in its perm-only form gives the order that step will use, and leaves it due
+        if (perm_host) {
+            launch_gather(e, s, nullptr);
+            BGX_CK_LAUNCH();
+        }
         if (perm_host) BGX_CK(hipMemcpyAsync(perm_host, e->perm, B * 4, hipMemcpyDeviceToHost, s));
         if (cls_host) BGX_CK(hipMemcpyAsync(cls_host, e->a.cls, B, hipMemcpyDeviceToHost, s));
         if (ctr_host) BGX_CK(hipMemcpyAsync(ctr_host, e->a.ctr, B * 8, hipMemcpyDeviceToHost, s));
@@ -1127,9 +1213,7 @@ int bgx_reset(bgx_engine* e, const uint8_t* lane_mask_dev, float* obs_dev, void*
         LAUNCH_LOG(k_reset, dim3(A.B), s, A, lane_mask_dev, obs_dev, 0);
     }
     BGX_CK_LAUNCH();
-    if (A.cls) {
-        launch_order(e, s);
-    }
+    if (A.cls) launch_count(e, s);
     return slow_path(e, s, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
 }
 

@@ -73,7 +73,7 @@ for k in kernels[:4]:
 # both k_step launches, the dispatch-order sort, and the overflow tiers.  Durations are
 # averaged over the C3 (B = 65,536) dispatches only: the default bench also runs C2 at
 # B = 4,096 with the same kernels, told apart by grid size.
-STEP_KERNELS = ("k_step<0", "k_order_count", "k_order_scatter", "k_movegen_over<0")
+STEP_KERNELS = ("k_step<0", "k_order_count", "k_step_gather", "k_movegen_over<0")
 env = {"kernels": [], "hbm_bytes_per_step": 0.0, "busy_ns_per_step": 0.0}
 for k in kernels:
     sh = short(k["name"])
