@@ -1142,7 +1142,9 @@ int bgx_two_ply_timings(bgx_engine* e, float* ms2);
  * BGX_2PLY_POOL n (leaf-pool slots: retry rounds), BGX_2PLY_UNFACTORED (the 13-k-block
  * evaluator), BGX_2PLY_BARROW 0 (bar rows per job), BGX_2PLY_DUMP path (pool, row sides,
  * V per slot), BGX_2PLY_DEBUG (round sizes on stderr), BGX_POLICY_SKIP 0 (no tile skip),
- * BGX_POLICY_HEAVY n (the policy's heavy-row bound); read at engine creation: BGX_XCD 0,
+ * BGX_POLICY_HEAVY n (the policy's heavy-row bound), BGX_POLICY_ROWBEST 0 | 1 | 2 (the
+ * policy's noise guard: on the lane's best key / on the row's, gathered rows of main waves
+ * drawing nothing / that per quarter tile, the default); read at engine creation: BGX_XCD 0,
  * BGX_ORDER 0 (lane-order dispatch), BGX_STAMPS, BGX_STEP_DEBUG, BGX_TIER1_CAP n and
  * BGX_MOVEGEN_CAP n (the unique-afterstate caps of the step's first overflow tier and of
  * bgx_movegen's main table, clamped to [1, the table's own cap]).  Every alternative is

@@ -192,10 +192,13 @@ __host__ __device__ inline void views(P base, int T, int OT, P& hdr, P& w1q, P& 
 // steps/s; 32 is worse: the 64-row windows of the extra workgroups overflow).
 constexpr int kZWin = 256, kZCap = 64;
 constexpr int kHeavyDefault = 64;
+constexpr int kRowBestDefault = 2;                   // BGX_POLICY_ROWBEST: the noise guard's form (tile loop)
 
 #ifdef BGX_POLICY_STAMPS
 // experiment: per-wave s_memrealtime stamps of the rollout policy kernel (tools/policy_stamps.py)
-// [wave][6]: start, after the count-0 scan + staging, after GEMM1, end, flags (extra | main), tiles
+// [wave][6]: start, after the count-0 scan + staging, after GEMM1, end, flags (extra | main),
+// tile counts: bits 0-7 tiles walked, 8-15 tiles whose noise block some lane entered, 16 the
+// value tile among them, 17 a tile at or past o_s other than the value tile among them
 constexpr int kStampWaves = 8192;
 __device__ unsigned long long g_pstamp[kStampWaves][6];
 #define PSTAMP(k) do { if (MODE == 0 && sw < kStampWaves && lane_id() == 0) g_pstamp[sw][k] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -218,7 +221,9 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
     PSTAMP(0);
     const uint32_t step = step_arg + (step_ctr ? *step_ctr : 0u);
     constexpr int kW = MODE == 0 ? 4 : 1;              // waves per workgroup
-    const bool greedy = MODE < 0 ? greedy_arg != 0 : false;
+    // greedy_arg: bit 0 greedy (MODE -1), bits 1-2 the noise guard's form (the tile loop)
+    const bool greedy = MODE < 0 ? (greedy_arg & 1) != 0 : false;
+    const int rowbest = (greedy_arg >> 1) & 3;
     float* const logits_out = MODE < 0 ? logits_arg : nullptr;
     const bool skip_on = MODE == 0 && skip_arg != 0;
     __shared__ uint8_t srec_[kW][32 * 64];
@@ -408,6 +413,9 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
     // (branch-free: outputs that are not actions of this lane enter as -inf)
     float m = -INFINITY, s = 0.0f, best = -INFINITY, bestz = 0.0f, value = 0.0f;
     int besta = 0;
+#ifdef BGX_POLICY_STAMPS
+    unsigned long long ptiles = 0;
+#endif
     const uint32_t rowkey = mix32(mix32(seed_lo ^ mix32(seed_hi + 0x9E3779B9u)) ^ step) ^ (uint32_t)grow * 0x85EBCA6Bu;
     constexpr int NF = T * 2 * 2;                      // weight fragments per output tile
     uint4 w[NF];
@@ -477,22 +485,67 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
             s = s * fast_exp(m - mn) + acc;
             m = mn;
         }
-        // A key is z + g with g <= kGumbelMax, so when tm + kGumbelMax < best no
-        // output of this tile can replace the lane's current best: the noise is
-        // skipped (exact — the same keys are never larger).  Past the legal
-        // actions' tile(s) this holds for every lane of a row with legal moves
-        // (masked outputs sit 103 below).
-        if (greedy ? tm > best : !(tm + kGumbelMax < best)) {
-            #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int a = 32 * o + hid(r, h);
-                const float key = greedy ? z[r] : z[r] + gumbel(mix32(rowkey ^ ((uint32_t)a * 0xC2B2AE35u)));
-                const bool up_ = key > best;
-                best = up_ ? key : best;
-                besta = up_ ? a : besta;
-                bestz = up_ ? z[r] : bestz;
+        // The noise guard.  A key is z + g with g <= kGumbelMax, so keys whose largest z
+        // has zmax + kGumbelMax < b_row, the best key so far of the lane's ROW (both halves:
+        // lanes j and j + 32), cannot win the row, and their noise is not drawn.  Exact:
+        //  - a skipped key is below b_row and the row's final best is at least b_row, so it
+        //    neither wins nor ties;
+        //  - the lane's own best / besta / bestz may differ from those of a lane-level guard
+        //    (which might have taken such a key), but only in the half that loses the final
+        //    take2 combine: a later key that either form accepts in that half is still below
+        //    the other half's best unless it is a genuine winner, and both accept a genuine
+        //    winner;
+        //  - in an extra workgroup the same holds per wave, before the LDS merge: a key
+        //    below the wave's own row best cannot win the merged row.
+        // The lane's best alone does not do: in a row with 1-4 legal moves every output of
+        // half 1 is masked from tile 0 on, that half's best is a masked key 103 below, and
+        // one such row makes the whole wave draw 16 keys per lane on every masked tile and
+        // on the value tile.  A gathered row (an extra workgroup's: no store below) draws
+        // nothing on a main wave: the count-0 rows riding along have masked keys only, and
+        // with them 79 % of the main waves still entered the block on the value tile
+        // (per-wave counts, tools/policy_stamps.py; profiles/policy_noise).
+        // The guard is taken per quarter tile: registers 4g .. 4g + 3 hold, over the two
+        // halves, the eight consecutive outputs 32o + 8g .. 32o + 8g + 7, and group g is
+        // tested with its own max against the row's best at the tile's start or the lane's
+        // best now, whichever is larger (both are lower bounds of the row's final best: the
+        // argument above on fewer keys).  In a tile legal only in its first outputs for every
+        // row of the wave the later groups skip wave-wide.
+        // rowbest (BGX_POLICY_ROWBEST; tests and A/B runs): 0 = the lane's best and the
+        // tile's max, 1 = the row's best and the tile's max, 2 = all of the above.  With the
+        // tile's max (and in greedy mode) the later groups' tests only drop keys that would
+        // fail key > best: the state of one test per tile.
+        const float b_row = rowbest ? fmaxf(best, __shfl_xor(best, 32)) : best;
+#ifdef BGX_POLICY_STAMPS
+        bool drawn = false;
+#endif
+        #pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const float gm = !greedy && rowbest == 2
+                ? fmaxf(fmaxf(z[4 * g], z[4 * g + 1]), fmaxf(z[4 * g + 2], z[4 * g + 3])) : tm;
+            const bool draw = greedy ? gm > best : !(gm + kGumbelMax < fmaxf(b_row, best)) && !(rowbest && gathered);
+#ifdef BGX_POLICY_STAMPS
+            drawn = drawn || draw;
+#endif
+            if (draw) {
+                #pragma unroll
+                for (int r = 4 * g; r < 4 * g + 4; ++r) {
+                    const int a = 32 * o + hid(r, h);
+                    const float key = greedy ? z[r] : z[r] + gumbel(mix32(rowkey ^ ((uint32_t)a * 0xC2B2AE35u)));
+                    const bool up_ = key > best;
+                    best = up_ ? key : best;
+                    besta = up_ ? a : besta;
+                    bestz = up_ ? z[r] : bestz;
+                }
             }
         }
+#ifdef BGX_POLICY_STAMPS
+        if (MODE == 0) {
+            const unsigned long long any = __ballot(drawn) != 0ull;
+            ptiles += 1ull + (any << 8);
+            ptiles |= any && o == vt ? 1ull << 16 : 0ull;
+            ptiles |= any && o >= o_s && o != vt ? 1ull << 17 : 0ull;
+        }
+#endif
         int next = o + 1;
         if (at_s) {
             const float m_row = fmaxf(m, __shfl_xor(m, 32)), b_row = fmaxf(best, __shfl_xor(best, 32));
@@ -538,7 +591,10 @@ __global__ __launch_bounds__(MODE == 0 ? 256 : 64) __attribute__((amdgpu_waves_p
     }
     PSTAMP(3);
 #ifdef BGX_POLICY_STAMPS
-    if (MODE == 0 && sw < kStampWaves && lane_id() == 0) g_pstamp[sw][4] = extra ? 1 : 2;
+    if (MODE == 0 && sw < kStampWaves && lane_id() == 0) {
+        g_pstamp[sw][4] = extra ? 1 : 2;
+        g_pstamp[sw][5] = ptiles;
+    }
 #endif
     // combine the two lane halves of each row (lanes j and j+32)
     const float m2 = __shfl_xor(m, 32), s2 = __shfl_xor(s, 32);
@@ -923,16 +979,19 @@ int bgx_policy_act_ctr(const uint8_t* records_dev, int32_t n, const float* packe
     // rows with more legal actions than this go to the extra workgroups too (their tiles split
     // four ways), so no main wave walks more than ceil(heavy / 32) action tiles (round 5)
     const int heavy = (int)bgx_dbg_int("BGX_POLICY_HEAVY", kHeavyDefault);
+    // the noise guard of the tile loop (0 lane-level, 1 row-level, 2 row-level per quarter tile):
+    // bits 1-2 of the kernel's greedy argument
+    const int garg = (greedy ? 1 : 0) | ((int)min(max(bgx_dbg_int("BGX_POLICY_ROWBEST", kRowBestDefault), 0ll), 2ll) << 1);
     const dim3 grid0(skip ? n_wg + 2 * ((n + kZWin - 1) / kZWin) : n_wg);
 #define BGX_ACT(TT)                                                                                           \
     do {                                                                                                      \
         if (plain)                                                                                            \
             hipLaunchKernelGGL((k_policy_act<TT, 0>), grid0, dim3(256), 0, s, records_dev, n, packed, n_actions, OT, \
-                               lo, hi, step, step_ctr, greedy, act_out, logp_out, value_out, logits_out,     \
+                               lo, hi, step, step_ctr, garg, act_out, logp_out, value_out, logits_out,     \
                                records_out, skip ? (heavy > 0 ? heavy : 1) : 0);                             \
         else                                                                                                  \
             hipLaunchKernelGGL((k_policy_act<TT, -1>), grid, blk, 0, s, records_dev, n, packed, n_actions, OT,   \
-                               lo, hi, step, step_ctr, greedy, act_out, logp_out, value_out, logits_out,     \
+                               lo, hi, step, step_ctr, garg, act_out, logp_out, value_out, logits_out,     \
                                records_out, 0);                                                               \
     } while (0)
     switch (T) {
