@@ -912,6 +912,76 @@ int bgx_rollout_cube_bearoff_cut(const bgx_bearoff_cube* cdb, const uint8_t* rec
                                  int64_t* cube_cut_tally_dev, int64_t* active_dev, uint8_t* reset_mask_out, int32_t cap,
                                  const uint8_t* cube0_dev, uint8_t* cube_dev, void* stream);
 
+/* ---- truncated cubeful rollouts and the static cube evaluator (csrc/bg_cube_trunc.h;
+ * bgx/cube.py, bgx/rollout.py; no counterpart in the reference) ----
+ * The value of a position with a cube on it from one cubeless value v of the side on roll, by
+ * Janowski's interpolation between the dead-cube and the live-cube equity.  Everything is in
+ * units of the current cube and from the view of the side on roll.  bgx_cube_life: cube_life x in
+ * [0, 1], win_value W and loss_value L, the mean points of a won / lost game, in [1, 3].  In
+ * fp32, every operation rounded once, no fma (a numpy float32 restatement gives the same bits):
+ *   c = scale * v;  c = 0 for a NaN, else clamped to [-L, W]      the dead-cube equity
+ *   p = (c + L) / (W + L)                                         the inferred win probability
+ *   D = W + L + 0.5f;  TP = (L - 0.5f) / D;  CP = (L + 1.0f) / D  live-cube take and cash points
+ *   seg(p; p0, y0, p1, y1) = y0 + (p - p0) * ((y1 - y0) / (p1 - p0))
+ *   live_cen(p) = p < TP ? seg(p; 0,-L, TP,-1) : p < CP ? seg(p; TP,-1, CP,1) : seg(p; CP,1, 1,W)
+ *   live_own(p) = p < CP ? seg(p; 0,-L, CP,1) : seg(p; CP,1, 1,W)
+ *   live_opp(p) = p < TP ? seg(p; 0,-L, TP,-1) : seg(p; TP,-1, 1,W)
+ *   E_s(p) = (1 - x) * c + x * live_s(p)                          s = cen, own, opp
+ * With jacoby != 0, E_cen is formed with W = L = 1 (c' = 2 p - 1, TP = 0.2, CP = 0.8; p as
+ * above).  The cube byte is read as the cube kernels read it (k as min(k, cap), owner 3 as 0);
+ * with m the record's mover (byte 52): k >= cap is the dead state (E = c), owner 0 cen, owner
+ * m + 1 own, otherwise opp.  The four values and the flags are bgx_bearoff_cube_lookup's:
+ *   [0] nd = E_s(p);  [1] DT = 2 E_opp(p), or 2 c when k + 1 >= cap (never the Jacoby form);
+ *   [2] e = max(nd, min(DT, 1)) where the mover may double (cen or own, k < cap), else nd;
+ *   [3] c;  flags bit 0: the mover may double, bit 1: it doubles (min(DT, 1) > nd; a tie is no
+ *   double), bit 2: the opponent takes (DT <= 1), bit 3: the cube is dead.
+ * bgx_cube_janowski: one thread per 64-byte record.  cube_dev uint8[n] (NULL: centred at 1 on
+ * every lane), value float[n], sel uint8[n] (NULL: every lane).  A selected record that is not
+ * game_over (byte 55) writes values_out float[n][4] (16-byte aligned, may be NULL) and its flags
+ * to flags_out uint8[n] (may be NULL); every other lane gets flags 0 and its values are not
+ * written.
+ * bgx_rollout_cube_trunc_cut: bgx_rollout_trunc_cut for cubeful rollouts, after
+ * bgx_rollout_advance and bgx_rollout_trunc_sel (tsel) and the value of the tsel lanes; the caller
+ * runs the masked bgx_reset after it.  cube_trunc_tally int64[n_groups][6]
+ * (bgx_rollout_cube_trunc_field) is zeroed by the caller.  A lane with tsel[i] != 0 and a valid
+ * group, k and the state read from cube[i]:
+ *   q = e when the record's mover is the start record's mover, else -e (e and not nd: the mover
+ *       has not yet taken this ply's cube decision);
+ *   Qq = llrintf(q * 65536.0f) clamped to +-196608;  Yq = Qq * 2^k  (|Yq| <= 3 * 2^26);
+ *   row group[i]: GAMES += 1, PLIES += plies[i], Y += Yq, Y2_LO += Yq^2 & (2^30 - 1),
+ *   Y2_HI += Yq^2 >> 30, LOG2 += k;
+ *   games_done[i] += 1, plies[i] = 0; the lane's last game: sel[i] = 0 and active drops;
+ *   cube[i] = cube0[i]; reset_mask_out[i] = 1.
+ * Every other lane gets reset_mask_out[i] = 0 and is otherwise untouched.  The unit is
+ * bgx_rollout_trunc_cut's 2^-16 points, so a dead-cube run equals a plain truncated run integer
+ * for integer.  The sums are integers: run-to-run identical.  Plain kernels, one thread per lane,
+ * no allocation and no synchronisation: graph-capturable.  BGX_EINVAL for what
+ * bgx_rollout_trunc_cut and the cube kernels reject (n <= 0, n_groups <= 0, games_per_lane < 0, a
+ * NaN scale, cap outside 0..10, a NULL pointer other than those named), a misaligned values_out,
+ * and a cube_life, win_value or loss_value that is NaN or outside its range. */
+typedef struct {
+    float cube_life;           /* x in [0, 1]: 0 = dead cube, 1 = live cube */
+    float win_value;           /* W in [1, 3]: mean points of a won game */
+    float loss_value;          /* L in [1, 3]: mean points of a lost game */
+} bgx_cube_life;
+enum bgx_rollout_cube_trunc_field {
+    BGX_ROLLOUT_CUBE_TRUNC_GAMES = 0,   /* truncated games */
+    BGX_ROLLOUT_CUBE_TRUNC_PLIES = 1,   /* their steps */
+    BGX_ROLLOUT_CUBE_TRUNC_Y = 2,       /* sum of Yq (2^-16 points, from the start mover's side) */
+    BGX_ROLLOUT_CUBE_TRUNC_Y2_LO = 3,   /* sum of Yq^2 & (2^30 - 1) */
+    BGX_ROLLOUT_CUBE_TRUNC_Y2_HI = 4,   /* sum of Yq^2 >> 30: sum Yq^2 = Y2_HI 2^30 + Y2_LO (2^-32) */
+    BGX_ROLLOUT_CUBE_TRUNC_LOG2 = 5     /* sum of k at the truncation */
+};
+int bgx_cube_janowski(const uint8_t* records_dev, const uint8_t* cube_dev_or_null, const float* value_dev, int32_t n,
+                      float scale, bgx_cube_life life, int32_t cap, int32_t jacoby, const uint8_t* sel_or_null,
+                      float* values_out, uint8_t* flags_out, void* stream);
+int bgx_rollout_cube_trunc_cut(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev,
+                               const uint8_t* tsel_dev, const float* value_dev, float scale, bgx_cube_life life,
+                               int32_t n, int32_t n_groups, int32_t games_per_lane, int32_t* games_done_dev,
+                               int32_t* plies_dev, uint8_t* sel_dev, int64_t* cube_trunc_tally_dev, int64_t* active_dev,
+                               uint8_t* reset_mask_out, int32_t cap, int32_t jacoby, const uint8_t* cube0_dev,
+                               uint8_t* cube_dev, void* stream);
+
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row
  * stride ld_logits; mask from the legal count in bytes 60-61 of each 64-byte

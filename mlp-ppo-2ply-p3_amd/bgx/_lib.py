@@ -27,6 +27,11 @@ class BgxCubeRule(ctypes.Structure):
                 ("too_good_at", ctypes.c_float), ("cap", _I32), ("jacoby", _I32)]
 
 
+class BgxCubeLife(ctypes.Structure):
+    """include/bgx.h bgx_cube_life, passed by value."""
+    _fields_ = [("cube_life", ctypes.c_float), ("win_value", ctypes.c_float), ("loss_value", ctypes.c_float)]
+
+
 SIGNATURES = {
     "bgx_engine_create": (ctypes.c_int, [ctypes.c_int, _I32, _I32, ctypes.c_uint64, _I32, _I32, _I32,
                                          ctypes.POINTER(_P)]),
@@ -110,6 +115,9 @@ SIGNATURES = {
     "bgx_bearoff_cube_lookup": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "bgx_rollout_cube_bearoff_cut": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _I32, _P,
                                                     _P, _P]),
+    "bgx_cube_janowski": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.c_float, BgxCubeLife, _I32, _I32, _P, _P, _P, _P]),
+    "bgx_rollout_cube_trunc_cut": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_float, BgxCubeLife, _I32, _I32, _I32, _P,
+                                                  _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),

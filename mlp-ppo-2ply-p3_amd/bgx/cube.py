@@ -5,19 +5,28 @@ on roll may double before it rolls when the cube is centred or its own, the oppo
 (k + 1, the cube is now the taker's) or passes (the game ends at 2^k).  Both decisions follow one
 threshold rule, CubeRule, on the mover's equity before the roll.  Where a game enters the cubeful
 exact bearoff table (bearoff.CubefulBearoffDB) it can be cut and scored with its
-exact cubeful expectation instead (cube_bearoff=; summarize_cube_bearoff).
+exact cubeful expectation instead (cube_bearoff=; summarize_cube_bearoff).  A cubeful game can
+also stop at a horizon and count Janowski's cube-life equity of the position reached, formed from
+a net's cubeless value (cube_truncate= a CubeTruncation; CubeLife; summarize_cube_truncated;
+DESIGN.md §17; csrc/bg_cube_trunc.h); static_cube_decision is the same rule per lane with no
+rollout, janowski_points its decision points.
 
     python -m bgx.rollout --net ckpt.pt --player 1ply --positions opening --trials 1296 --cube
     python -m bgx.rollout --net ckpt.pt --player 1ply --positions pos.json --cube --cube-decision
+    python -m bgx.rollout --net ckpt.pt --player 2ply --top-k 4 --positions pos.json --cube --cube-decision \\
+        --cube-truncate 8 --cube-life 0.68
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import check
+from .truncate import Truncation
 
 # cube_tally int64[n_groups][8] (include/bgx.h bgx_rollout_cube_field)
 CUBE_FIELDS = ("cube_games", "cube_points", "cube_points2", "cube_log2", "pass_games", "pass_plies", "pass_won",
@@ -29,6 +38,11 @@ CENTRED = 0                         # the owner field: 0 centred, 1 PLAYER1, 2 P
 CUBE_CUT_FIELDS = ("cut_games", "cut_plies", "cut_y", "cut_y2_lo", "cut_y2_hi", "cut_log2")
 CUBE_CUT_ONE = 1 << 20              # Yq = rint(q * CUBE_CUT_ONE) * 2^k
 CUBE_CUT_SPLIT = 30                 # sum Yq^2 = cut_y2_hi * 2^30 + cut_y2_lo
+# cube_trunc_tally int64[n_groups][6] (include/bgx.h bgx_rollout_cube_trunc_field): the cubeful
+# games truncated at the horizon, fixed point, 2^-16 points (truncate.TRUNC_ONE)
+CUBE_TRUNC_FIELDS = ("cube_trunc_games", "cube_trunc_plies", "cube_trunc_y", "cube_trunc_y2_lo", "cube_trunc_y2_hi",
+                     "cube_trunc_log2")
+CUBE_TRUNC_ONE = 1 << 16            # Yq = rint(q * CUBE_TRUNC_ONE) * 2^k, |q| <= 3
 
 
 def pack(k: int, owner: int) -> int:
@@ -245,7 +259,7 @@ def decide_reference(cube, mover, equity, rule: CubeRule):
 
 
 def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rule: CubeRule, cube0=None,
-                   cut_lookup=None) -> dict:
+                   cut_lookup=None, cube_truncate=None) -> dict:
     """A traced cube run replayed on the host with the kernels' arithmetic (include/bgx.h
     bgx_rollout_cube_*).  `trace`: run_lanes' with cube_mover, cube_equity, done and info
     [steps, B]; the lane records are taken as not game_over, which holds between the steps of an
@@ -254,7 +268,7 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
     active int).  `cut_lookup` (cube_bearoff_cut_reference's `lookup`): the run was cut at the
     cubeful bearoff table (run_lanes' cube_bearoff=) -- the cut is replayed after begin on the
     trace's cut_records0 and after every step on cut_records[t]; the result gains cut_tally
-    int64[P, 6], cut0 bool[B] and cut bool[steps, B]."""
+    int64[P, 6], cut0 bool[B] and cut bool[steps, B].  `cube_truncate`: cube_trunc_reference."""
     from .rollout import FIELDS, R_CUR
     mover = np.asarray(torch.as_tensor(trace["cube_mover"]).cpu()).astype(np.int64)
     equity = np.asarray(torch.as_tensor(trace["cube_equity"]).cpu()).astype(np.float32)
@@ -281,6 +295,11 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
         return out["mask"]
 
     cut0 = cut(trace["cut_records0"]) if cut_lookup is not None else None
+    if cube_truncate is not None:
+        tval = np.asarray(torch.as_tensor(trace["ctrunc_value"]).cpu()).astype(np.float32)
+        tmover = np.asarray(torch.as_tensor(trace["ctrunc_mover"]).cpu())
+        tt, tcuts = np.zeros((P, len(CUBE_TRUNC_FIELDS)), np.int64), np.zeros((T, B), bool)
+        tstates = np.zeros((T, B), np.uint8)
 
     def add(rows, lanes, values):
         for f, v in values.items():
@@ -322,15 +341,32 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
         plies = np.where(fin, 0, plies)
         if cut_lookup is not None:
             cuts[t] = cut(trace["cut_records"][t])
+        if cube_truncate is not None:
+            # the truncation, after advance and the table cut (whose lanes have plies 0)
+            tc = valid & (games < G) & (plies >= cube_truncate.plies)
+            tstates[t] = cube
+            k, _ = unpack(cube)
+            values, _ = janowski_reference(np.where(tc, tval[t], np.float32(0)), cube, tmover[t], cube_truncate.scale,
+                                           cube_truncate.life, cap, rule.jacoby)
+            yq = cube_trunc_fixed_reference(values[:, 2], tmover[t] == starts[:, R_CUR], k)
+            y2 = yq * yq
+            add(tt, tc, {0: 1, 1: plies, 2: yq, 3: y2 & ((1 << CUBE_CUT_SPLIT) - 1), 4: y2 >> CUBE_CUT_SPLIT, 5: k})
+            tcuts[t] = tc
+            games += tc
+            plies = np.where(tc, 0, plies)
+            cube = np.where(tc, c0, cube).astype(np.uint8)
     out = dict(cube_tally=ct, tally=tally, cube=states, dsel=dsels, mask=masks, games_done=games,
                active=int((valid & (games < G)).sum()))
     if cut_lookup is not None:
         out.update(cut_tally=cut_tally, cut0=cut0, cut=cuts)
+    if cube_truncate is not None:
+        out.update(cube_trunc_tally=tt, ctrunc=tcuts, ctrunc_cube=tstates)
     return out
 
 
 def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, cube=(0, CENTRED),
-                          first_roll: str = "stratified", max_steps: int = 4000, cube_bearoff=None) -> dict:
+                          first_roll: str = "stratified", max_steps: int = 4000, cube_bearoff=None,
+                          cube_truncate=None) -> dict:
     """"Double or not, take or pass?" for the side on roll in `record` (uint8[64]: board and
     mover), holding the cube `cube` = (k, owner) with access to it.  The position is rolled out
     twice in one run, as two groups over the same start records: "no double", with the cube as
@@ -341,7 +377,8 @@ def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, 
     iff min(double_take, 1) > no_double, `take` iff double_take <= 1.  `cube_bearoff` (a
     bearoff.CubefulBearoffDB): both rollouts are cut at the cubeful table
     (Rollout.run); for a position in the table that is the exact answer, the table's nd and DT at
-    the cut's 2^-20 resolution, with standard errors of 0."""
+    the cut's 2^-20 resolution, with standard errors of 0.  `cube_truncate` (a CubeTruncation;
+    DESIGN.md §17): both rollouts are truncated at its horizon and scored by Janowski's rule."""
     rec = torch.as_tensor(record).reshape(-1)
     if rec.numel() != 64 or rec.dtype != torch.uint8:
         raise ValueError("rollout_cube_decision: record must be 64 bytes (uint8)")
@@ -352,10 +389,268 @@ def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, 
                          f"the cap {rule.cap}")
     pos = torch.stack([rec.cpu(), rec.cpu()])
     res = rollout.run(player, pos, trials, first_roll=first_roll, max_steps=max_steps, cube=rule,
-                      cube_start=[(k, owner), (k + 1, 2 - mover)], cube_bearoff=cube_bearoff)
+                      cube_start=[(k, owner), (k + 1, 2 - mover)], cube_bearoff=cube_bearoff,
+                      cube_truncate=cube_truncate)
     unit = float(1 << k)
     nd, dt = res[0]["equity_cubeful"] / unit, res[1]["equity_cubeful"] / unit
     return dict(no_double=nd, no_double_stderr=res[0]["equity_cubeful_stderr"] / unit,
                 double_take=dt, double_take_stderr=res[1]["equity_cubeful_stderr"] / unit,
                 double_pass=1.0, double_pass_stderr=0.0, double=bool(min(dt, 1.0) > nd), take=bool(dt <= 1.0),
                 cube=[k, owner], rollouts=res)
+
+
+# ------------------------------------------------- truncated cubeful rollouts --
+class CubeLife:
+    """The parameters of Janowski's interpolation (csrc/bg_cube_trunc.h; include/bgx.h
+    bgx_cube_life): `x`, the cube life in [0, 1] (0: the cube is dead, the equity is the cubeless
+    one; 1: fully live), and `win_value` / `loss_value`, the mean points W / L of a won / lost
+    game in [1, 3] (gammon_values gives them from a cubeless rollout).  0.68 is a conventional
+    contact value: a parameter, not a claim about the best one."""
+
+    def __init__(self, x: float = 0.68, win_value: float = 1.0, loss_value: float = 1.0):
+        for name, v, lo, hi in (("x", x, 0.0, 1.0), ("win_value", win_value, 1.0, 3.0),
+                                ("loss_value", loss_value, 1.0, 3.0)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not lo <= float(v) <= hi:
+                raise ValueError(f"CubeLife: {name} must be a number in [{lo:g}, {hi:g}], got {v!r}")
+        self.x, self.win_value, self.loss_value = float(x), float(win_value), float(loss_value)
+
+    def struct(self) -> _lib.BgxCubeLife:
+        return _lib.BgxCubeLife(self.x, self.win_value, self.loss_value)
+
+
+class CubeTruncation(Truncation):
+    """truncate.Truncation for cubeful rollouts (run_lanes' cube_truncate=, with cube=): a game
+    that has run `plies` plies stops there and is scored with Janowski's cube-life equity of the
+    position reached, from `value` -- Truncation's value, scale and lookahead, and the same
+    equity() -- and `life` (a CubeLife).  The cap and the Jacoby rule are the CubeRule's."""
+
+    def __init__(self, value, plies: int, scale: float = 1.0, lookahead: int = 0, life: CubeLife = None):
+        super().__init__(value, plies, scale=scale, lookahead=lookahead)
+        life = CubeLife() if life is None else life
+        if not isinstance(life, CubeLife):
+            raise ValueError("CubeTruncation: life must be a cube.CubeLife")
+        self.life = life
+
+
+def gammon_values(summary) -> tuple:
+    """(W, L), the mean points of a won and of a lost game, from a cubeless rollout's summary
+    (rollout.summarize's win1..3 and loss1..3); 1.0 for a side without a game."""
+    def mean(prefix):
+        n = [int(summary[f"{prefix}{j}"]) for j in (1, 2, 3)]
+        return (n[0] + 2 * n[1] + 3 * n[2]) / sum(n) if sum(n) > 0 else 1.0
+    return mean("win"), mean("loss")
+
+
+def _seg(p, p0, y0, p1, y1):
+    return y0 + (p - p0) * ((y1 - y0) / (p1 - p0))
+
+
+def _live(p, W, L, f):
+    """live_cen, live_own, live_opp of include/bgx.h at p, every operation rounded to f once."""
+    half, one, zero = f(0.5), f(1), f(0)
+    D = f(f(W + L) + half)
+    TP, CP = f(f(L - half) / D), f(f(L + one) / D)
+    lo, hi = _seg(p, zero, -L, TP, -one), _seg(p, CP, one, one, W)
+    cen = np.where(p < TP, lo, np.where(p < CP, _seg(p, TP, -one, CP, one), hi))
+    own = np.where(p < CP, _seg(p, zero, -L, CP, one), hi)
+    opp = np.where(p < TP, lo, _seg(p, TP, -one, one, W))
+    return cen, own, opp
+
+
+def janowski_equities(p, life: CubeLife, jacoby: bool = False, dtype=np.float64):
+    """(c, E_cen, E_own, E_opp) of include/bgx.h at the win probabilities p, with c = p (W + L) - L,
+    in `dtype` (fp64: the rule itself, for its properties and janowski_points)."""
+    f = dtype
+    p = np.asarray(p, f)
+    x, W, L, one = f(life.x), f(life.win_value), f(life.loss_value), f(1)
+    c = p * f(W + L) - L
+    live = _live(p, W, L, f)
+    e = [(one - x) * c + x * s for s in live]
+    if jacoby:
+        e[0] = (one - x) * (f(2) * p - one) + x * _live(p, one, one, f)[0]
+    return c, e[0], e[1], e[2]
+
+
+def janowski_reference(value, cube, mover, scale: float, life: CubeLife, cap: int, jacoby: bool = False):
+    """cube_trunc_values of csrc/bg_cube_trunc.h (bgx_cube_janowski without the lane selection)
+    on arrays in numpy float32, bit for bit: (values f32[n, 4] = nd, DT, e, c; flags uint8[n])
+    for the cubeless values `value`, the cube bytes `cube` (None: centred at 1) and the movers
+    `mover` (record byte 52)."""
+    f = np.float32
+    v = np.asarray(value, f).reshape(-1)
+    n = v.shape[0]
+    cb = sanitise(np.zeros(n, np.uint8) if cube is None else np.asarray(cube).reshape(-1), cap)
+    k, o = unpack(cb)
+    m = np.asarray(mover).reshape(-1).astype(np.int64) & 1
+    x, W, L, one = f(life.x), f(life.win_value), f(life.loss_value), f(1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = (f(scale) * v).astype(f)
+    c = np.where(np.isnan(c), f(0), np.minimum(np.maximum(c, -L), W)).astype(f)
+    p = ((c + L).astype(f) / f(W + L)).astype(f)
+    dead = k >= int(cap)
+    access = ~dead & ((o == 0) | (o == m + 1))
+    live = _live(p, W, L, f)
+    omx = f(one - x)
+
+    def mix(d, s):
+        return ((omx * d).astype(f) + (x * s).astype(f)).astype(f)
+    e_cen, e_own, e_opp = (mix(c, s.astype(f)) for s in live)
+    if jacoby:
+        e_cen = mix(((f(2) * p).astype(f) - one).astype(f), _live(p, one, one, f)[0].astype(f))
+    nd = np.where(dead, c, np.where(o == 0, e_cen, np.where(access, e_own, e_opp))).astype(f)
+    dt = (f(2) * np.where(k + 1 >= int(cap), c, e_opp)).astype(f)
+    cash = np.where(dt < one, dt, one).astype(f)
+    doubles = access & (cash > nd)
+    values = np.stack([nd, dt, np.where(doubles, cash, nd).astype(f), c], axis=1).astype(f)
+    flags = (access * 1 + doubles * 2 + (dt <= one) * 4 + dead * 8).astype(np.uint8)
+    return values, flags
+
+
+def cube_trunc_fixed_reference(e, start_mover_on_roll, k):
+    """cube_trunc_q of csrc/bg_cube_trunc.h on arrays: Yq = clamp(rint(fp32(+-e 2^16)), +-3 * 2^16) 2^k,
+    0 for a NaN (round half even)."""
+    f = np.float32
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = (np.where(start_mover_on_roll, np.asarray(e, f), -np.asarray(e, f)).astype(f) * f(CUBE_TRUNC_ONE)).astype(f)
+    y = np.where(np.isnan(y), f(0), np.clip(y, -3.0 * CUBE_TRUNC_ONE, 3.0 * CUBE_TRUNC_ONE))
+    return np.rint(y).astype(np.int64) * (np.int64(1) << np.asarray(k).astype(np.int64))
+
+
+def _root(g, lo=0.0, hi=1.0):
+    for _ in range(200):
+        mid = 0.5 * (lo + hi)
+        lo, hi = (mid, hi) if g(mid) < 0.0 else (lo, mid)
+    return 0.5 * (lo + hi)
+
+
+def janowski_points(life: CubeLife) -> dict:
+    """The rule's decision points as cubeless equities c = p (W + L) - L of the side on roll, in
+    fp64 (no Jacoby rule), from which a CubeRule's thresholds follow for the same cube life:
+    `take`, above which the opponent passes (2 E_opp > 1: CubeRule's pass_at); `double_centred`
+    and `redouble`, from which doubling beats holding a centred / an own cube (2 E_opp = E_cen /
+    E_own: double_at); and, for W > 1, `too_good`, above which playing on with a centred cube
+    beats cashing (E_cen > 1: too_good_at).  Each is the root of a continuous piecewise linear
+    function on [0, 1], by bisection; `p_take` etc. hold the win probabilities themselves."""
+    W, L = life.win_value, life.loss_value
+
+    def eq(p):
+        return [float(v) for v in janowski_equities(np.float64(p), life)]
+    roots = dict(take=_root(lambda p: 2.0 * eq(p)[3] - 1.0),
+                 double_centred=_root(lambda p: 2.0 * eq(p)[3] - eq(p)[1]),
+                 redouble=_root(lambda p: 2.0 * eq(p)[3] - eq(p)[2]))
+    if W > 1.0:
+        roots["too_good"] = _root(lambda p: eq(p)[1] - 1.0)
+    out = {name: p * (W + L) - L for name, p in roots.items()}
+    out.update({f"p_{name}": p for name, p in roots.items()})
+    return out
+
+
+def cube_trunc_reference(trace, starts, group, n_groups: int, games_per_lane: int, rule: CubeRule, truncation,
+                         cube0=None, cut_lookup=None) -> dict:
+    """A traced truncated cubeful run (run_lanes' cube= with cube_truncate=) replayed on the host:
+    cube_reference extended by the truncation, the way its cut_lookup= extends it by the table
+    cut.  After every step's advance (and table cut) a selected lane whose game has run
+    truncation.plies plies adds Yq = cube_trunc_fixed_reference(e of janowski_reference on the
+    trace's ctrunc_value and ctrunc_mover and the replay's own cube state; signed for the start
+    mover; k) to its row, counts the game and gets its starting cube back.  The result gains
+    cube_trunc_tally int64[P, 6], ctrunc bool[steps, B] and ctrunc_cube uint8[steps, B] (the
+    states the truncation saw)."""
+    return cube_reference(trace, starts, group, n_groups, games_per_lane, rule, cube0=cube0, cut_lookup=cut_lookup,
+                          cube_truncate=truncation)
+
+
+def summarize_cube_truncated(tally_row, cube_row, trunc_row, unfinished: int = 0, cut_row=None) -> dict:
+    """summarize_cube(tally_row, cube_row, unfinished) for a truncated cubeful run,
+    with the row's 6 truncation sums (CUBE_TRUNC_FIELDS) and, when the run was also cut at the
+    cubeful bearoff table, its 6 cut sums `cut_row` (CUBE_CUT_FIELDS).  A truncated game's result
+    is y = Yq / 2^16 points, Janowski's estimate times the cube.  `games` = played out + passed +
+    truncated (+ cut); `equity_cubeful` and `equity_cubeful_stderr` over all kinds together from
+    Python integers, in units of 2^-16 (2^-20 with cut_row: the truncation's sums are rescaled
+    by 2^4 and 2^8), so equal results give their value exactly and a standard error of 0.
+    `pass_share`, `doubles_per_game`, `mean_cube_log2` and `plies_per_game` are over all games;
+    adds `truncated_games`, `truncated_share`, `truncated_equity_cubeful` (the truncated games'
+    mean result in points), with cut_row `cut_share`, and the sums under their names.  The
+    standard error is the sample's spread: it contains neither the net's error nor the rule's.
+    Raises ValueError when CUBE_GAMES != GAMES + PASS_GAMES."""
+    r = summarize_cube(tally_row, cube_row, unfinished)
+    c = [int(v) for v in trunc_row]
+    if len(c) != len(CUBE_TRUNC_FIELDS):
+        raise ValueError(f"summarize_cube_truncated: a truncation row has {len(CUBE_TRUNC_FIELDS)} entries, got {len(c)}")
+    tr = dict(zip(CUBE_TRUNC_FIELDS, c))
+    ty, ty2 = tr["cube_trunc_y"], (tr["cube_trunc_y2_hi"] << CUBE_CUT_SPLIT) + tr["cube_trunc_y2_lo"]
+    cut = None
+    if cut_row is not None:
+        cc = [int(v) for v in cut_row]
+        if len(cc) != len(CUBE_CUT_FIELDS):
+            raise ValueError(f"summarize_cube_truncated: a cut row has {len(CUBE_CUT_FIELDS)} entries, got {len(cc)}")
+        cut = dict(zip(CUBE_CUT_FIELDS, cc))
+    one = CUBE_TRUNC_ONE if cut is None else CUBE_CUT_ONE
+    up = one // CUBE_TRUNC_ONE
+    n_t = tr["cube_trunc_games"]
+    n = r["cube_games"] + n_t + (cut["cut_games"] if cut else 0)
+    s1 = r["cube_points"] * one + ty * up + (cut["cut_y"] if cut else 0)
+    s2 = (r["cube_points2"] * one * one + ty2 * up * up +
+          ((cut["cut_y2_hi"] << CUBE_CUT_SPLIT) + cut["cut_y2_lo"] if cut else 0))
+
+    def per_game(v):
+        return v / n if n > 0 else 0.0
+
+    var_num = max(n * s2 - s1 * s1, 0)                   # n^2 (n - 1) one^2 x the variance of the mean
+    r.update(tr)
+    if cut:
+        r.update(cut, cut_share=per_game(cut["cut_games"]))
+    r.update(games=n, truncated_games=n_t, truncated_share=per_game(n_t),
+             truncated_equity_cubeful=ty / (n_t * CUBE_TRUNC_ONE) if n_t > 0 else 0.0,
+             equity_cubeful=s1 / (n * one) if n > 0 else 0.0,
+             equity_cubeful_stderr=math.sqrt(var_num / (n * n * (n - 1))) / one if n > 1 else 0.0,
+             pass_share=per_game(r["pass_games"]), doubles_per_game=per_game(r["doubles"]),
+             mean_cube_log2=per_game(r["cube_log2"] + tr["cube_trunc_log2"] + (cut["cut_log2"] if cut else 0)),
+             plies_per_game=per_game(r["played_out"]["plies"] + r["pass_plies"] + tr["cube_trunc_plies"] +
+                                     (cut["cut_plies"] if cut else 0)))
+    return r
+
+
+def static_cube_decision(eng_or_records, head, cube=None, scale: float = 1.0, life: CubeLife = None, cap: int = 6,
+                         jacoby: bool = False, sel=None, value=None, out=None):
+    """"Double or not, take or pass?" with no rollout (bgx_cube_janowski): (values f32[n, 4],
+    flags uint8[n]) for an Engine's lane records or a contiguous uint8[n, 64] tensor on the GPU,
+    shaped like bearoff.CubefulBearoffDB.lookup's -- values = (nd, DT, e, cubeless c) of the
+    record's mover holding the cube byte cube[i] (uint8[n], pack(k, owner); None: centred at 1),
+    flags bit 0: the mover may double, 1: it doubles, 2: the opponent takes, 3: the cube is dead.
+    The cubeless value is `head`'s static value of the records (search.value_lanes), or `value`
+    (float32[n] on the records' device) when given.  `sel` (uint8[n]): only those records; a
+    record off sel or game_over gets flags 0 and keeps what `out` = (values, flags) held (NaN
+    without `out`).  Sync-free."""
+    from .arena import _stream
+    from .engine import Engine, _ptr
+    from .search import value_lanes
+    life = CubeLife() if life is None else life
+    if not isinstance(life, CubeLife):
+        raise ValueError("static_cube_decision: life must be a cube.CubeLife")
+    if int(cap) != cap or not 0 <= int(cap) <= MAX_CAP:
+        raise ValueError(f"static_cube_decision: cap must be in 0..{MAX_CAP}, got {cap!r}")
+    if math.isnan(float(scale)):
+        raise ValueError("static_cube_decision: scale is NaN")
+    r = eng_or_records
+    if isinstance(r, Engine):
+        n, dev, rp = r.batch, r.device, ctypes.c_void_p(r.lanes_ptr())
+    else:
+        if (not isinstance(r, torch.Tensor) or r.dtype != torch.uint8 or r.dim() != 2 or r.shape[1] != 64
+                or not r.is_contiguous() or not r.is_cuda):
+            raise ValueError("static_cube_decision: records must be an Engine or a contiguous uint8[n, 64] tensor on "
+                             "the GPU")
+        n, dev, rp = r.shape[0], r.device, _ptr(r)
+    for name, t, dt in (("cube", cube, torch.uint8), ("sel", sel, torch.uint8), ("value", value, torch.float32)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.shape != (n,) or t.dtype != dt or t.device != dev
+                              or not t.is_contiguous()):
+            raise ValueError(f"static_cube_decision: {name} must be a contiguous {dt}[{n}] tensor on {dev}")
+    if value is None:
+        value = value_lanes(r, head, sel=sel)
+    if out is None:
+        out = (torch.full((n, 4), float("nan"), dtype=torch.float32, device=dev),
+               torch.empty(n, dtype=torch.uint8, device=dev))
+    values, flags = out
+    check(_lib.load().bgx_cube_janowski(rp, _ptr(cube), _ptr(value), n, float(scale), life.struct(), int(cap),
+                                        int(bool(jacoby)), _ptr(sel), _ptr(values), _ptr(flags), _stream(dev)),
+          "bgx_cube_janowski")
+    return values, flags

@@ -21,9 +21,11 @@ on roll may double by a threshold rule on a net's value, a passed double ends th
 result is the cubeful equity (cube.summarize_cube); --cube-decision answers "double or not,
 take or pass?" per position; --cube-bearoff K cuts the cubeful games at the cubeful exact bearoff
 table (bearoff.CubefulBearoffDB), where both the endgame's dice and its cube
-action are replaced by the exact cubeful expectation.  --truncate N: a game that has run N plies stops there and is scored by
-a net's value head (bgx/truncate.py; DESIGN.md §14), which makes the slow players affordable;
-with --luck the dice noise of the plies played goes too (summarize_truncated_luck).  The
+action are replaced by the exact cubeful expectation; --cube-truncate N stops the cubeful games
+after N plies and scores them with Janowski's cube-life equity from a net's value,
+which is what makes --cube-decision affordable with the slow players.  --truncate N: a game that
+has run N plies stops there and is scored by a net's value head (bgx/truncate.py),
+which makes the slow players affordable; with --luck the dice noise of the plies played goes too (summarize_truncated_luck).  The
 estimate then carries the net's own error, which no standard error shows.
 """
 from __future__ import annotations
@@ -312,11 +314,22 @@ def _records(positions) -> torch.Tensor:
 
 
 def _check_modes(where: str, luck=None, bearoff=None, cube=None, truncate=None, cube_bearoff=None, cube0=None,
-                 types: bool = False) -> None:
+                 types: bool = False, cube_truncate=None) -> None:
     """The combinations of modes that Rollout.run and run_lanes refuse, as ValueError(f"{where}: ...")
     for the first one that applies.  `types` (run_lanes): also what only the lanes can tell --
-    a cube_bearoff that is no cubeful table, a truncate that is no Truncation, cube0 without cube --
-    each at its place in the order.  Nothing here touches the engine or the library."""
+    a cube_bearoff that is no cubeful table, a truncate that is no Truncation, a cube_truncate that
+    is no CubeTruncation, cube0 without cube -- each at its place in the order.  Nothing here
+    touches the engine or the library."""
+    if cube_truncate is not None:
+        if cube is None:
+            raise ValueError(f"{where}: cube_truncate without cube")
+        for name, other in (("luck", luck), ("bearoff", bearoff), ("truncate", truncate)):
+            if other is not None:
+                raise ValueError(f"{where}: cube_truncate together with {name} is not supported")
+        if types:
+            from .cube import CubeTruncation
+            if not isinstance(cube_truncate, CubeTruncation):
+                raise ValueError(f"{where}: cube_truncate must be a cube.CubeTruncation")
     if cube_bearoff is not None:
         if cube is None:
             raise ValueError(f"{where}: cube_bearoff without cube")
@@ -554,6 +567,45 @@ class _TruncStage(_Stage):
         c.reset(self.mask)
 
 
+class _CubeTruncStage(_Stage):
+    """`cube_truncate` (a cube.CubeTruncation), with `cube`: a cubeful game that has
+    run cube_truncate.plies plies without ending stops there and is scored with Janowski's
+    cube-life equity of the side on roll, times the lane's cube.  After advance, as the last
+    stage (after the table cut, whose lanes have plies 0 and so are not truncated in the same
+    step): trunc_sel, value, cube_trunc_cut (which also takes the cube stage's cap, Jacoby rule,
+    cube0 and state), reset(mask).  Sync-free when the truncation is.  Result (after cube_tally
+    and cube_cut_tally, if any): cube_trunc_tally int64[n_groups, 6] (cube.CUBE_TRUNC_FIELDS); the
+    trace gains per step ctrunc uint8 (the lanes truncated), ctrunc_value (NaN off them),
+    ctrunc_mover (the side on roll there) and ctrunc_cube (the cube states before the cut)."""
+
+    def __init__(self, c: _Pass, truncation, cube: _CubeStage):
+        from .cube import CUBE_TRUNC_FIELDS
+        self.c, self.t, self.cube, self.sync_free = c, truncation, cube, truncation.sync_free
+        self.life = truncation.life.struct()
+        self.tally = c.tally(CUBE_TRUNC_FIELDS)
+        self.tsel, self.mask = c.lane_buffers(2, torch.uint8)
+        self.buf, self.scratch = c.lane_buffers(2, torch.float32, float("nan"))
+        c.traced(("ctrunc", torch.uint8), ("ctrunc_value", torch.float32), ("ctrunc_mover", torch.uint8),
+                 ("ctrunc_cube", torch.uint8))
+
+    def after_advance(self, step):
+        c, tr, rule = self.c, self.c.tr, self.cube.rule
+        check(c.L.bgx_rollout_trunc_sel(c.recs, _ptr(c.grp), c.B, c.P, self.t.plies, c.lanes[1], c.lanes[2],
+                                        _ptr(self.tsel), None, c.stream), "bgx_rollout_trunc_sel")
+        tv = self.t.equity(c.eng, self.tsel, self.scratch, self.buf)
+        if tr is not None:
+            c.eng.records(out=c.rec)
+            tr["ctrunc"][step] = self.tsel
+            tr["ctrunc_value"][step] = torch.where(self.tsel != 0, tv, float("nan"))
+            tr["ctrunc_mover"][step] = c.rec[:, R_CUR]
+            tr["ctrunc_cube"][step] = self.cube.state
+        check(c.L.bgx_rollout_cube_trunc_cut(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(self.tsel), _ptr(tv),
+                                             self.t.scale, self.life, c.B, c.P, c.G, *c.lanes, _ptr(self.tally),
+                                             c.active, _ptr(self.mask), rule.cap, int(rule.jacoby), _ptr(self.cube.c0),
+                                             _ptr(self.cube.state), c.stream), "bgx_rollout_cube_trunc_cut")
+        c.reset(self.mask)
+
+
 class Rollout:
     """`batch` lanes of an engine of its own (auto_reset, so a finished game's lane starts
     its next one, from its start record, in the same step)."""
@@ -578,7 +630,7 @@ class Rollout:
 
     def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
                   trace: bool = False, luck=None, bearoff=None, cube=None, cube0=None, truncate=None,
-                  cube_bearoff=None):
+                  cube_bearoff=None, cube_truncate=None):
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
@@ -592,12 +644,13 @@ class Rollout:
 
         Every mode is a stage (the classes above; their docstrings say what each does per step,
         returns and traces).  The loop calls them in a fixed order -- luck, cube, table cut,
-        truncation -- after begin, before act, after the step (before advance) and after advance:
+        truncation, cubeful truncation -- after begin, before act, after the step (before advance)
+        and after advance:
 
             begin; cube_begin; cut, reset(mask)
             [ roll_luck, luck_add;  cube_sel, equity, cube_decide, reset(mask);
               act, merge, step;  luck_flush;  cube_flush;  advance;
-              cut, reset(mask);  trunc_sel, value, trunc_cut, reset(mask) ]
+              cut, reset(mask);  trunc_sel, value, trunc_cut or cube_trunc_cut, reset(mask) ]
 
         `luck` (a search.ValueHead): the luck of every roll, summed per game -> luck_tally.
         `bearoff` (a bearoff.BearoffDB or OneSidedBearoffDB): games stop at the table -> cut_tally.
@@ -605,14 +658,19 @@ class Rollout:
         `truncate` (a truncate.Truncation): games stop at a horizon, scored by a value -> trunc_tally.
         `cube_bearoff` (a bearoff.CubefulBearoffDB), with `cube`: cubeful games stop at the cubeful
         table -> cube_tally, cube_cut_tally.
+        `cube_truncate` (a cube.CubeTruncation), with `cube`: cubeful games stop at a horizon, scored
+        by Janowski's cube-life equity -> cube_tally, [cube_cut_tally,] cube_trunc_tally.
         Each None: nothing changes; all None: exactly the three results above.
 
         Together: `truncate` with `luck` IS supported (..., luck_tally, trunc_tally;
-        summarize_truncated_luck) and `cube_bearoff` needs `cube`.  Every other pair raises
+        summarize_truncated_luck), `cube_bearoff` and `cube_truncate` need `cube` and go together
+        (exact where the table reaches, Janowski elsewhere).  Every other pair raises
         ValueError (_check_modes): `bearoff` with `luck` needs cross sums that are not kept, the
         luck of a cubeful game and cubeful values of the cubeless table do not exist (`cube` with
-        `luck` or `bearoff`), nor do three-way summaries (`truncate` or `cube_bearoff` with others)."""
-        _check_modes("run_lanes", luck, bearoff, cube, truncate, cube_bearoff, cube0, types=True)
+        `luck` or `bearoff`), nor do other three-way summaries (`truncate`, `cube_bearoff` or
+        `cube_truncate` with others)."""
+        _check_modes("run_lanes", luck, bearoff, cube, truncate, cube_bearoff, cube0, types=True,
+                     cube_truncate=cube_truncate)
         max_steps, G, P = int(max_steps), int(games_per_lane), int(n_groups)
         if max_steps < 0 or G < 0 or P <= 0:
             raise ValueError(f"run_lanes: max_steps {max_steps}, games_per_lane {G} must be >= 0, n_groups {P} > 0")
@@ -638,7 +696,8 @@ class Rollout:
         cube_stage = _CubeStage(c, cube, cube0) if cube is not None else None
         cut_stage = _TableCutStage(c, table, cube_stage) if table is not None else None
         trunc_stage = _TruncStage(c, truncate, luck is not None) if truncate is not None else None
-        stages = [s for s in (luck_stage, cube_stage, cut_stage, trunc_stage) if s is not None]
+        ctrunc_stage = _CubeTruncStage(c, cube_truncate, cube_stage) if cube_truncate is not None else None
+        stages = [s for s in (luck_stage, cube_stage, cut_stage, trunc_stage, ctrunc_stage) if s is not None]
         for s in stages:
             s.after_begin()
         every = SYNC_EVERY if getattr(player, "sync_free", False) and all(s.sync_free for s in stages) else 1
@@ -681,7 +740,7 @@ class Rollout:
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
             trace: bool = False, luck=None, luck_scale="fit", bearoff=None, cube=None, cube_start=(0, 0),
-            truncate=None, cube_bearoff=None):
+            truncate=None, cube_bearoff=None, cube_truncate=None):
         """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
         bytes come from the layout) `trials` times with `player` (any arena player object)
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
@@ -699,8 +758,10 @@ class Rollout:
         `truncate` (a truncate.Truncation): the results are summarize_truncated's,
         with `luck` those of summarize_truncated_luck.  `cube_bearoff` (a bearoff.CubefulBearoffDB;
         DESIGN.md §15), with `cube`: the results are cube.summarize_cube_bearoff's and carry
-        `bearoff_kind` = "cubeful"."""
-        _check_modes("run", luck, bearoff, cube, truncate, cube_bearoff)
+        `bearoff_kind` = "cubeful".  `cube_truncate` (a cube.CubeTruncation), with
+        `cube`: the results are cube.summarize_cube_truncated's (with `cube_bearoff` too, its
+        cut_row= form)."""
+        _check_modes("run", luck, bearoff, cube, truncate, cube_bearoff, cube_truncate=cube_truncate)
         pos = _records(positions)
         P = pos.shape[0]
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
@@ -718,14 +779,14 @@ class Rollout:
             tally, unf, tr, *extra = self.run_lanes(
                 player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck, bearoff=bearoff, cube=cube,
                 cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None, truncate=truncate,
-                cube_bearoff=cube_bearoff)
+                cube_bearoff=cube_bearoff, cube_truncate=cube_truncate)
             sums = [tally, unf] + extra                            # the modes' tallies in run_lanes' order
             totals = sums if totals is None else [a + b for a, b in zip(totals, sums)]
             if trace:
                 tr.update(group=grp, starts=starts, games_per_lane=G)
         self.eng.set_starts(None)
         rows, unf, *extra = (t.cpu().tolist() for t in totals)
-        summary = _summary(luck, bearoff, cube, truncate, cube_bearoff)
+        summary = _summary(luck, bearoff, cube, truncate, cube_bearoff, cube_truncate)
         scale = () if luck is None else (luck_scale,)
         res = [summary(rows[p], *(e[p] for e in extra), *scale, unf[p]) for p in range(P)]
         table = bearoff if bearoff is not None else cube_bearoff
@@ -735,11 +796,15 @@ class Rollout:
         return (res, tr) if trace else res
 
 
-def _summary(luck, bearoff, cube, truncate, cube_bearoff):
+def _summary(luck, bearoff, cube, truncate, cube_bearoff, cube_truncate=None):
     """The summary of a position's rows by the modes of the run (after _check_modes): a function
     (tally_row, *the modes' rows in run_lanes' order, [luck_scale with luck,] unfinished)."""
     if cube is not None:
-        from .cube import summarize_cube, summarize_cube_bearoff
+        from .cube import summarize_cube, summarize_cube_bearoff, summarize_cube_truncated
+        if cube_truncate is not None and cube_bearoff is not None:
+            return lambda t, c, cut, tr, unf=0: summarize_cube_truncated(t, c, tr, unf, cut_row=cut)
+        if cube_truncate is not None:
+            return summarize_cube_truncated
         return summarize_cube_bearoff if cube_bearoff is not None else summarize_cube
     if truncate is not None:
         return summarize_truncated_luck if luck is not None else summarize_truncated
@@ -882,7 +947,8 @@ def _luck_scale(text: str):
 class _Parser(argparse.ArgumentParser):
     """--top-k is an error for any player but a 2ply one with weights; --luck and --cube need
     weights; --cube goes with neither --luck nor a bearoff cut; --truncate needs a net and goes
-    with neither a bearoff cut nor --cube."""
+    with neither a bearoff cut nor --cube; --cube-truncate and its options need --cube and go with
+    none of --luck, --bearoff, --bearoff1 and --truncate."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -936,6 +1002,24 @@ class _Parser(argparse.ArgumentParser):
                     self.error(f"--truncate and --{name} cannot be combined")
             if math.isnan(ns.truncate_scale):
                 self.error("--truncate-scale must be a number")
+        if ns.cube_truncate is None:
+            if (ns.cube_truncate_net is not None or ns.cube_truncate_lookahead != 0 or ns.cube_truncate_scale != 1.0
+                    or ns.cube_life != 0.68 or ns.cube_win_value != 1.0 or ns.cube_loss_value != 1.0):
+                self.error("--cube-life, --cube-win-value, --cube-loss-value, --cube-truncate-net, "
+                           "--cube-truncate-scale and --cube-truncate-lookahead need --cube-truncate")
+        else:
+            if not ns.cube:
+                self.error("--cube-truncate needs --cube")
+            if ns.cube_truncate < 1:
+                self.error("--cube-truncate takes a number of plies >= 1")
+            for name in ("luck", "bearoff", "bearoff1", "truncate"):
+                if getattr(ns, name) not in (None, False):
+                    self.error(f"--cube-truncate and --{name} cannot be combined")
+            if math.isnan(ns.cube_truncate_scale):
+                self.error("--cube-truncate-scale must be a number")
+            for name, lo, hi in (("cube_life", 0.0, 1.0), ("cube_win_value", 1.0, 3.0), ("cube_loss_value", 1.0, 3.0)):
+                if not lo <= getattr(ns, name) <= hi:
+                    self.error(f"--{name.replace('_', '-')} takes a number in [{lo:g}, {hi:g}]")
         if ns.trials < 1 or ns.batch < 1:
             self.error("--trials and --batch must be >= 1")
         return ns
@@ -997,6 +1081,24 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --cube: stop a game at the cubeful exact bearoff table for K checkers a side (1..8) "
                          "and score it with its exact cubeful expectation; not with --luck, --bearoff, --bearoff1 "
                          "or --truncate")
+    ap.add_argument("--cube-truncate", type=int, default=None, metavar="N",
+                    help="with --cube: stop a game after N plies (>= 1) and score it with Janowski's cube-life "
+                         "equity from a net's value head; goes with --cube-bearoff; not with --luck, --bearoff, "
+                         "--bearoff1 or --truncate")
+    ap.add_argument("--cube-life", type=float, default=0.68, metavar="X",
+                    help="the cube life in [0, 1]: 0 scores the cubeless equity, 1 the fully live cube's")
+    ap.add_argument("--cube-win-value", type=float, default=1.0, metavar="W",
+                    help="mean points of a won game in [1, 3] (from a cubeless rollout's gammon rates)")
+    ap.add_argument("--cube-loss-value", type=float, default=1.0, metavar="L",
+                    help="mean points of a lost game in [1, 3]")
+    ap.add_argument("--cube-truncate-scale", type=float, default=1.0, metavar="S",
+                    help="points per unit of the net's value")
+    ap.add_argument("--cube-truncate-lookahead", type=int, default=0, choices=(0, 1),
+                    help="0: the value head on the position itself (sync-free); 1: its mean best 1-ply value "
+                         "over the 21 rolls")
+    ap.add_argument("--cube-truncate-net", default=None, metavar="PATH",
+                    help="the state_dict whose value head scores the truncated games (default: --cube-net if "
+                         "given, else the player's net)")
     ap.add_argument("--cube-decision", action="store_true",
                     help="per position: no double / double, take / double, pass for the side on roll with a "
                          "centred cube, and the verdict")
@@ -1053,18 +1155,28 @@ def main(argv=None):
                            args.truncate, scale=args.truncate_scale, lookahead=args.truncate_lookahead)
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
+    ctrunc = None
+    if args.cube_truncate is not None:
+        from .cube import CubeLife, CubeTruncation
+        from .search import ValueHead
+        cnet = args.cube_truncate_net if args.cube_truncate_net is not None else args.cube_net
+        ctrunc = CubeTruncation(ValueHead(net if cnet is None else load_net(cnet, dev)), args.cube_truncate,
+                                scale=args.cube_truncate_scale, lookahead=args.cube_truncate_lookahead,
+                                life=CubeLife(args.cube_life, args.cube_win_value, args.cube_loss_value))
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
     if args.cube_decision:
         # one line per position: the three equities and the verdict; the summary counts both rollouts' games
         res = []
         for i in range(positions.shape[0]):
             d = rollout_cube_decision(ro, player, positions[i], args.trials, rule, first_roll=args.first_roll,
-                                      max_steps=args.max_steps, cube_bearoff=cdb)
+                                      max_steps=args.max_steps, cube_bearoff=cdb, cube_truncate=ctrunc)
             print(json.dumps(dict(position=i, cube_decision=True, **d)), flush=True)
             res.extend(d["rollouts"])
     else:
         res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
                      luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff) or dbs1.get(args.bearoff1), cube=rule,
-                     truncate=trunc, cube_bearoff=cdb)
+                     truncate=trunc, cube_bearoff=cdb, cube_truncate=ctrunc)
     dt = time.perf_counter() - t0
     for i, r in enumerate(res if not args.cube_decision else ()):
         print(json.dumps(dict(position=i, **r)), flush=True)
@@ -1101,6 +1213,12 @@ def main(argv=None):
                        truncate_lookahead=args.truncate_lookahead, truncate_net=args.truncate_net,
                        truncated_games=tg, truncated_share=tg / games if games else 0.0,
                        plies_per_game=sum(r["plies_per_game"] * r["games"] for r in res) / games if games else 0.0)
+    if ctrunc is not None:
+        tg = sum(r["truncated_games"] for r in res)
+        summary.update(cube_truncate=args.cube_truncate, cube_life=args.cube_life, cube_win_value=args.cube_win_value,
+                       cube_loss_value=args.cube_loss_value, cube_truncate_scale=args.cube_truncate_scale,
+                       cube_truncate_lookahead=args.cube_truncate_lookahead, cube_truncate_net=args.cube_truncate_net,
+                       truncated_games=tg, truncated_share=tg / games if games else 0.0)
     print(json.dumps(summary), flush=True)
     return res, summary
 
