@@ -26,23 +26,13 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .replay import R_CUR, LaneReplay, split_sq
+from .tally import (CUBE_CUT_FIELDS, CUBE_CUT_ONE, CUBE_CUT_SPLIT, CUBE_FIELDS, CUBE_TRUNC_FIELDS,  # noqa: F401
+                    CUBE_TRUNC_ONE, summarize_cube, summarize_cube_bearoff, summarize_cube_truncated)
 from .truncate import Truncation
 
-# cube_tally int64[n_groups][8] (include/bgx.h bgx_rollout_cube_field)
-CUBE_FIELDS = ("cube_games", "cube_points", "cube_points2", "cube_log2", "pass_games", "pass_plies", "pass_won",
-               "doubles")
 MAX_CAP = 10
 CENTRED = 0                         # the owner field: 0 centred, 1 PLAYER1, 2 PLAYER2
-# cube_cut_tally int64[n_groups][6] (include/bgx.h bgx_rollout_cube_cut_field): the games cut at
-# the cubeful bearoff table, fixed point, 2^-20 points
-CUBE_CUT_FIELDS = ("cut_games", "cut_plies", "cut_y", "cut_y2_lo", "cut_y2_hi", "cut_log2")
-CUBE_CUT_ONE = 1 << 20              # Yq = rint(q * CUBE_CUT_ONE) * 2^k
-CUBE_CUT_SPLIT = 30                 # sum Yq^2 = cut_y2_hi * 2^30 + cut_y2_lo
-# cube_trunc_tally int64[n_groups][6] (include/bgx.h bgx_rollout_cube_trunc_field): the cubeful
-# games truncated at the horizon, fixed point, 2^-16 points (truncate.TRUNC_ONE)
-CUBE_TRUNC_FIELDS = ("cube_trunc_games", "cube_trunc_plies", "cube_trunc_y", "cube_trunc_y2_lo", "cube_trunc_y2_hi",
-                     "cube_trunc_log2")
-CUBE_TRUNC_ONE = 1 << 16            # Yq = rint(q * CUBE_TRUNC_ONE) * 2^k, |q| <= 3
 
 
 def pack(k: int, owner: int) -> int:
@@ -138,74 +128,6 @@ class CubeRule:
         return e
 
 
-def summarize_cube(tally_row, cube_row, unfinished: int = 0) -> dict:
-    """One position's cubeful result from its 8 tally entries (the games played to the end) and its
-    8 cube sums (CUBE_FIELDS), in fp64 from the integers: `games` (played out + passed),
-    `equity_cubeful` = CUBE_POINTS / games in points from the start mover's side,
-    `equity_cubeful_stderr` = sqrt((CUBE_POINTS2 - games equity^2) / (games - 1) / games),
-    `pass_share` = PASS_GAMES / games, `doubles_per_game`, `mean_cube_log2` (the mean k at the
-    game's end), `plies_per_game` over PLIES + PASS_PLIES, the 8 sums under their names, and
-    `played_out` = summarize(tally_row): the cubeless result of the subset of games that
-    reached the end -- no estimate of the position's cubeless equity, as the passed games are
-    missing from it.  No games: the rates are 0; one game: the standard error is 0.  Raises
-    ValueError when CUBE_GAMES != GAMES + PASS_GAMES."""
-    from .rollout import summarize
-    played = summarize(tally_row, unfinished)
-    c = [int(v) for v in cube_row]
-    if len(c) != len(CUBE_FIELDS):
-        raise ValueError(f"summarize_cube: a cube row has {len(CUBE_FIELDS)} entries, got {len(c)}")
-    r = dict(zip(CUBE_FIELDS, c))
-    n = r["cube_games"]
-    if n != played["games"] + r["pass_games"]:
-        raise ValueError(f"summarize_cube: the cube row counts {n} games, the tally row {played['games']} and "
-                         f"{r['pass_games']} passed")
-    def per_game(v):
-        return v / n if n > 0 else 0.0
-
-    var_num = max(n * r["cube_points2"] - r["cube_points"] ** 2, 0)        # n^2 (n - 1) x the variance of the mean
-    r.update(games=n, equity_cubeful=per_game(r["cube_points"]),
-             equity_cubeful_stderr=math.sqrt(var_num / (n * n * (n - 1))) if n > 1 else 0.0,
-             pass_share=per_game(r["pass_games"]), doubles_per_game=per_game(r["doubles"]),
-             mean_cube_log2=per_game(r["cube_log2"]), plies_per_game=per_game(played["plies"] + r["pass_plies"]),
-             unfinished=int(unfinished), played_out=played)
-    return r
-
-
-def summarize_cube_bearoff(tally_row, cube_row, cut_row, unfinished: int = 0) -> dict:
-    """summarize_cube(tally_row, cube_row, unfinished) for a run cut at the cubeful bearoff table
-    (DESIGN.md §15), with the row's 6 cut sums (CUBE_CUT_FIELDS).  A cut game's result is its
-    exact cubeful expectation y = Yq / 2^20 points.  `games` = played out + passed + cut,
-    `equity_cubeful` and `equity_cubeful_stderr` over all three kinds together, from Python
-    integers: sum y = CUBE_POINTS 2^20 + CUT_Y in units of 2^-20, sum y^2 = CUBE_POINTS2 2^40 +
-    CUT_Y2_HI 2^30 + CUT_Y2_LO in units of 2^-40, so equal results give their value exactly and a
-    standard error of 0.  `pass_share`, `doubles_per_game`, `mean_cube_log2` (CUBE_LOG2 +
-    CUT_LOG2) and `plies_per_game` (PLIES + PASS_PLIES + CUT_PLIES) are over all games; adds
-    `cut_share` = CUT_GAMES / games and the 6 sums under their names.  The cut replaces the
-    endgame's dice noise and its cube action by the expectation, so the standard error is that of
-    the mixed sample.  Raises ValueError when CUBE_GAMES != GAMES + PASS_GAMES (the cut games are
-    counted beside them)."""
-    r = summarize_cube(tally_row, cube_row, unfinished)
-    c = [int(v) for v in cut_row]
-    if len(c) != len(CUBE_CUT_FIELDS):
-        raise ValueError(f"summarize_cube_bearoff: a cut row has {len(CUBE_CUT_FIELDS)} entries, got {len(c)}")
-    cut = dict(zip(CUBE_CUT_FIELDS, c))
-    n = r["cube_games"] + cut["cut_games"]
-    s1 = r["cube_points"] * CUBE_CUT_ONE + cut["cut_y"]
-    s2 = r["cube_points2"] * CUBE_CUT_ONE ** 2 + (cut["cut_y2_hi"] << CUBE_CUT_SPLIT) + cut["cut_y2_lo"]
-
-    def per_game(v):
-        return v / n if n > 0 else 0.0
-
-    var_num = max(n * s2 - s1 * s1, 0)                   # n^2 (n - 1) 2^40 x the variance of the mean
-    r.update(cut, games=n, cut_share=per_game(cut["cut_games"]),
-             equity_cubeful=s1 / (n * CUBE_CUT_ONE) if n > 0 else 0.0,
-             equity_cubeful_stderr=math.sqrt(var_num / (n * n * (n - 1))) / CUBE_CUT_ONE if n > 1 else 0.0,
-             pass_share=per_game(r["pass_games"]), doubles_per_game=per_game(r["doubles"]),
-             mean_cube_log2=per_game(r["cube_log2"] + cut["cut_log2"]),
-             plies_per_game=per_game(r["played_out"]["plies"] + r["pass_plies"] + cut["cut_plies"]))
-    return r
-
-
 def cube_bearoff_cut_reference(records, cube, plies, games_done, sel, starts, group, n_groups: int,
                                games_per_lane: int, cap: int, cube0, lookup) -> dict:
     """One call of bgx_rollout_cube_bearoff_cut on the host (include/bgx.h), state in, state out.
@@ -215,29 +137,29 @@ def cube_bearoff_cut_reference(records, cube, plies, games_done, sel, starts, gr
     the start mover; k of its cube) to its row, counts the game and gets its starting cube back.
     Returns dict(cut_tally int64[P, 6], mask bool[B], games_done, plies, sel uint8[B], cube
     uint8[B], retired int = the lanes that finished their last game)."""
-    from .bearoff import cube_fixed_reference
-    from .rollout import R_CUR
-    records, starts = np.asarray(records), np.asarray(starts)
-    group = np.asarray(group).astype(np.int64)
-    B, P, G = group.shape[0], int(n_groups), int(games_per_lane)
-    cube = np.asarray(cube).astype(np.uint8).copy()
-    plies, games = np.asarray(plies).astype(np.int64).copy(), np.asarray(games_done).astype(np.int64).copy()
+    rp = LaneReplay(starts, group, n_groups, games_per_lane, cap=cap, c0=sanitise(np.asarray(cube0), cap))
+    rp.tally("cut_tally", CUBE_CUT_FIELDS)
+    rp.cube = np.asarray(cube).astype(np.uint8).copy()
+    rp.plies, rp.games = np.asarray(plies).astype(np.int64).copy(), np.asarray(games_done).astype(np.int64).copy()
     sel = np.asarray(sel).astype(np.uint8).copy()
-    in_db, values, _ = lookup(records, cube, cap)
-    m = (sel != 0) & (group >= 0) & (group < P) & np.asarray(in_db, bool)
-    k = np.minimum(cube.astype(np.int64) & 15, int(cap))
-    v = np.where(plies == 0, values[:, 0], values[:, 2]).astype(np.float32)
-    yq = cube_fixed_reference(np.where(m, v, np.float32(0)), records[:, R_CUR] == starts[:, R_CUR], k)
-    y2 = yq * yq
-    tally = np.zeros((P, len(CUBE_CUT_FIELDS)), np.int64)
-    for f, x in enumerate((np.ones(B, np.int64), plies, yq, y2 & ((1 << CUBE_CUT_SPLIT) - 1), y2 >> CUBE_CUT_SPLIT, k)):
-        np.add.at(tally[:, f], group[m], x[m])
-    games[m] += 1
-    plies[m] = 0
-    retired = m & (games >= G)
+    m = _table_cut(rp, np.asarray(records), lookup, sel != 0)
+    retired = m & (rp.games >= rp.G)
     sel[retired] = 0
-    cube[m] = sanitise(np.asarray(cube0), cap)[m]
-    return dict(cut_tally=tally, mask=m, games_done=games, plies=plies, sel=sel, cube=cube, retired=int(retired.sum()))
+    return dict(cut_tally=rp.tallies["cut_tally"], mask=m, games_done=rp.games, plies=rp.plies, sel=sel, cube=rp.cube,
+                retired=int(retired.sum()))
+
+
+def _table_cut(rp: LaneReplay, records, lookup, sel):
+    """The cubeful table cut on the replay's state: the `sel` lanes with a valid group whose record
+    is in the table are scored, counted and get their starting cube back.  Returns their mask."""
+    from .bearoff import cube_fixed_reference
+    in_db, values, _ = lookup(records, rp.cube, rp.cap)
+    m = sel & rp.valid & np.asarray(in_db, bool)
+    k = rp.cube_k()
+    v = np.where(rp.plies == 0, values[:, 0], values[:, 2]).astype(np.float32)
+    yq = cube_fixed_reference(np.where(m, v, np.float32(0)), records[:, R_CUR] == rp.start_cur, k)
+    rp.cut("cut_tally", m, (yq, *split_sq(yq), k), cube=True)
+    return m
 
 
 def decide_reference(cube, mover, equity, rule: CubeRule):
@@ -269,98 +191,44 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
     cubeful bearoff table (run_lanes' cube_bearoff=) -- the cut is replayed after begin on the
     trace's cut_records0 and after every step on cut_records[t]; the result gains cut_tally
     int64[P, 6], cut0 bool[B] and cut bool[steps, B].  `cube_truncate`: cube_trunc_reference."""
-    from .rollout import FIELDS, R_CUR
-    mover = np.asarray(torch.as_tensor(trace["cube_mover"]).cpu()).astype(np.int64)
-    equity = np.asarray(torch.as_tensor(trace["cube_equity"]).cpu()).astype(np.float32)
-    done = np.asarray(torch.as_tensor(trace["done"]).cpu())
-    info = np.asarray(torch.as_tensor(trace["info"]).cpu()).astype(np.int64)
-    starts, group = np.asarray(torch.as_tensor(starts).cpu()), np.asarray(torch.as_tensor(group).cpu()).astype(np.int64)
-    B, P, G, cap = group.shape[0], int(n_groups), int(games_per_lane), rule.cap
-    c0 = np.zeros(B, np.uint8) if cube0 is None else sanitise(np.asarray(torch.as_tensor(cube0).cpu()), cap)
-    cube = c0.copy()
-    valid = (group >= 0) & (group < P)
-    start_m = starts[:, R_CUR].astype(np.int64) & 1
-    plies, games = np.zeros(B, np.int64), np.zeros(B, np.int64)
-    tally, ct = np.zeros((P, len(FIELDS)), np.int64), np.zeros((P, len(CUBE_FIELDS)), np.int64)
+    def host(x):
+        return np.asarray(torch.as_tensor(x).cpu())
+    mover, equity = host(trace["cube_mover"]), host(trace["cube_equity"]).astype(np.float32)
+    done, info = host(trace["done"]), host(trace["info"])
+    cap = rule.cap
+    B = host(group).shape[0]
+    c0 = np.zeros(B, np.uint8) if cube0 is None else sanitise(host(cube0), cap)
+    rp = LaneReplay(host(starts), host(group), n_groups, games_per_lane, cap=cap, c0=c0, jacoby=rule.jacoby)
+    rp.tally("cube_tally", CUBE_FIELDS)
     T = done.shape[0]
     states, dsels, masks = np.zeros((T, B), np.uint8), np.zeros((T, B), bool), np.zeros((T, B), bool)
-    cut_tally, cuts = np.zeros((P, len(CUBE_CUT_FIELDS)), np.int64), np.zeros((T, B), bool)
-
-    def cut(recs):
-        nonlocal cube, plies, games
-        out = cube_bearoff_cut_reference(np.asarray(torch.as_tensor(recs).cpu()), cube, plies, games, valid & (games < G),
-                                         starts, group, P, G, cap, c0, cut_lookup)
-        cube, plies, games = out["cube"], out["plies"], out["games_done"]
-        cut_tally[:] += out["cut_tally"]
-        return out["mask"]
-
-    cut0 = cut(trace["cut_records0"]) if cut_lookup is not None else None
+    if cut_lookup is not None:
+        rp.tally("cut_tally", CUBE_CUT_FIELDS)
+        cuts = np.zeros((T, B), bool)
+        cut0 = _table_cut(rp, host(trace["cut_records0"]), cut_lookup, rp.sel)
     if cube_truncate is not None:
-        tval = np.asarray(torch.as_tensor(trace["ctrunc_value"]).cpu()).astype(np.float32)
-        tmover = np.asarray(torch.as_tensor(trace["ctrunc_mover"]).cpu())
-        tt, tcuts = np.zeros((P, len(CUBE_TRUNC_FIELDS)), np.int64), np.zeros((T, B), bool)
-        tstates = np.zeros((T, B), np.uint8)
-
-    def add(rows, lanes, values):
-        for f, v in values.items():
-            np.add.at(rows[:, f], group[lanes], np.broadcast_to(v, (B,))[lanes])
-
+        rp.tally("cube_trunc_tally", CUBE_TRUNC_FIELDS)
+        tval, tmover = host(trace["ctrunc_value"]).astype(np.float32), host(trace["ctrunc_mover"])
+        tcuts, tstates = np.zeros((T, B), bool), np.zeros((T, B), np.uint8)
     for t in range(T):
-        sel = valid & (games < G)
-        states[t] = cube
-        k, _ = unpack(cube)
-        m = mover[t] & 1
-        act, nxt, access = decide_reference(cube, m, equity[t], rule)
-        dsel = sel & (plies > 0) & access
-        dsels[t] = dsel
-        act = np.where(dsel, act, 0)
-        pas, dbl = act == 2, act > 0
-        y = np.where(m == start_m, 1, -1) * (1 << k)
-        add(ct, pas, {0: 1, 1: y, 2: y * y, 3: k, 4: 1, 5: plies, 6: (y > 0).astype(np.int64)})
-        add(ct, dbl, {7: 1})
-        masks[t] = pas
-        games += pas
-        plies = np.where(pas, 0, plies)
-        cube = np.where(pas, c0, np.where(dbl, nxt, cube)).astype(np.uint8)
-        # the step, cube_flush and advance
-        sel = valid & (games < G)
-        plies = plies + sel
-        winner = ((info[t] >> 8) & 0xFF) - 1
-        score = np.clip((info[t] >> 16) & 0xFF, 1, 3)
-        dn = sel & (done[t] != 0)
-        fin = dn & (winner >= 0)
-        k, _ = unpack(cube)
-        won = winner == start_m
-        s = np.where(rule.jacoby & (k == 0), 1, score)
-        y = np.where(won, 1, -1) * (s << k)
-        add(ct, fin, {0: 1, 1: y, 2: y * y, 3: k})
-        add(tally, fin, {0: 1, 1: plies})
-        np.add.at(tally, (group[fin], (np.where(won, 2, 5) + score - 1)[fin]), 1)
-        cube = np.where(dn, c0, cube).astype(np.uint8)
-        games += fin
-        plies = np.where(fin, 0, plies)
+        states[t] = rp.cube
+        dsels[t], masks[t] = rp.decide(mover[t], *decide_reference(rp.cube, mover[t], equity[t], rule))
+        rp.advance(done[t], info[t])
         if cut_lookup is not None:
-            cuts[t] = cut(trace["cut_records"][t])
+            cuts[t] = _table_cut(rp, host(trace["cut_records"][t]), cut_lookup, rp.sel)
         if cube_truncate is not None:
             # the truncation, after advance and the table cut (whose lanes have plies 0)
-            tc = valid & (games < G) & (plies >= cube_truncate.plies)
-            tstates[t] = cube
-            k, _ = unpack(cube)
-            values, _ = janowski_reference(np.where(tc, tval[t], np.float32(0)), cube, tmover[t], cube_truncate.scale,
+            tc, k = rp.horizon(cube_truncate.plies), rp.cube_k()
+            tcuts[t], tstates[t] = tc, rp.cube
+            values, _ = janowski_reference(np.where(tc, tval[t], np.float32(0)), rp.cube, tmover[t], cube_truncate.scale,
                                            cube_truncate.life, cap, rule.jacoby)
-            yq = cube_trunc_fixed_reference(values[:, 2], tmover[t] == starts[:, R_CUR], k)
-            y2 = yq * yq
-            add(tt, tc, {0: 1, 1: plies, 2: yq, 3: y2 & ((1 << CUBE_CUT_SPLIT) - 1), 4: y2 >> CUBE_CUT_SPLIT, 5: k})
-            tcuts[t] = tc
-            games += tc
-            plies = np.where(tc, 0, plies)
-            cube = np.where(tc, c0, cube).astype(np.uint8)
-    out = dict(cube_tally=ct, tally=tally, cube=states, dsel=dsels, mask=masks, games_done=games,
-               active=int((valid & (games < G)).sum()))
+            yq = cube_trunc_fixed_reference(values[:, 2], tmover[t] == rp.start_cur, k)
+            rp.cut("cube_trunc_tally", tc, (yq, *split_sq(yq), k), cube=True)
+    out = dict(rp.tallies, cube=states, dsel=dsels, mask=masks, games_done=rp.games, active=rp.active)
     if cut_lookup is not None:
-        out.update(cut_tally=cut_tally, cut0=cut0, cut=cuts)
+        out.update(cut0=cut0, cut=cuts)
     if cube_truncate is not None:
-        out.update(cube_trunc_tally=tt, ctrunc=tcuts, ctrunc_cube=tstates)
+        out.update(ctrunc=tcuts, ctrunc_cube=tstates)
     return out
 
 
@@ -557,57 +425,6 @@ def cube_trunc_reference(trace, starts, group, n_groups: int, games_per_lane: in
     states the truncation saw)."""
     return cube_reference(trace, starts, group, n_groups, games_per_lane, rule, cube0=cube0, cut_lookup=cut_lookup,
                           cube_truncate=truncation)
-
-
-def summarize_cube_truncated(tally_row, cube_row, trunc_row, unfinished: int = 0, cut_row=None) -> dict:
-    """summarize_cube(tally_row, cube_row, unfinished) for a truncated cubeful run,
-    with the row's 6 truncation sums (CUBE_TRUNC_FIELDS) and, when the run was also cut at the
-    cubeful bearoff table, its 6 cut sums `cut_row` (CUBE_CUT_FIELDS).  A truncated game's result
-    is y = Yq / 2^16 points, Janowski's estimate times the cube.  `games` = played out + passed +
-    truncated (+ cut); `equity_cubeful` and `equity_cubeful_stderr` over all kinds together from
-    Python integers, in units of 2^-16 (2^-20 with cut_row: the truncation's sums are rescaled
-    by 2^4 and 2^8), so equal results give their value exactly and a standard error of 0.
-    `pass_share`, `doubles_per_game`, `mean_cube_log2` and `plies_per_game` are over all games;
-    adds `truncated_games`, `truncated_share`, `truncated_equity_cubeful` (the truncated games'
-    mean result in points), with cut_row `cut_share`, and the sums under their names.  The
-    standard error is the sample's spread: it contains neither the net's error nor the rule's.
-    Raises ValueError when CUBE_GAMES != GAMES + PASS_GAMES."""
-    r = summarize_cube(tally_row, cube_row, unfinished)
-    c = [int(v) for v in trunc_row]
-    if len(c) != len(CUBE_TRUNC_FIELDS):
-        raise ValueError(f"summarize_cube_truncated: a truncation row has {len(CUBE_TRUNC_FIELDS)} entries, got {len(c)}")
-    tr = dict(zip(CUBE_TRUNC_FIELDS, c))
-    ty, ty2 = tr["cube_trunc_y"], (tr["cube_trunc_y2_hi"] << CUBE_CUT_SPLIT) + tr["cube_trunc_y2_lo"]
-    cut = None
-    if cut_row is not None:
-        cc = [int(v) for v in cut_row]
-        if len(cc) != len(CUBE_CUT_FIELDS):
-            raise ValueError(f"summarize_cube_truncated: a cut row has {len(CUBE_CUT_FIELDS)} entries, got {len(cc)}")
-        cut = dict(zip(CUBE_CUT_FIELDS, cc))
-    one = CUBE_TRUNC_ONE if cut is None else CUBE_CUT_ONE
-    up = one // CUBE_TRUNC_ONE
-    n_t = tr["cube_trunc_games"]
-    n = r["cube_games"] + n_t + (cut["cut_games"] if cut else 0)
-    s1 = r["cube_points"] * one + ty * up + (cut["cut_y"] if cut else 0)
-    s2 = (r["cube_points2"] * one * one + ty2 * up * up +
-          ((cut["cut_y2_hi"] << CUBE_CUT_SPLIT) + cut["cut_y2_lo"] if cut else 0))
-
-    def per_game(v):
-        return v / n if n > 0 else 0.0
-
-    var_num = max(n * s2 - s1 * s1, 0)                   # n^2 (n - 1) one^2 x the variance of the mean
-    r.update(tr)
-    if cut:
-        r.update(cut, cut_share=per_game(cut["cut_games"]))
-    r.update(games=n, truncated_games=n_t, truncated_share=per_game(n_t),
-             truncated_equity_cubeful=ty / (n_t * CUBE_TRUNC_ONE) if n_t > 0 else 0.0,
-             equity_cubeful=s1 / (n * one) if n > 0 else 0.0,
-             equity_cubeful_stderr=math.sqrt(var_num / (n * n * (n - 1))) / one if n > 1 else 0.0,
-             pass_share=per_game(r["pass_games"]), doubles_per_game=per_game(r["doubles"]),
-             mean_cube_log2=per_game(r["cube_log2"] + tr["cube_trunc_log2"] + (cut["cut_log2"] if cut else 0)),
-             plies_per_game=per_game(r["played_out"]["plies"] + r["pass_plies"] + tr["cube_trunc_plies"] +
-                                     (cut["cut_plies"] if cut else 0)))
-    return r
 
 
 def static_cube_decision(eng_or_records, head, cube=None, scale: float = 1.0, life: CubeLife = None, cap: int = 6,

@@ -42,90 +42,15 @@ from . import _lib
 from ._lib import check
 from .arena import PLAYER_KINDS, SYNC_EVERY, TRACE_LIMIT, _stream, load_net, make_player
 from .engine import Engine, R_CUR, R_ROLL0, R_ROLL1, _ptr, validate_starts
-from .truncate import (TRUNC_FIELDS, Truncation, summarize_truncated, summarize_truncated_luck,  # noqa: F401
-                       truncate_reference)
+from .replay import LaneReplay
+from .tally import (CUBE_CUT_FIELDS, CUBE_FIELDS, CUBE_TRUNC_FIELDS, CUT_FIELDS, CUT_ONE, FIELDS, LUCK_CLAMP,  # noqa: F401
+                    LUCK_FIELDS, LUCK_ONE, TRUNC_FIELDS, summarize, summarize_bearoff, summarize_cube,
+                    summarize_cube_bearoff, summarize_cube_truncated, summarize_luck, summarize_truncated,
+                    summarize_truncated_luck)
+from .truncate import Truncation, truncate_reference  # noqa: F401
 
-# tally int64[n_groups][8] (include/bgx.h bgx_rollout_field)
-FIELDS = ("games", "plies", "win1", "win2", "win3", "loss1", "loss2", "loss3")
-# luck_tally int64[n_groups][4] (include/bgx.h bgx_rollout_luck_field): fixed point, 2^-16 points
-LUCK_FIELDS = ("luck", "luck2", "resluck", "luck_games")
-LUCK_ONE = 65536                    # Lq = rint(L * LUCK_ONE)
-LUCK_CLAMP = 1 << 21                # |Lq| <= LUCK_CLAMP
 ROLLS36 = [(a, b) for a in range(1, 7) for b in range(1, 7)]       # the 36 ordered rolls
 FIRST_ROLLS = ("stratified", "random")
-# cut_tally int64[n_groups][4] (include/bgx.h bgx_rollout_cut_field): fixed point, 2^-20
-CUT_FIELDS = ("cut_games", "cut_plies", "cut_p", "cut_p2")
-CUT_ONE = 1 << 20                   # Pq = rint(q * CUT_ONE), q the start mover's exact win probability
-
-
-def summarize(tally_row, unfinished: int = 0) -> dict:
-    """One position's result from its 8 tally entries: `games`, `plies_per_game`, the
-    cumulative rates of each side (`win` = any win, `win_gammon` = gammon or backgammon,
-    `win_backgammon`; `loss*` likewise), `equity` = sum_k k (WINk - LOSSk) / games in points,
-    `equity_stderr` = sqrt((sum_k k^2 (WINk + LOSSk) - games equity^2) / (games - 1) / games),
-    the standard error of a mean of independent games, and `unfinished` (scheduled games that
-    did not end).  With stratified first rolls the games are not independent draws -- each
-    first roll occurs exactly equally often, which removes that part of the variance -- so
-    the standard error is a conservative bound there.  No games: the rates are 0; one game:
-    the standard error is 0."""
-    t = [int(v) for v in tally_row]
-    if len(t) != len(FIELDS):
-        raise ValueError(f"summarize: a tally row has {len(FIELDS)} entries, got {len(t)}")
-    r = dict(zip(FIELDS, t))
-    g = r["games"]
-    w, l = t[2:5], t[5:8]
-    inv = 1.0 / g if g > 0 else 0.0
-    eq = sum((k + 1) * (w[k] - l[k]) for k in range(3)) * inv
-    sq = sum((k + 1) ** 2 * (w[k] + l[k]) for k in range(3))
-    var = max(sq - g * eq * eq, 0.0) / (g - 1) / g if g > 1 else 0.0
-    r.update(plies_per_game=r["plies"] * inv,
-             win=sum(w) * inv, win_gammon=(w[1] + w[2]) * inv, win_backgammon=w[2] * inv,
-             loss=sum(l) * inv, loss_gammon=(l[1] + l[2]) * inv, loss_backgammon=l[2] * inv,
-             equity=eq, equity_stderr=math.sqrt(var), unfinished=int(unfinished))
-    return r
-
-
-def summarize_luck(tally_row, luck_row, scale="fit", unfinished: int = 0) -> dict:
-    """summarize(tally_row, unfinished) plus the luck-adjusted estimate from the row's 4 luck
-    sums (LUCK_FIELDS; DESIGN.md "Luck adjustment").  A game's adjusted result is
-    y = res - c L with L its luck (the sum over its rolls of the value after the roll that came
-    minus the mean over all 21 rolls, signed for the start mover).  E[L] = 0, so any constant
-    c leaves the mean unbiased.  In fp64 from the integer sums, n = games, sum L = LUCK / 2^16,
-    sum L^2 = LUCK2 / 2^32, sum res L = RESLUCK / 2^16:
-        equity_luck = (sum res - c sum L) / n
-        var_y = (sum res^2 - 2 c sum res L + c^2 sum L^2 - n equity_luck^2) / (n - 1), >= 0
-        equity_luck_stderr = sqrt(var_y / n)        variance_ratio = var_y / var_res
-    (variance_ratio 1.0 when var_res is 0; n < 2: the stderr is 0).  `scale` = "fit": the
-    control-variate coefficient c = cov(res, L) / var(L) of these games (0 when var(L) is 0),
-    which absorbs the unit difference between the net's reward scale and points and never
-    raises the variance in the limit; fitted on the same games, it biases equity_luck by
-    O(1/n).  A float: that fixed c (1.0 when the net's values are in points).  Adds luck_scale
-    (c), luck_mean (sum L / n), equity_luck, equity_luck_stderr and variance_ratio.  Raises
-    ValueError when the luck row counts other games than the tally row."""
-    r = summarize(tally_row, unfinished)
-    k = [int(v) for v in luck_row]
-    if len(k) != len(LUCK_FIELDS):
-        raise ValueError(f"summarize_luck: a luck row has {len(LUCK_FIELDS)} entries, got {len(k)}")
-    n = r["games"]
-    if k[3] != n:
-        raise ValueError(f"summarize_luck: the luck row counts {k[3]} games, the tally row {n}")
-    sl, sl2, srl = k[0] / LUCK_ONE, k[1] / (LUCK_ONE * LUCK_ONE), k[2] / LUCK_ONE
-    w, l = [r[f"win{j}"] for j in (1, 2, 3)], [r[f"loss{j}"] for j in (1, 2, 3)]
-    sr = sum((j + 1) * (w[j] - l[j]) for j in range(3))
-    sr2 = float(sum((j + 1) ** 2 * (w[j] + l[j]) for j in range(3)))
-    if scale == "fit":
-        # numerator and denominator times n, as exact integers: a constant result gives 0
-        num, den = n * k[2] - sr * k[0], n * k[1] - k[0] * k[0]
-        c = LUCK_ONE * (num / den) if den > 0 else 0.0
-    else:
-        c = float(scale)
-    inv = 1.0 / n if n > 0 else 0.0
-    eq = (sr - c * sl) * inv
-    var_y = max(sr2 - 2.0 * c * srl + c * c * sl2 - n * eq * eq, 0.0) / (n - 1) if n > 1 else 0.0
-    var_r = max(sr2 - n * r["equity"] ** 2, 0.0) / (n - 1) if n > 1 else 0.0
-    r.update(luck_scale=c, luck_mean=sl * inv, equity_luck=eq, equity_luck_stderr=math.sqrt(var_y * inv),
-             variance_ratio=var_y / var_r if var_r > 0.0 else 1.0)
-    return r
 
 
 def luck_tally_reference(luck, mover, done, info, starts, group, n_groups: int, games_per_lane: int) -> np.ndarray:
@@ -136,72 +61,13 @@ def luck_tally_reference(luck, mover, done, info, starts, group, n_groups: int, 
     +-2^21, 0 when not finite.  `luck`, `mover`, `done`, `info`: [steps, B] as run_lanes
     traces them; `starts` uint8[B, 64]; `group` int32[B].  A lane is active while its group is
     in [0, n_groups) and it has finished fewer than `games_per_lane` games."""
-    luck = np.asarray(luck, np.float32)
-    mover, done, info = np.asarray(mover), np.asarray(done), np.asarray(info).astype(np.int64)
-    starts, group = np.asarray(starts), np.asarray(group).astype(np.int64)
-    B, P, G = group.shape[0], int(n_groups), int(games_per_lane)
-    valid = (group >= 0) & (group < P)
-    fixed = starts[:, R_ROLL0] != 0
-    lane = np.zeros(B, np.float32)
-    plies = np.zeros(B, np.int64)
-    games = np.zeros(B, np.int64)
-    tally = np.zeros((P, len(LUCK_FIELDS)), np.int64)
+    luck, mover = np.asarray(luck, np.float32), np.asarray(mover)
+    rp = LaneReplay(starts, group, n_groups, games_per_lane)
+    rp.tally("luck_tally", LUCK_FIELDS)
     for t in range(luck.shape[0]):
-        sel = valid & (games < G)
-        add = sel & ~((plies == 0) & fixed)
-        signed = np.where(mover[t] == starts[:, R_CUR], luck[t], -luck[t]).astype(np.float32)
-        lane = np.where(add, (lane + np.where(add, signed, np.float32(0))).astype(np.float32), lane)
-        winner = ((info[t] >> 8) & 0xFF) - 1
-        score = np.clip((info[t] >> 16) & 0xFF, 1, 3)
-        dn = sel & (done[t] != 0)
-        fin = dn & (winner >= 0)
-        x = (lane * np.float32(LUCK_ONE)).astype(np.float32)
-        x = np.where(np.isfinite(x), np.clip(x, -float(LUCK_CLAMP), float(LUCK_CLAMP)), 0.0)
-        lq = np.rint(x).astype(np.int64)
-        res = np.where(winner == (starts[:, R_CUR] & 1), score, -score)
-        for f, v in enumerate((lq, lq * lq, res * lq, np.ones(B, np.int64))):
-            np.add.at(tally[:, f], group[fin], v[fin])
-        lane = np.where(dn, np.float32(0), lane)
-        plies = np.where(sel, np.where(fin, 0, plies + 1), plies)
-        games += fin
-    return tally
-
-
-def summarize_bearoff(tally_row, cut_row, unfinished: int = 0) -> dict:
-    """One position's result from its 8 tally entries (the games played to the end) and its 4
-    cut sums (CUT_FIELDS: the games that reached the bearoff table and were scored with the
-    start mover's exact win probability P).  A cut game's result is y = 2 P - 1
-    points (a single game: both sides have checkers off).  With n_c cut games,
-    sum P = CUT_P / 2^20 and sum P^2 = CUT_P2 / 2^40: sum y = 2 sum P - n_c and
-    sum y^2 = 4 sum P^2 - 4 sum P + n_c.  On summarize's fields: `games` = natural + cut,
-    `equity` = (sum res + sum y) / games, `equity_stderr` from sum res^2 + sum y^2 as summarize
-    forms it, `win` = (wins + sum P) / games and `loss` likewise, the gammon and backgammon
-    rates count natural games only (over all games), `plies_per_game` over both kinds; adds
-    `natural_games`, `cut_games` and `cut_share` = cut_games / games.  The sums are combined as
-    integers, so equal cut values give their value exactly and a standard error of 0.  The
-    cut removes the endgame's dice noise, so equity_stderr is that of the mixed sample."""
-    r = summarize(tally_row, unfinished)
-    c = [int(v) for v in cut_row]
-    if len(c) != len(CUT_FIELDS):
-        raise ValueError(f"summarize_bearoff: a cut row has {len(CUT_FIELDS)} entries, got {len(c)}")
-    n_c, cut_plies, sp, sp2 = c
-    w, l = [r[f"win{j}"] for j in (1, 2, 3)], [r[f"loss{j}"] for j in (1, 2, 3)]
-    n_nat = r["games"]
-    n = n_nat + n_c
-    # sum of results in 2^-20 points, sum of squares in 2^-40: exact integers
-    s1 = sum((k + 1) * (w[k] - l[k]) for k in range(3)) * CUT_ONE + 2 * sp - n_c * CUT_ONE
-    s2 = sum((k + 1) ** 2 * (w[k] + l[k]) for k in range(3)) * CUT_ONE ** 2 + 4 * sp2 - 4 * sp * CUT_ONE + n_c * CUT_ONE ** 2
-    inv = 1.0 / n if n > 0 else 0.0
-    var_num = max(n * s2 - s1 * s1, 0)                       # n^2 (n - 1) CUT_ONE^2 x the variance of the mean
-    r.update(games=n, natural_games=n_nat, cut_games=n_c, cut_share=n_c * inv,
-             plies_per_game=(r["plies"] + cut_plies) * inv,
-             win=(sum(w) * CUT_ONE + sp) / (n * CUT_ONE) if n > 0 else 0.0,
-             loss=(sum(l) * CUT_ONE + n_c * CUT_ONE - sp) / (n * CUT_ONE) if n > 0 else 0.0,
-             win_gammon=(w[1] + w[2]) * inv, win_backgammon=w[2] * inv,
-             loss_gammon=(l[1] + l[2]) * inv, loss_backgammon=l[2] * inv,
-             equity=s1 / (n * CUT_ONE) if n > 0 else 0.0,
-             equity_stderr=math.sqrt(var_num / (n * n * (n - 1))) / CUT_ONE if n > 1 else 0.0)
-    return r
+        rp.luck_add(luck[t], mover[t])
+        rp.advance(done[t], info[t])
+    return rp.tallies["luck_tally"]
 
 
 def bearoff_cut_reference(records0, records, done, info, starts, group, n_groups: int, games_per_lane: int,
@@ -223,46 +89,25 @@ def bearoff_cut_reference(records0, records, done, info, starts, group, n_groups
 
         def lookup(recs):
             return lookup_reference(recs, configs, table, max_checkers)
-    records0, records = np.asarray(records0), np.asarray(records)
-    done, info = np.asarray(done), np.asarray(info).astype(np.int64)
-    starts, group = np.asarray(starts), np.asarray(group).astype(np.int64)
-    B, P, G = group.shape[0], int(n_groups), int(games_per_lane)
-    valid = (group >= 0) & (group < P)
-    sel = valid & (G > 0)
-    plies, games = np.zeros(B, np.int64), np.zeros(B, np.int64)
-    tally, cut_tally = np.zeros((P, len(FIELDS)), np.int64), np.zeros((P, len(CUT_FIELDS)), np.int64)
+    records0, records, done = np.asarray(records0), np.asarray(records), np.asarray(done)
+    rp = LaneReplay(starts, group, n_groups, games_per_lane)
+    rp.tally("cut_tally", CUT_FIELDS)
 
     def cut(recs):
-        nonlocal sel
         in_db, w = lookup(recs)
-        m = sel & in_db
+        m = rp.sel & in_db
         w = np.where(m, w, np.float32(0)).astype(np.float32)
-        q = np.where(recs[:, R_CUR] == starts[:, R_CUR], w, (np.float32(1) - w).astype(np.float32))
+        q = np.where(recs[:, R_CUR] == rp.start_cur, w, (np.float32(1) - w).astype(np.float32))
         pq = np.clip(np.rint((q * np.float32(CUT_ONE)).astype(np.float32)).astype(np.int64), 0, CUT_ONE)
-        for f, v in enumerate((np.ones(B, np.int64), plies, pq, pq * pq)):
-            np.add.at(cut_tally[:, f], group[m], v[m])
-        games[m] += 1
-        plies[m] = 0
-        sel = sel & ~(m & (games >= G))
+        rp.cut("cut_tally", m, (pq, pq * pq))
         return m
 
     cut0 = cut(records0)
     cuts = np.zeros(done.shape, bool)
     for t in range(done.shape[0]):
-        winner = ((info[t] >> 8) & 0xFF) - 1
-        score = np.clip((info[t] >> 16) & 0xFF, 1, 3)
-        fin = sel & (done[t] != 0) & (winner >= 0)
-        plies[sel] += 1
-        won = winner == (starts[:, R_CUR] & 1)
-        field = np.where(won, 2, 5) + score - 1
-        np.add.at(tally[:, 0], group[fin], 1)
-        np.add.at(tally[:, 1], group[fin], plies[fin])
-        np.add.at(tally, (group[fin], field[fin]), 1)
-        games[fin] += 1
-        plies[fin] = 0
-        sel = sel & ~(fin & (games >= G))
+        rp.advance(done[t], info[t])
         cuts[t] = cut(records[t])
-    return dict(tally=tally, cut_tally=cut_tally, games_done=games, active=int(sel.sum()), cut0=cut0, cut=cuts)
+    return dict(rp.tallies, games_done=rp.games, active=rp.active, cut0=cut0, cut=cuts)
 
 
 def layout(n_positions: int, trials: int, first_roll: str = "stratified", batch: int = 4096):
@@ -435,7 +280,7 @@ class _CubeStage(_Stage):
     cube_equity (NaN off cube_dsel) and cube_mask (the passes)."""
 
     def __init__(self, c: _Pass, rule, cube0):
-        from .cube import CUBE_FIELDS, validate_cube0
+        from .cube import validate_cube0
         self.c, self.rule = c, rule
         self.c0 = (torch.zeros(c.B, dtype=torch.uint8, device=c.dev) if cube0 is None
                    else torch.as_tensor(cube0).to(c.dev).contiguous())
@@ -500,7 +345,6 @@ class _TableCutStage(_Stage):
     def __init__(self, c: _Pass, table, cube: _CubeStage = None):
         self.c, self.table = c, table
         if table.kind == "cubeful":
-            from .cube import CUBE_CUT_FIELDS
             what, fields, self.entry = "cubeful bearoff table", CUBE_CUT_FIELDS, "bgx_rollout_cube_bearoff_cut"
             self.extra = (cube.rule.cap, _ptr(cube.c0), _ptr(cube.state))
         else:
@@ -531,79 +375,83 @@ class _TableCutStage(_Stage):
     after_advance = cut
 
 
-class _TruncStage(_Stage):
-    """`truncate` (a truncate.Truncation; DESIGN.md §14): a game that has run truncate.plies plies
-    without ending stops there and is scored with the truncation's value of the side on roll.
-    After advance: trunc_sel, value, trunc_cut, reset(mask) -- the cut sits where the bearoff cut
-    sits, where the truncated game's luck sum is complete (the roll now in the record is added
-    only at the next step), and the masked reset gives the lane its start record again.  With a
-    value head at lookahead 0 the stage is sync-free.  `with_luck`: the luck stage runs too and
-    trunc_cut also takes and clears the truncated games' luck sums (summarize_truncated_luck).
-    Result (after luck_tally, if any): trunc_tally int64[n_groups, 7] (truncate.TRUNC_FIELDS);
-    the trace gains per step trunc uint8 (the lanes truncated), trunc_value (NaN off them) and
-    trunc_mover (the side on roll there)."""
+class _HorizonStage(_Stage):
+    """The two horizon cuts: after advance trunc_sel, value, the stage's cut(tv), reset(mask) -- where
+    the bearoff cut sits; the masked reset gives the lane its start record again.  Sync-free when the
+    truncation is.  The trace gains per step `prefix` uint8 (the lanes truncated), prefix_value (NaN
+    off them), prefix_mover (the side on roll there) and the stage's extra_fields."""
+    extra_fields = ()
 
-    def __init__(self, c: _Pass, truncation, with_luck: bool):
+    def __init__(self, c: _Pass, truncation, fields):
         self.c, self.t, self.sync_free = c, truncation, truncation.sync_free
-        self.luck = _ptr(c.ro.lane_luck) if with_luck else None
-        self.tally = c.tally(TRUNC_FIELDS)
+        self.tally = c.tally(fields)
         self.tsel, self.mask = c.lane_buffers(2, torch.uint8)
         self.buf, self.scratch = c.lane_buffers(2, torch.float32, float("nan"))
-        c.traced(("trunc", torch.uint8), ("trunc_value", torch.float32), ("trunc_mover", torch.uint8))
+        p = self.prefix
+        c.traced((p, torch.uint8), (p + "_value", torch.float32), (p + "_mover", torch.uint8), *self.extra_fields)
+
+    def extra_trace(self, step):
+        pass
 
     def after_advance(self, step):
-        c, tr = self.c, self.c.tr
+        c, tr, p = self.c, self.c.tr, self.prefix
         check(c.L.bgx_rollout_trunc_sel(c.recs, _ptr(c.grp), c.B, c.P, self.t.plies, c.lanes[1], c.lanes[2],
                                         _ptr(self.tsel), None, c.stream), "bgx_rollout_trunc_sel")
         tv = self.t.equity(c.eng, self.tsel, self.scratch, self.buf)
         if tr is not None:
             c.eng.records(out=c.rec)
-            tr["trunc"][step] = self.tsel
-            tr["trunc_value"][step] = torch.where(self.tsel != 0, tv, float("nan"))
-            tr["trunc_mover"][step] = c.rec[:, R_CUR]
-        check(c.L.bgx_rollout_trunc_cut(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(self.tsel), _ptr(tv), self.t.scale,
-                                        c.B, c.P, c.G, *c.lanes, self.luck, _ptr(self.tally), c.active,
-                                        _ptr(self.mask), c.stream), "bgx_rollout_trunc_cut")
+            tr[p][step] = self.tsel
+            tr[p + "_value"][step] = torch.where(self.tsel != 0, tv, float("nan"))
+            tr[p + "_mover"][step] = c.rec[:, R_CUR]
+            self.extra_trace(step)
+        self.cut(tv)
         c.reset(self.mask)
 
 
-class _CubeTruncStage(_Stage):
+class _TruncStage(_HorizonStage):
+    """`truncate` (a truncate.Truncation; DESIGN.md §14): a game that has run truncate.plies plies
+    without ending stops there and is scored with the truncation's value of the side on roll
+    (trunc_cut).  The cut sits where the truncated game's luck sum is complete (the roll now in the
+    record is added only at the next step).  `with_luck`: the luck stage runs too and trunc_cut also
+    takes and clears the truncated games' luck sums (summarize_truncated_luck).  Result (after
+    luck_tally, if any): trunc_tally int64[n_groups, 7] (TRUNC_FIELDS)."""
+    prefix = "trunc"
+
+    def __init__(self, c: _Pass, truncation, with_luck: bool):
+        super().__init__(c, truncation, TRUNC_FIELDS)
+        self.luck = _ptr(c.ro.lane_luck) if with_luck else None
+
+    def cut(self, tv):
+        c = self.c
+        check(c.L.bgx_rollout_trunc_cut(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(self.tsel), _ptr(tv), self.t.scale,
+                                        c.B, c.P, c.G, *c.lanes, self.luck, _ptr(self.tally), c.active,
+                                        _ptr(self.mask), c.stream), "bgx_rollout_trunc_cut")
+
+
+class _CubeTruncStage(_HorizonStage):
     """`cube_truncate` (a cube.CubeTruncation), with `cube`: a cubeful game that has
     run cube_truncate.plies plies without ending stops there and is scored with Janowski's
-    cube-life equity of the side on roll, times the lane's cube.  After advance, as the last
-    stage (after the table cut, whose lanes have plies 0 and so are not truncated in the same
-    step): trunc_sel, value, cube_trunc_cut (which also takes the cube stage's cap, Jacoby rule,
-    cube0 and state), reset(mask).  Sync-free when the truncation is.  Result (after cube_tally
-    and cube_cut_tally, if any): cube_trunc_tally int64[n_groups, 6] (cube.CUBE_TRUNC_FIELDS); the
-    trace gains per step ctrunc uint8 (the lanes truncated), ctrunc_value (NaN off them),
-    ctrunc_mover (the side on roll there) and ctrunc_cube (the cube states before the cut)."""
+    cube-life equity of the side on roll, times the lane's cube (cube_trunc_cut, which also takes
+    the cube stage's cap, Jacoby rule, cube0 and state).  It is the last stage (after the table cut,
+    whose lanes have plies 0 and so are not truncated in the same step).  Result (after cube_tally
+    and cube_cut_tally, if any): cube_trunc_tally int64[n_groups, 6] (CUBE_TRUNC_FIELDS); the trace
+    also gains ctrunc_cube (the cube states before the cut)."""
+    prefix = "ctrunc"
+    extra_fields = (("ctrunc_cube", torch.uint8),)
 
     def __init__(self, c: _Pass, truncation, cube: _CubeStage):
-        from .cube import CUBE_TRUNC_FIELDS
-        self.c, self.t, self.cube, self.sync_free = c, truncation, cube, truncation.sync_free
-        self.life = truncation.life.struct()
-        self.tally = c.tally(CUBE_TRUNC_FIELDS)
-        self.tsel, self.mask = c.lane_buffers(2, torch.uint8)
-        self.buf, self.scratch = c.lane_buffers(2, torch.float32, float("nan"))
-        c.traced(("ctrunc", torch.uint8), ("ctrunc_value", torch.float32), ("ctrunc_mover", torch.uint8),
-                 ("ctrunc_cube", torch.uint8))
+        super().__init__(c, truncation, CUBE_TRUNC_FIELDS)
+        self.cube, self.life = cube, truncation.life.struct()
 
-    def after_advance(self, step):
-        c, tr, rule = self.c, self.c.tr, self.cube.rule
-        check(c.L.bgx_rollout_trunc_sel(c.recs, _ptr(c.grp), c.B, c.P, self.t.plies, c.lanes[1], c.lanes[2],
-                                        _ptr(self.tsel), None, c.stream), "bgx_rollout_trunc_sel")
-        tv = self.t.equity(c.eng, self.tsel, self.scratch, self.buf)
-        if tr is not None:
-            c.eng.records(out=c.rec)
-            tr["ctrunc"][step] = self.tsel
-            tr["ctrunc_value"][step] = torch.where(self.tsel != 0, tv, float("nan"))
-            tr["ctrunc_mover"][step] = c.rec[:, R_CUR]
-            tr["ctrunc_cube"][step] = self.cube.state
+    def extra_trace(self, step):
+        self.c.tr["ctrunc_cube"][step] = self.cube.state
+
+    def cut(self, tv):
+        c, rule = self.c, self.cube.rule
         check(c.L.bgx_rollout_cube_trunc_cut(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(self.tsel), _ptr(tv),
                                              self.t.scale, self.life, c.B, c.P, c.G, *c.lanes, _ptr(self.tally),
                                              c.active, _ptr(self.mask), rule.cap, int(rule.jacoby), _ptr(self.cube.c0),
                                              _ptr(self.cube.state), c.stream), "bgx_rollout_cube_trunc_cut")
-        c.reset(self.mask)
 
 
 class Rollout:
@@ -800,7 +648,6 @@ def _summary(luck, bearoff, cube, truncate, cube_bearoff, cube_truncate=None):
     """The summary of a position's rows by the modes of the run (after _check_modes): a function
     (tally_row, *the modes' rows in run_lanes' order, [luck_scale with luck,] unfinished)."""
     if cube is not None:
-        from .cube import summarize_cube, summarize_cube_bearoff, summarize_cube_truncated
         if cube_truncate is not None and cube_bearoff is not None:
             return lambda t, c, cut, tr, unf=0: summarize_cube_truncated(t, c, tr, unf, cut_row=cut)
         if cube_truncate is not None:

@@ -340,43 +340,24 @@ __global__ __launch_bounds__(256) void k_bo_act(const uint8_t* __restrict__ recs
 }
 
 // ---- rollout cut (bgx_rollout_bearoff_cut), after k_rollout_begin / k_rollout_advance ----
-// A selected lane with a valid group whose record is in the table ends its game here: its
-// start mover's exact win probability in 2^-20 fixed point goes to its group's row, the lane
-// counts the game and is marked for the caller's masked reset.  Per wave one add per (group,
-// field) it holds cut lanes of; integer adds commute.
+// bg_rollout.h's table_cut with this table's test and its exact win probability.  Per wave one
+// add per (group, field) it holds cut lanes of; integer adds commute.
 __global__ __launch_bounds__(256) void k_bo_cut(const uint8_t* __restrict__ recs, const uint8_t* __restrict__ starts,
                                                  const int32_t* __restrict__ group, int n_rec, int n_groups, int G,
                                                  int K, int n, const int16_t* __restrict__ rank_of,
                                                  const float* __restrict__ W, int32_t* games_done, int32_t* plies,
                                                  uint8_t* sel, int64_t* cut_tally, int64_t* active, uint8_t* mask) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool on = i < n_rec && sel[i] != 0;
-    const int g = on ? rollout_group(group, i, n_groups) : -1;
-    bool cut = false, retired = false;
-    long long pq = 0, pl = 0;
-    if (g >= 0) {
+    table_cut(starts, group, n_rec, n_groups, G, games_done, plies, sel, cut_tally, active, mask,
+              [&](int i, int* cur, float* w) {
         BoRec rec;
         rec.load(recs, i);
         int idx[2];
-        if (bo_in_table(rec, K, rank_of, idx)) {
-            cut = true;
-            const int m = rec.at(R_CUR) & 1;
-            const float w = W[(size_t)idx[m] * n + idx[1 - m]];
-            const float q = rec.at(R_CUR) == (int)starts[(size_t)i * 64 + R_CUR] ? w : __fsub_rn(1.0f, w);
-            pq = min(max(llrintf(__fmul_rn(q, 1048576.0f)), 0ll), 1048576ll);
-            retired = end_game(i, G, games_done, plies, sel, &pl);
-        }
-    }
-    if (i < n_rec) mask[i] = cut ? 1 : 0;
-    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
-        const long long v = mine ? pq : 0;
-        int64_t* row = cut_tally + (size_t)gl * 4;
-        tally_add(row, BGX_ROLLOUT_CUT_GAMES, (long long)__popcll(m));
-        tally_add(row, BGX_ROLLOUT_CUT_PLIES, wave_sum(mine ? pl : 0));
-        tally_add(row, BGX_ROLLOUT_CUT_P, wave_sum(v));
-        tally_add(row, BGX_ROLLOUT_CUT_P2, wave_sum(v * v));
+        if (!bo_in_table(rec, K, rank_of, idx)) return false;
+        *cur = rec.at(R_CUR);
+        const int m = *cur & 1;
+        *w = W[(size_t)idx[m] * n + idx[1 - m]];
+        return true;
     });
-    tally_add(active, 0, -count(retired));
 }
 
 // the host's list of configurations: (pip count, base-9 key) ascending

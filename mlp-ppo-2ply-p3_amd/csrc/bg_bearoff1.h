@@ -336,44 +336,25 @@ __global__ __launch_bounds__(256) void k_b1_act(const uint8_t* __restrict__ recs
     act[i] = arg;
 }
 
-// ---- rollout cut (bgx_rollout_bearoff1_cut): k_bo_cut on this table's value (end_game and
-// for_each_group, bg_rollout.h) ----
-// A selected lane with a valid group whose record is in the table with checkers of both sides
-// off (the test's value 1: the game can only be a single one) ends its game here.
+// ---- rollout cut (bgx_rollout_bearoff1_cut): bg_rollout.h's table_cut on this table, where the
+// record is in it with checkers of both sides off (the test's value 1: a single game) ----
 __global__ __launch_bounds__(256) void k_b1_cut(const uint8_t* __restrict__ recs, const uint8_t* __restrict__ starts,
                                                 const int32_t* __restrict__ group, int n_rec, int n_groups, int G,
                                                 int K, const int32_t* __restrict__ index_of,
                                                 const float* __restrict__ dist, const float* __restrict__ surv,
                                                 int32_t* games_done, int32_t* plies, uint8_t* sel, int64_t* cut_tally,
                                                 int64_t* active, uint8_t* mask) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool on = i < n_rec && sel[i] != 0;
-    const int g = on ? rollout_group(group, i, n_groups) : -1;
-    bool cut = false, retired = false;
-    long long pq = 0, pl = 0;
-    if (g >= 0) {
+    table_cut(starts, group, n_rec, n_groups, G, games_done, plies, sel, cut_tally, active, mask,
+              [&](int i, int* cur, float* w) {
         B1Rec rec;
         rec.load(recs, i);
         int idx[2];
-        if (b1_in_table(rec, K, index_of, idx) == 1) {
-            cut = true;
-            const int m = rec.at(R_CUR) & 1;
-            const float w = b1_win(dist + (size_t)idx[m] * kB1T, surv + (size_t)idx[1 - m] * kB1T);
-            const float q = rec.at(R_CUR) == (int)starts[(size_t)i * 64 + R_CUR] ? w : sub_rn(1.0f, w);
-            pq = min(max(llrintf(mul_rn(q, 1048576.0f)), 0ll), 1048576ll);
-            retired = end_game(i, G, games_done, plies, sel, &pl);
-        }
-    }
-    if (i < n_rec) mask[i] = cut ? 1 : 0;
-    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
-        const long long v = mine ? pq : 0;
-        int64_t* row = cut_tally + (size_t)gl * 4;
-        tally_add(row, BGX_ROLLOUT_CUT_GAMES, (long long)__popcll(m));
-        tally_add(row, BGX_ROLLOUT_CUT_PLIES, wave_sum(mine ? pl : 0));
-        tally_add(row, BGX_ROLLOUT_CUT_P, wave_sum(v));
-        tally_add(row, BGX_ROLLOUT_CUT_P2, wave_sum(v * v));
+        if (b1_in_table(rec, K, index_of, idx) != 1) return false;
+        *cur = rec.at(R_CUR);
+        const int m = *cur & 1;
+        *w = b1_win(dist + (size_t)idx[m] * kB1T, surv + (size_t)idx[1 - m] * kB1T);
+        return true;
     });
-    tally_add(active, 0, -count(retired));
 }
 
 // the host's list of configurations: (pip count, pack) ascending

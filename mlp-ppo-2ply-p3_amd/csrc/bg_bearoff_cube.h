@@ -26,7 +26,6 @@ namespace bg {
 
 // the cube as the record's mover sees it; dead: the cube shows 2^cap, nobody doubles any more
 enum BocState { kBocCen = 0, kBocOwn = 1, kBocOpp = 2, kBocDead = 3 };
-enum BocFlag { kBocMayDouble = 1, kBocDoubles = 2, kBocTakes = 4, kBocIsDead = 8 };
 constexpr float kBocOne = 1048576.0f;              // 2^20: the cut's fixed point
 
 CUBE_HD int boc_state(uint8_t c, int cap, int mover) {
@@ -211,8 +210,8 @@ __global__ __launch_bounds__(256) void k_boc_lookup(const uint8_t* __restrict__ 
 }
 
 // ---- the cubeful rollout cut (bgx_rollout_cube_bearoff_cut), after bgx_rollout_begin +
-// bgx_rollout_cube_begin and after every bgx_rollout_advance: k_bo_cut (end_game, for_each_group) with the
-// cubeful expectation, scaled by the lane's cube, as the game's result ----
+// bgx_rollout_cube_begin and after every bgx_rollout_advance: bg_rollout.h's cut skeleton (cut_group,
+// end_game, cut_finish) with the cubeful expectation, scaled by the lane's cube, as the game's result ----
 __global__ __launch_bounds__(256) void k_boc_cut(const uint8_t* __restrict__ recs, const uint8_t* __restrict__ starts,
                                                  const int32_t* __restrict__ group, int n_rec, int n_groups, int G,
                                                  int cap, int K, int n, const int16_t* __restrict__ rank_of,
@@ -220,9 +219,10 @@ __global__ __launch_bounds__(256) void k_boc_cut(const uint8_t* __restrict__ rec
                                                  const float* __restrict__ W, const uint8_t* __restrict__ cube0,
                                                  uint8_t* cube, int32_t* games_done, int32_t* plies, uint8_t* sel,
                                                  int64_t* cut_tally, int64_t* active, uint8_t* mask) {
+    static_assert(BGX_ROLLOUT_CUBE_CUT_Y == 2 && BGX_ROLLOUT_CUBE_CUT_Y2_LO == 3 && BGX_ROLLOUT_CUBE_CUT_Y2_HI == 4 &&
+                  BGX_ROLLOUT_CUBE_CUT_LOG2 == 5, "cube_cut_tally: `own` in field order");
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool on = i < n_rec && sel[i] != 0;
-    const int g = on ? rollout_group(group, i, n_groups) : -1;
+    const int g = cut_group(sel, group, i, n_rec, n_groups);
     bool cut = false, retired = false;
     long long yq = 0, pl = 0, kk = 0;
     if (g >= 0) {
@@ -240,18 +240,9 @@ __global__ __launch_bounds__(256) void k_boc_cut(const uint8_t* __restrict__ rec
             cube[i] = cube_sanitise(cube0[i], cap);
         }
     }
-    if (i < n_rec) mask[i] = cut ? 1 : 0;
-    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
-        const long long y = mine ? yq : 0, y2 = y * y;
-        int64_t* row = cut_tally + (size_t)gl * 6;
-        tally_add(row, BGX_ROLLOUT_CUBE_CUT_GAMES, (long long)__popcll(m));
-        tally_add(row, BGX_ROLLOUT_CUBE_CUT_PLIES, wave_sum(mine ? pl : 0));
-        tally_add(row, BGX_ROLLOUT_CUBE_CUT_Y, wave_sum(y));
-        tally_add(row, BGX_ROLLOUT_CUBE_CUT_Y2_LO, wave_sum(y2 & ((1ll << 30) - 1)));
-        tally_add(row, BGX_ROLLOUT_CUBE_CUT_Y2_HI, wave_sum(y2 >> 30));
-        tally_add(row, BGX_ROLLOUT_CUBE_CUT_LOG2, wave_sum(mine ? kk : 0));
-    });
-    tally_add(active, 0, -count(retired));
+    long long own[4] = {yq, 0, 0, kk};
+    square_split(yq, &own[1], &own[2]);
+    cut_finish(i, n_rec, cut, retired, g, pl, own, cut_tally, active, mask);
 }
 
 }  // namespace

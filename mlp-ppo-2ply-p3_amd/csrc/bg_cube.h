@@ -24,6 +24,8 @@ namespace bg {
 
 constexpr int kCubeMaxCap = 10;
 enum CubeAction { kCubeNone = 0, kCubeTake = 1, kCubePass = 2 };
+// the flags of bgx_bearoff_cube_lookup and bgx_cube_janowski (bg_bearoff_cube.h, bg_cube_trunc.h)
+enum BocFlag { kBocMayDouble = 1, kBocDoubles = 2, kBocTakes = 4, kBocIsDead = 8 };
 
 CUBE_HD int cube_k(uint8_t c, int cap) {
     const int k = c & 15;

@@ -10,7 +10,7 @@
 // ct_mul / ct_add / ct_sub, which carry no contraction flag (bg_returns.hip's mul_rn / add_rn /
 // sub_rn for host and device); a compiler without the pragma takes -ffp-contract=off.
 // Part 2 (device): the two kernels, one thread per lane, and their C entry points.  They use
-// bg_rollout.h's helpers (tally_add, count, wave_sum, for_each_group, end_game).  No LDS, no
+// bg_rollout.h's cut skeleton (cut_group, end_game, square_split, cut_finish).  No LDS, no
 // scratch.  BGX_CUBE_TRUNC_PART1_ONLY (the host test program tools/cube_trunc_host.cpp, any C++
 // compiler) takes part 1 alone.
 #pragma once
@@ -24,7 +24,6 @@
 
 namespace bg {
 
-enum CtFlag { kCtMayDouble = 1, kCtDoubles = 2, kCtTakes = 4, kCtIsDead = 8 };   // bg_bearoff_cube.h's BocFlag
 constexpr float kCtOne = 65536.0f;               // 2^16: the cut's fixed point, bg_trunc.h's
 constexpr float kCtClamp = 196608.0f;            // 3 points
 
@@ -98,8 +97,8 @@ CUBE_HD uint8_t cube_trunc_values(uint8_t c, int cap, int mover, float scale, fl
     values[1] = dt;
     values[2] = doubles ? cash : nd;
     values[3] = cl;
-    return (uint8_t)((access ? kCtMayDouble : 0) | (doubles ? kCtDoubles : 0) | (dt <= 1.0f ? kCtTakes : 0) |
-                     (dead ? kCtIsDead : 0));
+    return (uint8_t)((access ? kBocMayDouble : 0) | (doubles ? kBocDoubles : 0) | (dt <= 1.0f ? kBocTakes : 0) |
+                     (dead ? kBocIsDead : 0));
 }
 
 // A cut game's result in 2^-16 units of one point: e = the equity of the record's mover in units
@@ -147,8 +146,8 @@ __global__ __launch_bounds__(256) void k_cube_janowski(const uint8_t* __restrict
     if (flags) flags[i] = fl;
 }
 
-// The truncation of a cubeful game on the tsel lanes (k_trunc_cut with the rule's e, scaled by
-// the lane's cube, as the game's result; k_boc_cut's six sums in bg_trunc.h's unit).
+// The truncation of a cubeful game on the tsel lanes (bg_rollout.h's cut skeleton with the rule's e,
+// scaled by the lane's cube, as the game's result; k_boc_cut's six sums in bg_trunc.h's unit).
 __global__ __launch_bounds__(256) void k_cube_trunc_cut(const uint8_t* __restrict__ recs, const uint8_t* __restrict__ starts,
                                                         const int32_t* __restrict__ group,
                                                         const uint8_t* __restrict__ tsel, const float* __restrict__ value,
@@ -156,9 +155,10 @@ __global__ __launch_bounds__(256) void k_cube_trunc_cut(const uint8_t* __restric
                                                         int32_t* games_done, int32_t* plies, uint8_t* sel,
                                                         int64_t* tally, int64_t* active, uint8_t* mask, int cap, int jacoby,
                                                         const uint8_t* __restrict__ cube0, uint8_t* cube) {
+    static_assert(BGX_ROLLOUT_CUBE_TRUNC_Y == 2 && BGX_ROLLOUT_CUBE_TRUNC_Y2_LO == 3 &&
+                  BGX_ROLLOUT_CUBE_TRUNC_Y2_HI == 4 && BGX_ROLLOUT_CUBE_TRUNC_LOG2 == 5, "cube_trunc_tally: `own`");
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool on = i < n && tsel[i] != 0;
-    const int g = on ? rollout_group(group, i, n_groups) : -1;
+    const int g = cut_group(tsel, group, i, n, n_groups);
     const bool cut = g >= 0;
     bool retired = false;
     long long yq = 0, pl = 0, kk = 0;
@@ -172,18 +172,9 @@ __global__ __launch_bounds__(256) void k_cube_trunc_cut(const uint8_t* __restric
         retired = end_game(i, G, games_done, plies, sel, &pl);
         cube[i] = cube_sanitise(cube0[i], cap);
     }
-    if (i < n) mask[i] = cut ? 1 : 0;
-    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
-        const long long y = mine ? yq : 0, y2 = y * y;
-        int64_t* row = tally + (size_t)gl * 6;
-        tally_add(row, BGX_ROLLOUT_CUBE_TRUNC_GAMES, (long long)__popcll(m));
-        tally_add(row, BGX_ROLLOUT_CUBE_TRUNC_PLIES, wave_sum(mine ? pl : 0));
-        tally_add(row, BGX_ROLLOUT_CUBE_TRUNC_Y, wave_sum(y));
-        tally_add(row, BGX_ROLLOUT_CUBE_TRUNC_Y2_LO, wave_sum(y2 & ((1ll << 30) - 1)));
-        tally_add(row, BGX_ROLLOUT_CUBE_TRUNC_Y2_HI, wave_sum(y2 >> 30));
-        tally_add(row, BGX_ROLLOUT_CUBE_TRUNC_LOG2, wave_sum(mine ? kk : 0));
-    });
-    tally_add(active, 0, -count(retired));
+    long long own[4] = {yq, 0, 0, kk};
+    square_split(yq, &own[1], &own[2]);
+    cut_finish(i, n, cut, retired, g, pl, own, tally, active, mask);
 }
 
 bool cube_life_struct_ok(const bgx_cube_life& l) { return cube_life_ok(l.cube_life, l.win_value, l.loss_value); }

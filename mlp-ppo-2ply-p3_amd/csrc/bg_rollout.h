@@ -1,7 +1,7 @@
 // Device helpers of the accounting kernels of the arena and of position rollouts: the per-wave
-// integer sums, the group loop, a game's end.  Device-only: bg_engine.hip and part 2 of
-// bg_bearoff.h, bg_bearoff1.h, bg_cube.h, bg_trunc.h and bg_bearoff_cube.h include it; part 1 of
-// those headers and the host-only builds never see it.
+// integer sums, the group loop, a game's end, the cut skeleton.  Device-only: bg_engine.hip and
+// part 2 of bg_bearoff.h, bg_bearoff1.h, bg_cube.h, bg_trunc.h, bg_cube_trunc.h and
+// bg_bearoff_cube.h include it; part 1 of those headers and the host-only builds never see it.
 #pragma once
 #include "bg_engine.h"
 
@@ -68,6 +68,70 @@ __device__ __forceinline__ bool end_game(int i, int G, int32_t* games_done, int3
     const bool retired = gd >= G;
     if (retired) sel[i] = 0;
     return retired;
+}
+
+// ---- the cut skeleton of the kernels that end a game early (the table cuts k_bo_cut, k_b1_cut,
+// k_boc_cut, the horizon cuts k_trunc_cut, k_cube_trunc_cut): cut_group, the kernel's own scoring
+// of the lane with end_game, cut_finish ----
+// Thread i's group when flag[i] (the table cuts' sel, the horizon cuts' tsel) marks a lane with a valid one, else -1.
+__device__ __forceinline__ int cut_group(const uint8_t* flag, const int32_t* group, int i, int n, int n_groups) {
+    const bool on = i < n && flag[i] != 0;
+    return on ? rollout_group(group, i, n_groups) : -1;
+}
+
+// The tail: mask[i] = cut; per group of the wave's cut lanes GAMES += their number,
+// PLIES += their `pl` (end_game's plies_before) and field 2 + k += their own[k], on a tally of
+// 2 + N fields a row (every cut tally of include/bgx.h has GAMES = 0 and PLIES = 1; the
+// kernels assert the places of their own fields); the retired lanes leave `active`.  EVERY
+// thread of the wave calls it, outside any divergent branch: for_each_group's rule.
+template <int N>
+__device__ __forceinline__ void cut_finish(int i, int n, bool cut, bool retired, int g, long long pl,
+                                           const long long (&own)[N], int64_t* tally, int64_t* active, uint8_t* mask) {
+    static_assert(BGX_ROLLOUT_CUT_GAMES == 0 && BGX_ROLLOUT_TRUNC_GAMES == 0 && BGX_ROLLOUT_CUBE_CUT_GAMES == 0 &&
+                  BGX_ROLLOUT_CUBE_TRUNC_GAMES == 0 && BGX_ROLLOUT_CUT_PLIES == 1 && BGX_ROLLOUT_TRUNC_PLIES == 1 &&
+                  BGX_ROLLOUT_CUBE_CUT_PLIES == 1 && BGX_ROLLOUT_CUBE_TRUNC_PLIES == 1, "cut tallies: GAMES, PLIES");
+    if (i < n) mask[i] = cut ? 1 : 0;
+    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
+        int64_t* row = tally + (size_t)gl * (2 + N);
+        tally_add(row, 0, (long long)__popcll(m));
+        tally_add(row, 1, wave_sum(mine ? pl : 0));
+        #pragma unroll
+        for (int k = 0; k < N; ++k) tally_add(row, 2 + k, wave_sum(mine ? own[k] : 0));
+    });
+    tally_add(active, 0, -count(retired));
+}
+
+// y^2 of a cubeful result as the two sums that cannot overflow int64: y^2 & (2^30 - 1), y^2 >> 30
+__device__ __forceinline__ void square_split(long long y, long long* lo, long long* hi) {
+    const long long y2 = y * y;
+    *lo = y2 & ((1ll << 30) - 1);
+    *hi = y2 >> 30;
+}
+
+// A table cut (k_bo_cut, k_b1_cut): a selected lane with a valid group whose record is in the
+// table ends its game here: its start mover's win probability in 2^-20 fixed point goes to its
+// group's row, the lane counts the game and is marked for the caller's masked reset.
+// win(i, &cur, &w): the table's test on record i and, when it holds, the record's mover byte
+// and the win probability of the side on roll.
+template <class Win>
+__device__ __forceinline__ void table_cut(const uint8_t* __restrict__ starts, const int32_t* __restrict__ group,
+                                          int n_rec, int n_groups, int G, int32_t* games_done, int32_t* plies,
+                                          uint8_t* sel, int64_t* cut_tally, int64_t* active, uint8_t* mask, Win win) {
+    static_assert(BGX_ROLLOUT_CUT_P == 2 && BGX_ROLLOUT_CUT_P2 == 3, "cut_tally: P, P2 follow PLIES");
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int g = cut_group(sel, group, i, n_rec, n_groups);
+    bool cut = false, retired = false;
+    long long pq = 0, pl = 0;
+    int cur;
+    float w;
+    if (g >= 0 && win(i, &cur, &w)) {
+        cut = true;
+        const float q = cur == (int)starts[(size_t)i * 64 + R_CUR] ? w : __fsub_rn(1.0f, w);
+        pq = min(max(llrintf(__fmul_rn(q, 1048576.0f)), 0ll), 1048576ll);
+        retired = end_game(i, G, games_done, plies, sel, &pl);
+    }
+    const long long own[2] = {pq, pq * pq};
+    cut_finish(i, n_rec, cut, retired, g, pl, own, cut_tally, active, mask);
 }
 
 // a step's info word: the winner (-1 = none) and the game's points, 1..3

@@ -5,7 +5,7 @@
 // Part 1 (plain C++, host and device): the one function that turns a value into the game's
 // fixed-point result.
 // Part 2 (device): the two kernels, one thread per lane, and their C entry points.  They use
-// bg_rollout.h's helpers (tally_add, count, wave_sum, for_each_group, end_game).  No LDS, no
+// bg_rollout.h's helpers (tally_add, count, and the cut skeleton: cut_group, end_game, cut_finish).  No LDS, no
 // scratch.  BGX_TRUNC_PART1_ONLY (the host test program tools/trunc_host.cpp, any C++ compiler)
 // takes part 1 alone.
 #pragma once
@@ -69,9 +69,10 @@ __global__ __launch_bounds__(256) void k_trunc_cut(const uint8_t* __restrict__ r
                                                    float scale, int n, int n_groups, int G, int32_t* games_done,
                                                    int32_t* plies, uint8_t* sel, float* lane_luck, int64_t* trunc_tally,
                                                    int64_t* active, uint8_t* mask) {
+    static_assert(BGX_ROLLOUT_TRUNC_V == 2 && BGX_ROLLOUT_TRUNC_V2 == 3 && BGX_ROLLOUT_TRUNC_LUCK == 4 &&
+                  BGX_ROLLOUT_TRUNC_LUCK2 == 5 && BGX_ROLLOUT_TRUNC_VLUCK == 6, "trunc_tally: `own` in field order");
     const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool on = i < n && tsel[i] != 0;
-    const int g = on ? rollout_group(group, i, n_groups) : -1;
+    const int g = cut_group(tsel, group, i, n, n_groups);
     const bool cut = g >= 0;
     bool retired = false;
     long long vq = 0, lq = 0, pl = 0;
@@ -84,19 +85,8 @@ __global__ __launch_bounds__(256) void k_trunc_cut(const uint8_t* __restrict__ r
         }
         retired = end_game(i, G, games_done, plies, sel, &pl);
     }
-    if (i < n) mask[i] = cut ? 1 : 0;
-    for_each_group(cut, g, [&](int gl, bool mine, uint64_t m) {
-        const long long v = mine ? vq : 0, l = mine ? lq : 0;
-        int64_t* row = trunc_tally + (size_t)gl * 7;
-        tally_add(row, BGX_ROLLOUT_TRUNC_GAMES, (long long)__popcll(m));
-        tally_add(row, BGX_ROLLOUT_TRUNC_PLIES, wave_sum(mine ? pl : 0));
-        tally_add(row, BGX_ROLLOUT_TRUNC_V, wave_sum(v));
-        tally_add(row, BGX_ROLLOUT_TRUNC_V2, wave_sum(v * v));
-        tally_add(row, BGX_ROLLOUT_TRUNC_LUCK, wave_sum(l));
-        tally_add(row, BGX_ROLLOUT_TRUNC_LUCK2, wave_sum(l * l));
-        tally_add(row, BGX_ROLLOUT_TRUNC_VLUCK, wave_sum(v * l));
-    });
-    tally_add(active, 0, -count(retired));
+    const long long own[5] = {vq, vq * vq, lq, lq * lq, vq * lq};
+    cut_finish(i, n, cut, retired, g, pl, own, trunc_tally, active, mask);
 }
 
 }  // namespace

@@ -1,6 +1,9 @@
-"""Rollout.run_lanes / run after the rollout loop became one loop over stages (bgx/rollout.py,
-csrc/bg_rollout.h; DESIGN.md "Start positions and rollouts"): every mode computes exactly what
-the commit before that change computed.
+"""Rollout.run_lanes / run after the rollout loop became one loop over stages, and after the cut
+kernels, the horizon stages, the host replays and the summaries became one skeleton each
+(bgx/rollout.py, bgx/tally.py, csrc/bg_rollout.h; DESIGN.md "Start positions and rollouts"):
+every mode computes exactly what the commit before the change computed.  The file was recorded
+before the second change; its entries for the first eight modes equal, key by key, those recorded
+before the first.  "cube_bearoff_truncate" is cube + cube_bearoff + cube_truncate.
 
 tests/golden/rollout_modes.npz was recorded from the parent commit's library AND package
 (tools/record_rollout_modes.py, which runs `run_mode` below on that tree, never on the tree
@@ -13,9 +16,9 @@ The runs: 128 lanes (two waves), Philox dice, RandomPlayer, 2 games a lane, 3 gr
 and 38 lanes with 5 idle lanes among them, so wave 0 holds two groups and group 1 spans both
 waves.  Starts: group 0 the opening (long games), groups 1 and 2 both sides home with 3..8
 checkers (some inside the K = 6 table and, in the cubeful mode, the K = 3 table at the start:
-the cut after begin fires), every tenth lane a one-checker mover against 15 checkers in their
-home board (a gammon).  Value head, cube rule, horizon and tables are those of the GPU tests of
-each mode."""
+the cut after begin fires; "cube_bearoff_truncate" uses the cubeful mode's starts), every tenth
+lane a one-checker mover against 15 checkers in their home board (a gammon).  Value head, cube
+rule, horizon and tables are those of the GPU tests of each mode."""
 import hashlib
 import json
 import os
@@ -24,11 +27,18 @@ import numpy as np
 import pytest
 
 GOLDEN_NPZ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rollout_modes.npz")
-MODES = ("plain", "luck", "bearoff", "bearoff1", "cube", "cube_bearoff", "truncate", "truncate_luck")
+MODES = ("plain", "luck", "bearoff", "bearoff1", "cube", "cube_bearoff", "truncate", "truncate_luck", "cube_truncate",
+         "cube_bearoff_truncate")
 B, P, G = 128, 3, 2
 MAX_STEPS = 8000
 ROLLOUT_SEED, PLAYER_SEED = 5, 2
 HORIZON = 8
+# the cubeful truncation's horizons (a CubeTruncation on the same value head), chosen so that on
+# the recording commit truncated and naturally finished games both occur in "cube_truncate", a
+# table cut fires beside the truncation in "cube_bearoff_truncate" (whose starts are all short
+# races), and in each a lane's last game ends in the truncation kernel
+CUBE_HORIZON = 8
+CUBE_BEAROFF_HORIZON = 3
 CUBE_RULE = dict(double_at=0.13, pass_at=0.19, cap=4)        # test_gpu_cube.py's traced rule
 
 
@@ -53,8 +63,8 @@ def home_record(c1, c2, mover, roll=(0, 0)):
 
 def starts_for(mode):
     from bgx.rollout import opening_record
-    lo = 3 if mode == "cube_bearoff" else 5                   # the K = 3 table needs <= 3 checkers a side
-    hi = 6 if mode == "cube_bearoff" else 9
+    lo = 3 if "cube_bearoff" in mode else 5                   # the K = 3 table needs <= 3 checkers a side
+    hi = 6 if "cube_bearoff" in mode else 9
     rng = np.random.RandomState(21)
     group = groups()
     s = np.zeros((B, 64), np.uint8)
@@ -65,7 +75,7 @@ def starts_for(mode):
         if i % 10 == 3:
             c[mover], c[1 - mover] = (1, 0, 0, 0, 0, 0), (3, 3, 3, 2, 2, 2)
         s[i] = home_record(c[0], c[1], mover, roll)
-        if group[i] == 0 and mode != "cube_bearoff":
+        if group[i] == 0 and "cube_bearoff" not in mode:
             s[i] = opening_record().numpy()
             s[i, 52] = i & 1
     return s
@@ -87,7 +97,7 @@ def mode_kwargs(mode, group):
     """run_lanes' keyword arguments of a mode (cube0 by the lane's group) and those of run."""
     import torch
     from bgx.bearoff import BearoffDB, CubefulBearoffDB, OneSidedBearoffDB
-    from bgx.cube import CubeRule, pack
+    from bgx.cube import CubeRule, CubeTruncation, pack
     from bgx.policy import PolicyNet
     from bgx.search import ValueHead
     from bgx.truncate import Truncation
@@ -100,7 +110,12 @@ def mode_kwargs(mode, group):
           "cube": lambda: dict(cube=CubeRule(vh, jacoby=True, **CUBE_RULE)),
           "cube_bearoff": lambda: dict(cube=CubeRule(by_lane(B), cap=4), cube_bearoff=CubefulBearoffDB(BearoffDB(3))),
           "truncate": dict(truncate=Truncation(vh, HORIZON)),
-          "truncate_luck": dict(truncate=Truncation(vh, HORIZON), luck=vh)}[mode]
+          "truncate_luck": dict(truncate=Truncation(vh, HORIZON), luck=vh),
+          "cube_truncate": lambda: dict(cube=CubeRule(vh, jacoby=True, **CUBE_RULE),
+                                        cube_truncate=CubeTruncation(vh, CUBE_HORIZON)),
+          "cube_bearoff_truncate": lambda: dict(cube=CubeRule(by_lane(B), cap=4),
+                                                cube_bearoff=CubefulBearoffDB(BearoffDB(3)),
+                                                cube_truncate=CubeTruncation(vh, CUBE_BEAROFF_HORIZON))}[mode]
     kw = kw() if callable(kw) else kw
     lanes = dict(kw, cube0=cube0) if "cube" in kw else kw
     run = dict(kw, cube_start=[(0, 0), (1, 2)]) if "cube" in kw else kw

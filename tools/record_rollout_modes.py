@@ -7,8 +7,8 @@ library AND the bgx package of the commit BEFORE a change to the rollout loop or
 
 The runs are `run_mode` of this tree's test module, on the parent's package.  Before writing,
 the recorder checks that the parent finished every game of every mode and that each mode
-actually fired: a cut (one of them after begin), a double and a pass, a truncation, a nonzero
-luck sum, and a lane whose last game ended in a cut / decide kernel."""
+actually fired: a cut (one of them after begin), a double and a pass, a truncation (cubeless or
+cubeful), a nonzero luck sum, and a lane whose last game ended in a cut / decide / truncation kernel."""
 import os
 import sys
 
@@ -18,29 +18,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "mlp-ppo-2ply-p3_amd"
 
 
-def retired_in(tr, group, G, first, before, after):
+def retired_in(tr, group, G, first, before, after, only=None):
     """Lanes whose G-th game ended in a kernel other than advance: `first` the trace key of the
-    mask after begin (or None), `before` / `after` the per-step masks before the step and after
-    advance.  Replays the counting: masks fire on active lanes only, a natural end is a done
-    with a winner on an active lane."""
+    mask after begin (or None), `before` the per-step mask before the step, `after` the masks
+    after advance (one key or several, in the stages' order); `only`: count the lanes retired by
+    that mask alone.  Replays the counting: masks fire on active lanes only, a natural end is a
+    done with a winner on an active lane."""
     games = np.zeros(len(group), np.int64)
     hit = np.zeros(len(group), bool)
     valid = group >= 0
 
-    def end(m):
+    def end(m, key=None):
         m = m & valid & (games < G)
         games[m] += 1
-        return m & (games >= G)
+        return m & (games >= G) & (only is None or key == only)
+    after = (after,) if isinstance(after, str) else tuple(after or ())
     if first:
-        hit |= end(tr[first].cpu().numpy() != 0)
+        hit |= end(tr[first].cpu().numpy() != 0, first)
     done, info = tr["done"].cpu().numpy(), tr["info"].cpu().numpy().astype(np.int64)
-    masks = {k: tr[k].cpu().numpy() != 0 for k in (before, after) if k}
+    masks = {k: tr[k].cpu().numpy() != 0 for k in (before,) + after if k}
     for t in range(done.shape[0]):
         if before:
-            hit |= end(masks[before][t])
+            hit |= end(masks[before][t], before)
         end((done[t] != 0) & (((info[t] >> 8) & 0xFF) > 0))
-        if after:
-            hit |= end(masks[after][t])
+        for k in after:
+            hit |= end(masks[k][t], k)
     assert np.array_equal(games[valid], np.full(valid.sum(), G)), "the replay lost a game"
     return hit
 
@@ -54,10 +56,13 @@ def check_fired(mode, out, res, group, G):
     fired = {}
     if "luck" in mode:
         fired["luck"] = bool(out[3][:, 0].any())
-    if mode in ("bearoff", "bearoff1", "cube_bearoff"):
-        fired["cut"] = bool(out[-1][:, 0].sum() > 0) and bool(tr["cut"].any())
+    tmask = "ctrunc" if "cube" in mode else "trunc"          # the horizon cut's mask, where the mode has one
+    if "bearoff" in mode:
+        cut_tally = out[4] if "truncate" in mode else out[-1]
+        fired["cut"] = bool(cut_tally[:, 0].sum() > 0) and bool(tr["cut"].any())
         fired["cut0"] = bool(tr["cut0"].any())
-        fired["retired"] = bool(retired_in(tr, group, G, "cut0", "cube_mask" if "cube" in mode else None, "cut").any())
+        after = ("cut", tmask) if "truncate" in mode else "cut"
+        fired["retired"] = bool(retired_in(tr, group, G, "cut0", "cube_mask" if "cube" in mode else None, after).any())
     if "cube" in mode:
         ct = out[3].cpu().numpy()
         fired["double"] = bool(ct[:, CUBE_FIELDS.index("doubles")].sum() > ct[:, CUBE_FIELDS.index("pass_games")].sum())
@@ -65,8 +70,11 @@ def check_fired(mode, out, res, group, G):
     if mode == "cube":
         fired["retired"] = bool(retired_in(tr, group, G, None, "cube_mask", None).any())
     if "truncate" in mode:
-        fired["trunc"] = bool(out[-1][:, 0].sum() > 0) and bool(out[0][:, 0].sum() > 0)
-        fired["retired"] = bool(retired_in(tr, group, G, None, None, "trunc").any())
+        fired["trunc"] = bool(out[-1][:, 0].sum() > 0) and bool(tr[tmask].any())
+        fired["natural"] = bool(out[0][:, 0].sum() > 0)         # beside them, games played to the end
+        fired["retired_trunc"] = bool(retired_in(tr, group, G, "cut0" if "bearoff" in mode else None,
+                                                 "cube_mask" if "cube" in mode else None,
+                                                 ("cut", tmask) if "bearoff" in mode else tmask, only=tmask).any())
     assert all(fired.values()), f"{mode}: did not fire: {fired}"
     return fired
 

@@ -1,4 +1,4 @@
-"""Warm ms/step of Rollout.run_lanes in its eight modes, on two built trees alternately:
+"""Warm ms/step of Rollout.run_lanes in its ten modes, on two built trees alternately:
 
     python tools/rollout_modes_time.py PARENT_TREE [--runs 5] [--steps 100] [--out FILE.jsonl]
 
@@ -20,7 +20,8 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = "mlp-ppo-2ply-p3_amd"
-MODES = ("plain", "luck", "bearoff", "bearoff1", "cube", "cube_bearoff", "truncate", "truncate_luck")
+MODES = ("plain", "luck", "bearoff", "bearoff1", "cube", "cube_bearoff", "truncate", "truncate_luck", "cube_truncate",
+         "cube_bearoff_truncate")
 B = 65536
 
 
@@ -30,7 +31,7 @@ def child(tree, mode, steps):
     import torch
     from bgx.arena import RandomPlayer
     from bgx.bearoff import BearoffDB, CubefulBearoffDB, OneSidedBearoffDB
-    from bgx.cube import CubeRule
+    from bgx.cube import CubeRule, CubeTruncation
     from bgx.policy import PolicyNet
     from bgx.rollout import Rollout, opening_record
     from bgx.search import ValueHead
@@ -41,7 +42,10 @@ def child(tree, mode, steps):
     kw = {"plain": {}, "luck": dict(luck=vh), "bearoff": lambda: dict(bearoff=BearoffDB(6)),
           "bearoff1": lambda: dict(bearoff=OneSidedBearoffDB(15)), "cube": rule,
           "cube_bearoff": lambda: dict(rule, cube_bearoff=CubefulBearoffDB(BearoffDB(6))),
-          "truncate": dict(truncate=Truncation(vh, 8)), "truncate_luck": dict(truncate=Truncation(vh, 8), luck=vh)}[mode]
+          "truncate": dict(truncate=Truncation(vh, 8)), "truncate_luck": dict(truncate=Truncation(vh, 8), luck=vh),
+          "cube_truncate": dict(rule, cube_truncate=CubeTruncation(vh, 8)),
+          "cube_bearoff_truncate": lambda: dict(rule, cube_bearoff=CubefulBearoffDB(BearoffDB(6)),
+                                                cube_truncate=CubeTruncation(vh, 8))}[mode]
     kw = kw() if callable(kw) else kw
     rng = np.random.RandomState(3)
     starts = np.zeros((B, 64), np.uint8)
