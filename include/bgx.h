@@ -331,6 +331,16 @@ int bgx_two_ply_topk(bgx_engine* e, const float* vpacked_dev, int32_t hidden, fl
 int bgx_roll_luck(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float value_bias,
                   const uint8_t* lane_sel_dev, float* luck_out, float* mean_out, uint64_t* stats_host, void* stream);
 
+/* bgx_roll_luck's 21 values themselves (the cubeful luck needs them, as Janowski's
+ * equity is piecewise linear in v): values_out float[B][21], values_out[i][r] = v_r above for the
+ * 21 rolls r in bgx_two_ply's order, on the lanes with lane_sel_dev[i] != 0 (NULL = every lane);
+ * the other lanes' rows are not written.  The fp32 FMA chain over a row is bgx_roll_luck's
+ * mean_out[i] bit for bit, and v_(the lane's own roll) - mean its luck_out[i].  In every other
+ * respect the contract is bgx_roll_luck's: ordering, the synchronisation, stats_host, an all-zero
+ * selection, and BGX_EINVAL for a NULL engine, pack or values_out, or hidden out of range. */
+int bgx_roll_values(bgx_engine* e, const float* vpacked_dev, int32_t hidden, float value_bias,
+                    const uint8_t* lane_sel_dev, float* values_out, uint64_t* stats_host, void* stream);
+
 /* The static value of lane records (the value a truncated rollout scores a game
  * with).  records_dev = uint8[n][64] lane records, 16-byte aligned (the engine's, or any copy);
  * vpacked_dev the ordinary bgx_value_pack pack, every hidden with bgx_value_packed_size >= 0.
@@ -981,6 +991,72 @@ int bgx_rollout_cube_trunc_cut(const uint8_t* records_dev, const uint8_t* starts
                                int32_t* plies_dev, uint8_t* sel_dev, int64_t* cube_trunc_tally_dev, int64_t* active_dev,
                                uint8_t* reset_mask_out, int32_t cap, int32_t jacoby, const uint8_t* cube0_dev,
                                uint8_t* cube_dev, void* stream);
+
+/* ---- luck of cubeful rollouts (csrc/bg_cube_luck.h; bgx/cube.py, bgx/rollout.py; DESIGN.md §18;
+ * no counterpart in the reference) ----
+ * The luck adjustment of bgx_rollout_luck_* for games with a cube.  Everything per roll is in
+ * units of the lane's current cube and from the view of the side on roll m (record byte 52).
+ * bgx_cube_roll_luck: one thread per 64-byte record, 256 per block.  values21 float[n][21] =
+ * bgx_roll_values' v_r; cube uint8[n] (NULL: centred at 1 everywhere), read as every cube kernel
+ * reads it; sel uint8[n] (NULL: every lane).  After m plays roll r its opponent is on roll with
+ * the same cube, before its own cube decision, so with the rule of bgx_cube_janowski
+ *   g_r  = -e  of  (cube byte, cap, side on roll 1 - m, scale, value -v_r, life, jacoby)
+ *   mean = fma(p_20, g_20, ... fma(p_0, g_0, 0)) in fp32, p_r = 1/36 for doubles, else 2/36
+ *   luck = g_(the record's roll, bytes 53, 54) - mean in fp32   (0 when they hold no roll)
+ * (the two negations are exact).  A selected record that is not game_over writes luck_out[i]
+ * and, when it is given, mean_out[i]; other lanes are not written.  g is a fixed function of the
+ * position after the roll and of the cube, which is known before the roll, so the luck has mean
+ * zero given the history whatever the net, the life or the scale.  BGX_EINVAL for n <= 0, a NULL
+ * records, values21 or luck_out, cap outside 0..10, a life outside its ranges or a NaN scale.
+ *
+ * The bookkeeping, beside bgx_rollout_cube_*'s state: lane_luck float[n] (the running sum of the
+ * lane's current game, in POINTS) and cube_luck_tally int64[n_groups][5]
+ * (bgx_rollout_cube_luck_field), both zeroed by the caller.  A game's luck L is the fp32 sum in
+ * step order of s * 2^k * luck, s = +1 when the step's mover is the start record's mover, else
+ * -1, k the lane's cube AFTER that step's cube decision (the product with 2^k is exact).  When
+ * the game is booked, Lq = llrintf(L * 65536) clamped to +-2^31, 0 when not finite, and with y the
+ * game's cubeful result in points from the start mover's side, row group[i] gets
+ *   LUCK += Lq, LUCK2_LO += Lq^2 & (2^30 - 1), LUCK2_HI += Lq^2 >> 30, YLUCK += y * Lq,
+ *   LUCK_GAMES += 1.
+ * |y| <= 3 * 2^10, so |y Lq| < 2^43 and Lq^2 <= 2^62: a row holds 2^20 games at the clamp.
+ * bgx_rollout_cube_luck_pass: BEFORE bgx_rollout_cube_decide, with the same dsel, equity, rule
+ * and cube.  It evaluates the decision exactly as that call will; a lane with dsel[i] != 0 and a
+ * valid group whose double is passed books its game against y = +-2^k (the doubler wins) and
+ * gets lane_luck[i] = 0.  Nothing else is written: the decision itself stays with cube_decide.
+ * bgx_rollout_cube_luck_add: after cube_decide and the masked bgx_reset, before the players act,
+ * with luck_dev = bgx_cube_roll_luck's luck_out for the lanes as they stand.  Every lane with
+ * sel[i] != 0, except bgx_rollout_luck_add's first step of a game whose start record fixed the
+ * roll: lane_luck[i] += records[i][52] == starts[i][52] ? ldexp(luck[i], k) : -ldexp(luck[i], k).
+ * bgx_rollout_cube_luck_flush: after bgx_step and BEFORE bgx_rollout_cube_flush (which puts the
+ * starting cube back), with the step's done and info.  A lane with sel[i] != 0, a valid group
+ * and a game that bgx_rollout_advance counts books it against y = +-(score << k), score 1 under
+ * the Jacoby rule while k = 0 (bgx_rollout_cube_flush's result), and gets lane_luck[i] = 0; any
+ * other done of a selected lane only zeroes lane_luck[i].
+ * LUCK_GAMES equals BGX_ROLLOUT_CUBE_GAMES of the row.  One thread per lane, the sums combined
+ * per wave and group before the 64-bit atomics; integers, so run-to-run identical.  No
+ * allocation and no synchronisation: graph-capturable.  BGX_EINVAL for n <= 0, n_groups <= 0,
+ * cap outside 0..10, a rule bgx_rollout_cube_decide rejects, or a NULL pointer. */
+enum bgx_rollout_cube_luck_field {
+    BGX_ROLLOUT_CUBE_LUCK = 0,         /* sum of Lq (2^-16 points) */
+    BGX_ROLLOUT_CUBE_LUCK2_LO = 1,     /* sum of Lq^2 & (2^30 - 1) */
+    BGX_ROLLOUT_CUBE_LUCK2_HI = 2,     /* sum of Lq^2 >> 30: sum Lq^2 = LUCK2_HI 2^30 + LUCK2_LO (2^-32) */
+    BGX_ROLLOUT_CUBE_YLUCK = 3,        /* sum of y * Lq (2^-16), y in points */
+    BGX_ROLLOUT_CUBE_LUCK_GAMES = 4    /* games booked: equals BGX_ROLLOUT_CUBE_GAMES of the row */
+};
+int bgx_cube_roll_luck(const uint8_t* records_dev, const uint8_t* cube_dev_or_null, const float* values21_dev,
+                       int32_t n, float scale, bgx_cube_life life, int32_t cap, int32_t jacoby,
+                       const uint8_t* sel_or_null, float* luck_out, float* mean_out_or_null, void* stream);
+int bgx_rollout_cube_luck_add(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* plies_dev,
+                              const uint8_t* sel_dev, const uint8_t* cube_dev, const float* luck_dev, int32_t n,
+                              int32_t cap, float* lane_luck_dev, void* stream);
+int bgx_rollout_cube_luck_pass(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev,
+                               const uint8_t* dsel_dev, const float* equity_dev, int32_t n, int32_t n_groups,
+                               bgx_cube_rule rule, const uint8_t* cube_dev, float* lane_luck_dev,
+                               int64_t* cube_luck_tally_dev, void* stream);
+int bgx_rollout_cube_luck_flush(const uint8_t* starts_dev, const int32_t* group_dev, const uint8_t* sel_dev,
+                                const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
+                                int32_t cap, int32_t jacoby, const uint8_t* cube_dev, float* lane_luck_dev,
+                                int64_t* cube_luck_tally_dev, void* stream);
 
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row

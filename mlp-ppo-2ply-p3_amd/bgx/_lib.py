@@ -72,6 +72,7 @@ SIGNATURES = {
     "bgx_two_ply_sel": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
     "bgx_two_ply_topk": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P, _P]),
     "bgx_roll_luck": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P, _P]),
+    "bgx_roll_values": (ctypes.c_int, [_P, _P, _I32, ctypes.c_float, _P, _P, _P, _P]),
     "bgx_value_lanes": (ctypes.c_int, [_P, _I32, _P, _I32, ctypes.c_float, _P, _P, _P]),
     "bgx_two_ply_timings": (ctypes.c_int, [_P, _P]),
     "bgx_arena_begin": (ctypes.c_int, [_P, _I32, _I32, _P, _P, _P, _P, _P]),
@@ -118,6 +119,10 @@ SIGNATURES = {
     "bgx_cube_janowski": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.c_float, BgxCubeLife, _I32, _I32, _P, _P, _P, _P]),
     "bgx_rollout_cube_trunc_cut": (ctypes.c_int, [_P, _P, _P, _P, _P, ctypes.c_float, BgxCubeLife, _I32, _I32, _I32, _P,
                                                   _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "bgx_cube_roll_luck": (ctypes.c_int, [_P, _P, _P, _I32, ctypes.c_float, BgxCubeLife, _I32, _I32, _P, _P, _P, _P]),
+    "bgx_rollout_cube_luck_add": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "bgx_rollout_cube_luck_pass": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, BgxCubeRule, _P, _P, _P, _P]),
+    "bgx_rollout_cube_luck_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),

@@ -9,12 +9,15 @@ exact cubeful expectation instead (cube_bearoff=; summarize_cube_bearoff).  A cu
 also stop at a horizon and count Janowski's cube-life equity of the position reached, formed from
 a net's cubeless value (cube_truncate= a CubeTruncation; CubeLife; summarize_cube_truncated;
 DESIGN.md §17; csrc/bg_cube_trunc.h); static_cube_decision is the same rule per lane with no
-rollout, janowski_points its decision points.
+rollout, janowski_points its decision points.  The luck adjustment of cubeful games (cube_luck= a
+CubeLuck; summarize_cube_luck; csrc/bg_cube_luck.h) takes the dice noise out of the
+cubeful estimate: the luck of a roll is Janowski's equity after it minus its mean over the 21 rolls.
 
     python -m bgx.rollout --net ckpt.pt --player 1ply --positions opening --trials 1296 --cube
     python -m bgx.rollout --net ckpt.pt --player 1ply --positions pos.json --cube --cube-decision
     python -m bgx.rollout --net ckpt.pt --player 2ply --top-k 4 --positions pos.json --cube --cube-decision \\
         --cube-truncate 8 --cube-life 0.68
+    python -m bgx.rollout --net ckpt.pt --player 2ply --top-k 4 --positions pos.json --cube --cube-decision --cube-luck
 """
 from __future__ import annotations
 
@@ -27,8 +30,9 @@ import torch
 from . import _lib
 from ._lib import check
 from .replay import R_CUR, LaneReplay, split_sq
-from .tally import (CUBE_CUT_FIELDS, CUBE_CUT_ONE, CUBE_CUT_SPLIT, CUBE_FIELDS, CUBE_TRUNC_FIELDS,  # noqa: F401
-                    CUBE_TRUNC_ONE, summarize_cube, summarize_cube_bearoff, summarize_cube_truncated)
+from .tally import (CUBE_CUT_FIELDS, CUBE_CUT_ONE, CUBE_CUT_SPLIT, CUBE_FIELDS, CUBE_LUCK_FIELDS,  # noqa: F401
+                    CUBE_TRUNC_FIELDS, CUBE_TRUNC_ONE, summarize_cube, summarize_cube_bearoff, summarize_cube_luck,
+                    summarize_cube_truncated)
 from .truncate import Truncation
 
 MAX_CAP = 10
@@ -181,7 +185,7 @@ def decide_reference(cube, mover, equity, rule: CubeRule):
 
 
 def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rule: CubeRule, cube0=None,
-                   cut_lookup=None, cube_truncate=None) -> dict:
+                   cut_lookup=None, cube_truncate=None, cube_luck: bool = False) -> dict:
     """A traced cube run replayed on the host with the kernels' arithmetic (include/bgx.h
     bgx_rollout_cube_*).  `trace`: run_lanes' with cube_mover, cube_equity, done and info
     [steps, B]; the lane records are taken as not game_over, which holds between the steps of an
@@ -190,7 +194,8 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
     active int).  `cut_lookup` (cube_bearoff_cut_reference's `lookup`): the run was cut at the
     cubeful bearoff table (run_lanes' cube_bearoff=) -- the cut is replayed after begin on the
     trace's cut_records0 and after every step on cut_records[t]; the result gains cut_tally
-    int64[P, 6], cut0 bool[B] and cut bool[steps, B].  `cube_truncate`: cube_trunc_reference."""
+    int64[P, 6], cut0 bool[B] and cut bool[steps, B].  `cube_truncate`: cube_trunc_reference.
+    `cube_luck`: cube_luck_reference."""
     def host(x):
         return np.asarray(torch.as_tensor(x).cpu())
     mover, equity = host(trace["cube_mover"]), host(trace["cube_equity"]).astype(np.float32)
@@ -206,6 +211,10 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
         rp.tally("cut_tally", CUBE_CUT_FIELDS)
         cuts = np.zeros((T, B), bool)
         cut0 = _table_cut(rp, host(trace["cut_records0"]), cut_lookup, rp.sel)
+    if cube_luck:
+        rp.tally("cube_luck_tally", CUBE_LUCK_FIELDS)
+        lk, lmover = host(trace["cube_luck"]).astype(np.float32), host(trace["cube_luck_mover"])
+        lstates, lsels = np.zeros((T, B), np.uint8), np.zeros((T, B), bool)
     if cube_truncate is not None:
         rp.tally("cube_trunc_tally", CUBE_TRUNC_FIELDS)
         tval, tmover = host(trace["ctrunc_value"]).astype(np.float32), host(trace["ctrunc_mover"])
@@ -213,6 +222,9 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
     for t in range(T):
         states[t] = rp.cube
         dsels[t], masks[t] = rp.decide(mover[t], *decide_reference(rp.cube, mover[t], equity[t], rule))
+        if cube_luck:
+            lstates[t], lsels[t] = rp.cube, rp.sel
+            rp.cube_luck_add(lk[t], lmover[t])
         rp.advance(done[t], info[t])
         if cut_lookup is not None:
             cuts[t] = _table_cut(rp, host(trace["cut_records"][t]), cut_lookup, rp.sel)
@@ -229,12 +241,14 @@ def cube_reference(trace, starts, group, n_groups: int, games_per_lane: int, rul
         out.update(cut0=cut0, cut=cuts)
     if cube_truncate is not None:
         out.update(ctrunc=tcuts, ctrunc_cube=tstates)
+    if cube_luck:
+        out.update(cube_luck_state=lstates, cube_luck_sel=lsels, lane_luck=rp.luck)
     return out
 
 
 def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, cube=(0, CENTRED),
                           first_roll: str = "stratified", max_steps: int = 4000, cube_bearoff=None,
-                          cube_truncate=None) -> dict:
+                          cube_truncate=None, cube_luck=None, cube_luck_scale="fit") -> dict:
     """"Double or not, take or pass?" for the side on roll in `record` (uint8[64]: board and
     mover), holding the cube `cube` = (k, owner) with access to it.  The position is rolled out
     twice in one run, as two groups over the same start records: "no double", with the cube as
@@ -246,7 +260,11 @@ def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, 
     bearoff.CubefulBearoffDB): both rollouts are cut at the cubeful table
     (Rollout.run); for a position in the table that is the exact answer, the table's nd and DT at
     the cut's 2^-20 resolution, with standard errors of 0.  `cube_truncate` (a CubeTruncation;
-    DESIGN.md §17): both rollouts are truncated at its horizon and scored by Janowski's rule."""
+    DESIGN.md §17): both rollouts are truncated at its horizon and scored by Janowski's rule.
+    `cube_luck` (a CubeLuck), with `cube_luck_scale` (Rollout.run): both rollouts are
+    luck-adjusted; the result gains `no_double_luck` and `double_take_luck` with their `_stderr`,
+    from the adjusted equities, and `double_luck` / `take_luck`, the verdict by them.  The
+    existing keys keep their meaning: they are the raw estimates of the same games."""
     rec = torch.as_tensor(record).reshape(-1)
     if rec.numel() != 64 or rec.dtype != torch.uint8:
         raise ValueError("rollout_cube_decision: record must be 64 bytes (uint8)")
@@ -258,10 +276,16 @@ def rollout_cube_decision(rollout, player, record, trials: int, rule: CubeRule, 
     pos = torch.stack([rec.cpu(), rec.cpu()])
     res = rollout.run(player, pos, trials, first_roll=first_roll, max_steps=max_steps, cube=rule,
                       cube_start=[(k, owner), (k + 1, 2 - mover)], cube_bearoff=cube_bearoff,
-                      cube_truncate=cube_truncate)
+                      cube_truncate=cube_truncate, cube_luck=cube_luck, cube_luck_scale=cube_luck_scale)
     unit = float(1 << k)
     nd, dt = res[0]["equity_cubeful"] / unit, res[1]["equity_cubeful"] / unit
-    return dict(no_double=nd, no_double_stderr=res[0]["equity_cubeful_stderr"] / unit,
+    adjusted = {}
+    if cube_luck is not None:
+        ndl, dtl = res[0]["equity_cubeful_luck"] / unit, res[1]["equity_cubeful_luck"] / unit
+        adjusted = dict(no_double_luck=ndl, no_double_luck_stderr=res[0]["equity_cubeful_luck_stderr"] / unit,
+                        double_take_luck=dtl, double_take_luck_stderr=res[1]["equity_cubeful_luck_stderr"] / unit,
+                        double_luck=bool(min(dtl, 1.0) > ndl), take_luck=bool(dtl <= 1.0))
+    return dict(adjusted, no_double=nd, no_double_stderr=res[0]["equity_cubeful_stderr"] / unit,
                 double_take=dt, double_take_stderr=res[1]["equity_cubeful_stderr"] / unit,
                 double_pass=1.0, double_pass_stderr=0.0, double=bool(min(dt, 1.0) > nd), take=bool(dt <= 1.0),
                 cube=[k, owner], rollouts=res)
@@ -298,6 +322,29 @@ class CubeTruncation(Truncation):
         if not isinstance(life, CubeLife):
             raise ValueError("CubeTruncation: life must be a cube.CubeLife")
         self.life = life
+
+
+class CubeLuck:
+    """The luck adjustment of cubeful rollouts (run_lanes' cube_luck=, with cube=; DESIGN.md §18;
+    csrc/bg_cube_luck.h).  Every step takes the 21 per-roll values of the active lanes under
+    `value` (a search.ValueHead; search.roll_values), turns each into Janowski's cube-life equity
+    of the position after the roll -- the opponent on roll with the lane's cube, `scale` points
+    per unit of the value, `life` a CubeLife -- and adds the drawn roll's equity minus the mean
+    over the 21 rolls, times the cube, to the game's luck.  That luck has mean zero whatever the
+    net, the life or the scale, so they only decide how much variance it removes.  The cap and the
+    Jacoby rule are the CubeRule's."""
+
+    def __init__(self, value, scale: float = 1.0, life: CubeLife = None):
+        from .search import ValueHead
+        if not isinstance(value, ValueHead):
+            raise ValueError("CubeLuck: value must be a search.ValueHead")
+        if isinstance(scale, bool) or not isinstance(scale, (int, float, np.floating, np.integer)) or math.isnan(float(scale)):
+            raise ValueError(f"CubeLuck: scale must be a number, got {scale!r}")
+        life = CubeLife() if life is None else life
+        if not isinstance(life, CubeLife):
+            raise ValueError("CubeLuck: life must be a cube.CubeLife")
+        self.value, self.scale, self.life = value, float(scale), life
+        self.totals = {"calls": 0, "rows": 0, "leaves": 0}      # roll_values calls so far, their lanes and leaves
 
 
 def gammon_values(summary) -> tuple:
@@ -382,6 +429,64 @@ def cube_trunc_fixed_reference(e, start_mover_on_roll, k):
         y = (np.where(start_mover_on_roll, np.asarray(e, f), -np.asarray(e, f)).astype(f) * f(CUBE_TRUNC_ONE)).astype(f)
     y = np.where(np.isnan(y), f(0), np.clip(y, -3.0 * CUBE_TRUNC_ONE, 3.0 * CUBE_TRUNC_ONE))
     return np.rint(y).astype(np.int64) * (np.int64(1) << np.asarray(k).astype(np.int64))
+
+
+ROLL_P = np.asarray([1 if a == b else 2 for a in range(1, 7) for b in range(a, 7)], np.float32) / np.float32(36)
+
+
+def roll_index(roll) -> np.ndarray:
+    """The index of the rolls (d0, d1) [n, 2] among the 21 rolls (1-1, 1-2, ..., 6-6); -1: no roll."""
+    d = np.asarray(roll).astype(np.int64).reshape(-1, 2)
+    lo, hi = d.min(axis=1), d.max(axis=1)
+    return np.where((lo >= 1) & (hi <= 6), 7 * (lo - 1) - (lo - 1) * lo // 2 + hi - lo, -1)
+
+
+def fma32(a, b, c) -> np.ndarray:
+    """fp32 fma(a, b, c) of finite float32 arrays, rounded once: the product is exact in fp64, the
+    sum is formed in fp64 rounded to odd (the error of the fp64 sum, by two-sum, decides the last
+    bit), and 53 >= 24 + 2 bits make the final rounding to fp32 that of the exact value."""
+    p = np.asarray(a, np.float32).astype(np.float64) * np.asarray(b, np.float32).astype(np.float64)
+    c = np.broadcast_to(np.asarray(c, np.float32).astype(np.float64), p.shape)
+    s = p + c
+    bb = s - p
+    err = (p - (s - bb)) + (c - bb)
+    nudge = (err != 0) & ((np.ascontiguousarray(s).view(np.int64).reshape(s.shape) & 1) == 0)
+    toward = np.where(err > 0, np.inf, -np.inf)
+    return np.where(nudge, np.nextafter(s, toward), s).astype(np.float32)
+
+
+def cube_roll_luck_reference(values21, cube, mover, roll, scale: float, life: CubeLife, cap: int, jacoby: bool = False):
+    """cube_roll_luck of csrc/bg_cube_luck.h (bgx_cube_roll_luck without the lane selection) on
+    arrays in numpy float32, bit for bit: (luck f32[n], mean f32[n]) for the per-roll values
+    `values21` f32[n, 21] of the movers `mover` (record byte 52) holding the rolls `roll` uint8[n, 2]
+    (bytes 53, 54) with the cube bytes `cube` (None: centred at 1).  g_r = -e of janowski_reference
+    with the opponent on roll and the value -v_r; the mean is the fp32 FMA chain over r = 0..20,
+    each step formed exactly and rounded once (fma32); luck = g of the roll - mean, 0 without a roll."""
+    f = np.float32
+    v = np.asarray(values21, f).reshape(-1, 21)
+    n = v.shape[0]
+    m = np.asarray(mover).reshape(-1).astype(np.int64) & 1
+    g = np.empty((n, 21), f)
+    for r in range(21):
+        g[:, r] = -janowski_reference(-v[:, r], cube, 1 - m, scale, life, cap, jacoby)[0][:, 2]
+    mean = np.zeros(n, f)
+    for r in range(21):
+        mean = fma32(ROLL_P[r], g[:, r], mean)
+    idx = roll_index(roll)
+    mine = g[np.arange(n), np.maximum(idx, 0)]
+    return np.where(idx >= 0, (mine - mean).astype(f), f(0)).astype(f), mean
+
+
+def cube_luck_reference(trace, starts, group, n_groups: int, games_per_lane: int, rule: CubeRule, cube0=None) -> dict:
+    """A traced luck-adjusted cubeful run (run_lanes' cube= with cube_luck=) replayed on the host:
+    cube_reference extended by the three bookkeeping steps of include/bgx.h
+    bgx_rollout_cube_luck_*.  A pass books the game's luck before the decision is applied; after
+    the decision (and the masked reset) the trace's cube_luck, times the replay's own cube and
+    signed by cube_luck_mover, joins the selected lanes' sums; a finished game books its luck
+    before the starting cube comes back.  The result gains cube_luck_tally int64[P, 5],
+    cube_luck_state uint8[steps, B] (the cubes the luck was scaled with), cube_luck_sel bool[steps,
+    B] (the lanes selected there) and lane_luck f32[B] (the sums left at the end)."""
+    return cube_reference(trace, starts, group, n_groups, games_per_lane, rule, cube0=cube0, cube_luck=True)
 
 
 def _root(g, lo=0.0, hi=1.0):

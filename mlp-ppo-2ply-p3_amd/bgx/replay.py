@@ -7,7 +7,8 @@ from __future__ import annotations
 
 import numpy as np
 
-from .tally import CUBE_CUT_SPLIT, CUBE_FIELDS, FIELDS, LUCK_CLAMP, LUCK_FIELDS, LUCK_ONE
+from .tally import (CUBE_CUT_SPLIT, CUBE_FIELDS, CUBE_LUCK_CLAMP, CUBE_LUCK_ONE, FIELDS, LUCK_CLAMP, LUCK_FIELDS,
+                    LUCK_ONE)
 
 R_CUR, R_ROLL0 = 52, 53             # the lane record's mover and first roll byte (engine.R_CUR, engine.R_ROLL0)
 
@@ -24,6 +25,15 @@ def luck_q(luck) -> np.ndarray:
     with np.errstate(invalid="ignore", over="ignore"):
         x = (luck * np.float32(LUCK_ONE)).astype(np.float32)
     x = np.where(np.isfinite(x), np.clip(x, -float(LUCK_CLAMP), float(LUCK_CLAMP)), 0.0)
+    return np.rint(x).astype(np.int64)
+
+
+def cube_luck_q(luck) -> np.ndarray:
+    """A cubeful game's fp32 luck sum in points as Lq = rint(fp32(sum * 65536)) (round half even)
+    clamped to +-2^31, 0 when not finite (cube_luck_q of csrc/bg_cube_luck.h)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        x = (np.asarray(luck, np.float32) * np.float32(CUBE_LUCK_ONE)).astype(np.float32)
+    x = np.where(np.isfinite(x), np.clip(x, -float(CUBE_LUCK_CLAMP), float(CUBE_LUCK_CLAMP)), 0.0)
     return np.rint(x).astype(np.int64)
 
 
@@ -89,6 +99,19 @@ class LaneReplay:
         with np.errstate(invalid="ignore", over="ignore"):
             self.luck = np.where(add, (self.luck + np.where(add, signed, np.float32(0))).astype(np.float32), self.luck)
 
+    def cube_luck_add(self, luck, mover):
+        """bgx_rollout_cube_luck_add: luck_add with the roll's luck in units of the lane's cube as it
+        stands (after the step's decision): +-ldexp(luck, k) joins the selected lanes' sums."""
+        with np.errstate(invalid="ignore", over="ignore"):
+            self.luck_add(np.ldexp(np.asarray(luck, np.float32), self.cube_k().astype(np.int32)).astype(np.float32), mover)
+
+    def cube_luck_book(self, lanes, y):
+        """The booking of bgx_rollout_cube_luck_pass / _flush (where the replay has that tally):
+        the `lanes`' luck sums as Lq against their games' results y in points."""
+        if "cube_luck_tally" in self.tallies:
+            lq = cube_luck_q(self.luck)
+            self.add("cube_luck_tally", lanes, (lq, *split_sq(lq), y * lq, 1))
+
     def decide(self, mover, act, nxt, access):
         """bgx_rollout_cube_sel + bgx_rollout_cube_decide with cube.decide_reference's (act, nxt,
         access) of the current cubes: a pass ends the game at the cube's value, a take turns the
@@ -98,6 +121,7 @@ class LaneReplay:
         act = np.where(dsel, act, 0)
         pas, dbl = act == 2, act > 0
         y = np.where(m == (self.start_cur.astype(np.int64) & 1), 1, -1) * (1 << k)
+        self.cube_luck_book(pas, y)             # bgx_rollout_cube_luck_pass runs before the decision is applied
         self.add("cube_tally", pas, (1, y, y * y, k, 1, self.plies, (y > 0).astype(np.int64)))
         self.add("cube_tally", dbl, (1,), first=CUBE_FIELDS.index("doubles"))
         self.cube = np.where(dbl, nxt, self.cube).astype(np.uint8)
@@ -105,8 +129,8 @@ class LaneReplay:
         return dsel, pas
 
     def advance(self, done, info):
-        """The step's end on the selected lanes: bgx_rollout_luck_flush and bgx_rollout_cube_flush
-        (where the replay has those tallies), then bgx_rollout_advance.  A done with a winner is
+        """The step's end on the selected lanes: bgx_rollout_luck_flush, bgx_rollout_cube_luck_flush and
+        bgx_rollout_cube_flush (where the replay has those tallies), then bgx_rollout_advance.  A done with a winner is
         a finished game; any done clears the lane's luck and puts its starting cube back."""
         sel = self.sel
         winner, score = result_of(info)
@@ -116,10 +140,12 @@ class LaneReplay:
         if "luck_tally" in self.tallies:
             lq = luck_q(self.luck)
             self.add("luck_tally", fin, (lq, lq * lq, np.where(won, score, -score) * lq, 1))
-        self.luck = np.where(dn, np.float32(0), self.luck)
         if self.cube is not None:
             k = self.cube_k()
             y = np.where(won, 1, -1) * (np.where(self.jacoby & (k == 0), 1, score) << k)
+            self.cube_luck_book(fin, y)         # bgx_rollout_cube_luck_flush, before the sums are cleared
+        self.luck = np.where(dn, np.float32(0), self.luck)
+        if self.cube is not None:
             self.add("cube_tally", fin, (1, y, y * y, k))
             self.cube = np.where(dn, self.c0, self.cube).astype(np.uint8)
         self.plies = self.plies + sel

@@ -23,7 +23,9 @@ take or pass?" per position; --cube-bearoff K cuts the cubeful games at the cube
 table (bearoff.CubefulBearoffDB), where both the endgame's dice and its cube
 action are replaced by the exact cubeful expectation; --cube-truncate N stops the cubeful games
 after N plies and scores them with Janowski's cube-life equity from a net's value,
-which is what makes --cube-decision affordable with the slow players.  --truncate N: a game that
+which is what makes --cube-decision affordable with the slow players; --cube-luck: the luck-adjusted
+cubeful estimate beside the raw one (cube.summarize_cube_luck), the luck of a roll being
+Janowski's equity after it minus its mean over the 21 rolls, times the cube.  --truncate N: a game that
 has run N plies stops there and is scored by a net's value head (bgx/truncate.py),
 which makes the slow players affordable; with --luck the dice noise of the plies played goes too (summarize_truncated_luck).  The
 estimate then carries the net's own error, which no standard error shows.
@@ -43,10 +45,10 @@ from ._lib import check
 from .arena import PLAYER_KINDS, SYNC_EVERY, TRACE_LIMIT, _stream, load_net, make_player
 from .engine import Engine, R_CUR, R_ROLL0, R_ROLL1, _ptr, validate_starts
 from .replay import LaneReplay
-from .tally import (CUBE_CUT_FIELDS, CUBE_FIELDS, CUBE_TRUNC_FIELDS, CUT_FIELDS, CUT_ONE, FIELDS, LUCK_CLAMP,  # noqa: F401
-                    LUCK_FIELDS, LUCK_ONE, TRUNC_FIELDS, summarize, summarize_bearoff, summarize_cube,
-                    summarize_cube_bearoff, summarize_cube_truncated, summarize_luck, summarize_truncated,
-                    summarize_truncated_luck)
+from .tally import (CUBE_CUT_FIELDS, CUBE_FIELDS, CUBE_LUCK_FIELDS, CUBE_TRUNC_FIELDS, CUT_FIELDS, CUT_ONE,  # noqa: F401
+                    FIELDS, LUCK_CLAMP, LUCK_FIELDS, LUCK_ONE, TRUNC_FIELDS, summarize, summarize_bearoff,
+                    summarize_cube, summarize_cube_bearoff, summarize_cube_luck, summarize_cube_truncated,
+                    summarize_luck, summarize_truncated, summarize_truncated_luck)
 from .truncate import Truncation, truncate_reference  # noqa: F401
 
 ROLLS36 = [(a, b) for a in range(1, 7) for b in range(1, 7)]       # the 36 ordered rolls
@@ -159,12 +161,23 @@ def _records(positions) -> torch.Tensor:
 
 
 def _check_modes(where: str, luck=None, bearoff=None, cube=None, truncate=None, cube_bearoff=None, cube0=None,
-                 types: bool = False, cube_truncate=None) -> None:
+                 types: bool = False, cube_truncate=None, cube_luck=None) -> None:
     """The combinations of modes that Rollout.run and run_lanes refuse, as ValueError(f"{where}: ...")
     for the first one that applies.  `types` (run_lanes): also what only the lanes can tell --
     a cube_bearoff that is no cubeful table, a truncate that is no Truncation, a cube_truncate that
-    is no CubeTruncation, cube0 without cube -- each at its place in the order.  Nothing here
-    touches the engine or the library."""
+    is no CubeTruncation, a cube_luck that is no CubeLuck, cube0 without cube -- each at its place in
+    the order.  Nothing here touches the engine or the library."""
+    if cube_luck is not None:
+        if cube is None:
+            raise ValueError(f"{where}: cube_luck without cube")
+        for name, other in (("luck", luck), ("bearoff", bearoff), ("truncate", truncate), ("cube_bearoff", cube_bearoff),
+                            ("cube_truncate", cube_truncate)):
+            if other is not None:
+                raise ValueError(f"{where}: cube_luck together with {name} is not supported")
+        if types:
+            from .cube import CubeLuck
+            if not isinstance(cube_luck, CubeLuck):
+                raise ValueError(f"{where}: cube_luck must be a cube.CubeLuck")
     if cube_truncate is not None:
         if cube is None:
             raise ValueError(f"{where}: cube_truncate without cube")
@@ -277,11 +290,12 @@ class _CubeStage(_Stage):
     the active-lane count every step, as the equity synchronises.  Result: cube_tally
     int64[n_groups, 8] (cube.CUBE_FIELDS); the trace gains per step cube uint8 (the state before
     the decision), cube_mover (the side on roll there), cube_dsel (the lanes that may double),
-    cube_equity (NaN off cube_dsel) and cube_mask (the passes)."""
+    cube_equity (NaN off cube_dsel) and cube_mask (the passes).  `luck`: the _CubeLuckStage that
+    accompanies it, if any, called before the decision, after the masked reset and before cube_flush."""
 
     def __init__(self, c: _Pass, rule, cube0):
         from .cube import validate_cube0
-        self.c, self.rule = c, rule
+        self.c, self.rule, self.luck = c, rule, None
         self.c0 = (torch.zeros(c.B, dtype=torch.uint8, device=c.dev) if cube0 is None
                    else torch.as_tensor(cube0).to(c.dev).contiguous())
         if self.c0.shape != (c.B,) or self.c0.dtype != torch.uint8:
@@ -310,6 +324,8 @@ class _CubeStage(_Stage):
             tr["cube_mover"][step] = c.rec[:, R_CUR]
             tr["cube_dsel"][step] = self.dsel
             tr["cube_equity"][step] = torch.where(self.dsel != 0, eq, float("nan"))
+        if self.luck is not None:
+            self.luck.before_decide(eq)
         check(c.L.bgx_rollout_cube_decide(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(self.dsel), _ptr(eq), c.B, c.P,
                                           c.G, self.struct, _ptr(self.c0), _ptr(self.state), *c.lanes,
                                           _ptr(self.tally), c.active, _ptr(self.mask), c.stream),
@@ -317,12 +333,74 @@ class _CubeStage(_Stage):
         if tr is not None:
             tr["cube_mask"][step] = self.mask
         c.reset(self.mask)
+        if self.luck is not None:
+            self.luck.after_decide(step)
 
     def after_step(self, done, info):
         c = self.c
+        if self.luck is not None:
+            self.luck.flush(done, info)
         check(c.L.bgx_rollout_cube_flush(_ptr(c.starts), _ptr(c.grp), c.lanes[2], _ptr(done), _ptr(info), c.B, c.P,
                                          self.struct, _ptr(self.c0), _ptr(self.state), _ptr(self.tally), c.stream),
               "bgx_rollout_cube_flush")
+
+
+class _CubeLuckStage(_Stage):
+    """`cube_luck` (a cube.CubeLuck), with `cube`: the luck of every roll of a cubeful
+    game, in points, summed per game and booked against the game's cubeful result.  It has no
+    hooks of its own in the loop: the cube stage calls it where the order needs it -- before
+    cube_decide: cube_luck_pass (a passed game's luck is booked while its cube still stands); after
+    the masked reset: roll_values on sel, cube_roll_luck, cube_luck_add (the cube after the
+    decision scales the roll's luck); after the step, before cube_flush: cube_luck_flush.  The
+    games are the same as without it.  Result (after cube_tally): cube_luck_tally int64[n_groups, 5]
+    (CUBE_LUCK_FIELDS); the trace gains per step cube_luck f32 (in units of the lane's cube, NaN on
+    lanes that never were active), cube_luck_state uint8 (the cube after the decision),
+    cube_luck_mover (the side on roll there), cube_luck_roll uint8[.., 2] (its roll) and
+    cube_luck_values f32[.., 21] (roll_values' rows, NaN on lanes that never were active)."""
+
+    def __init__(self, c: _Pass, cl, cube: _CubeStage):
+        self.c, self.cl, self.cube = c, cl, cube
+        self.life = cl.life.struct()
+        self.tally = c.tally(CUBE_LUCK_FIELDS)
+        self.buf, = c.lane_buffers(1, torch.float32, float("nan"))
+        self.values = torch.full((c.B, 21), float("nan"), dtype=torch.float32, device=c.dev)
+        c.ro.lane_luck.zero_()
+        c.traced(("cube_luck", torch.float32), ("cube_luck_state", torch.uint8), ("cube_luck_mover", torch.uint8),
+                 ("cube_luck_roll", torch.uint8, 2), ("cube_luck_values", torch.float32, 21))
+        cube.luck = self
+
+    def before_decide(self, eq):
+        c, cube = self.c, self.cube
+        check(c.L.bgx_rollout_cube_luck_pass(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(cube.dsel), _ptr(eq), c.B, c.P,
+                                             cube.struct, _ptr(cube.state), _ptr(c.ro.lane_luck), _ptr(self.tally),
+                                             c.stream), "bgx_rollout_cube_luck_pass")
+
+    def after_decide(self, step):
+        from .search import roll_values
+        c, cube, rule = self.c, self.cube, self.cube.rule
+        stats = roll_values(c.eng, self.cl.value, sel=c.ro.sel, out=self.values)[1]
+        self.cl.totals["calls"] += 1
+        self.cl.totals["rows"] += stats["rows"]
+        self.cl.totals["leaves"] += stats["leaves"]
+        check(c.L.bgx_cube_roll_luck(c.recs, _ptr(cube.state), _ptr(self.values), c.B, self.cl.scale, self.life,
+                                     rule.cap, int(rule.jacoby), c.lanes[2], _ptr(self.buf), None, c.stream),
+              "bgx_cube_roll_luck")
+        check(c.L.bgx_rollout_cube_luck_add(c.recs, _ptr(c.starts), c.lanes[1], c.lanes[2], _ptr(cube.state),
+                                            _ptr(self.buf), c.B, rule.cap, _ptr(c.ro.lane_luck), c.stream),
+              "bgx_rollout_cube_luck_add")
+        if c.tr is not None:
+            c.eng.records(out=c.rec)
+            c.tr["cube_luck"][step] = self.buf
+            c.tr["cube_luck_state"][step] = cube.state
+            c.tr["cube_luck_mover"][step] = c.rec[:, R_CUR]
+            c.tr["cube_luck_roll"][step] = c.rec[:, R_ROLL0:R_ROLL1 + 1]
+            c.tr["cube_luck_values"][step] = self.values
+
+    def flush(self, done, info):
+        c, cube, rule = self.c, self.cube, self.cube.rule
+        check(c.L.bgx_rollout_cube_luck_flush(_ptr(c.starts), _ptr(c.grp), c.lanes[2], _ptr(done), _ptr(info), c.B, c.P,
+                                              rule.cap, int(rule.jacoby), _ptr(cube.state), _ptr(c.ro.lane_luck),
+                                              _ptr(self.tally), c.stream), "bgx_rollout_cube_luck_flush")
 
 
 class _TableCutStage(_Stage):
@@ -478,7 +556,7 @@ class Rollout:
 
     def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
                   trace: bool = False, luck=None, bearoff=None, cube=None, cube0=None, truncate=None,
-                  cube_bearoff=None, cube_truncate=None):
+                  cube_bearoff=None, cube_truncate=None, cube_luck=None):
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
@@ -496,8 +574,9 @@ class Rollout:
         and after advance:
 
             begin; cube_begin; cut, reset(mask)
-            [ roll_luck, luck_add;  cube_sel, equity, cube_decide, reset(mask);
-              act, merge, step;  luck_flush;  cube_flush;  advance;
+            [ roll_luck, luck_add;  cube_sel, equity, (cube_luck_pass,) cube_decide, reset(mask),
+              (roll_values, cube_roll_luck, cube_luck_add);
+              act, merge, step;  luck_flush;  (cube_luck_flush,) cube_flush;  advance;
               cut, reset(mask);  trunc_sel, value, trunc_cut or cube_trunc_cut, reset(mask) ]
 
         `luck` (a search.ValueHead): the luck of every roll, summed per game -> luck_tally.
@@ -508,6 +587,9 @@ class Rollout:
         table -> cube_tally, cube_cut_tally.
         `cube_truncate` (a cube.CubeTruncation), with `cube`: cubeful games stop at a horizon, scored
         by Janowski's cube-life equity -> cube_tally, [cube_cut_tally,] cube_trunc_tally.
+        `cube_luck` (a cube.CubeLuck), with `cube` alone: the luck of every roll of the cubeful games
+        (the parenthesised calls above, made from inside the cube stage) -> cube_tally,
+        cube_luck_tally.
         Each None: nothing changes; all None: exactly the three results above.
 
         Together: `truncate` with `luck` IS supported (..., luck_tally, trunc_tally;
@@ -516,9 +598,9 @@ class Rollout:
         ValueError (_check_modes): `bearoff` with `luck` needs cross sums that are not kept, the
         luck of a cubeful game and cubeful values of the cubeless table do not exist (`cube` with
         `luck` or `bearoff`), nor do other three-way summaries (`truncate`, `cube_bearoff` or
-        `cube_truncate` with others)."""
+        `cube_truncate` with others; `cube_luck` with anything but `cube`)."""
         _check_modes("run_lanes", luck, bearoff, cube, truncate, cube_bearoff, cube0, types=True,
-                     cube_truncate=cube_truncate)
+                     cube_truncate=cube_truncate, cube_luck=cube_luck)
         max_steps, G, P = int(max_steps), int(games_per_lane), int(n_groups)
         if max_steps < 0 or G < 0 or P <= 0:
             raise ValueError(f"run_lanes: max_steps {max_steps}, games_per_lane {G} must be >= 0, n_groups {P} > 0")
@@ -545,7 +627,8 @@ class Rollout:
         cut_stage = _TableCutStage(c, table, cube_stage) if table is not None else None
         trunc_stage = _TruncStage(c, truncate, luck is not None) if truncate is not None else None
         ctrunc_stage = _CubeTruncStage(c, cube_truncate, cube_stage) if cube_truncate is not None else None
-        stages = [s for s in (luck_stage, cube_stage, cut_stage, trunc_stage, ctrunc_stage) if s is not None]
+        cluck_stage = _CubeLuckStage(c, cube_luck, cube_stage) if cube_luck is not None else None
+        stages = [s for s in (luck_stage, cube_stage, cut_stage, trunc_stage, ctrunc_stage, cluck_stage) if s is not None]
         for s in stages:
             s.after_begin()
         every = SYNC_EVERY if getattr(player, "sync_free", False) and all(s.sync_free for s in stages) else 1
@@ -588,7 +671,7 @@ class Rollout:
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
             trace: bool = False, luck=None, luck_scale="fit", bearoff=None, cube=None, cube_start=(0, 0),
-            truncate=None, cube_bearoff=None, cube_truncate=None):
+            truncate=None, cube_bearoff=None, cube_truncate=None, cube_luck=None, cube_luck_scale="fit"):
         """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
         bytes come from the layout) `trials` times with `player` (any arena player object)
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
@@ -608,8 +691,10 @@ class Rollout:
         DESIGN.md §15), with `cube`: the results are cube.summarize_cube_bearoff's and carry
         `bearoff_kind` = "cubeful".  `cube_truncate` (a cube.CubeTruncation), with
         `cube`: the results are cube.summarize_cube_truncated's (with `cube_bearoff` too, its
-        cut_row= form)."""
-        _check_modes("run", luck, bearoff, cube, truncate, cube_bearoff, cube_truncate=cube_truncate)
+        cut_row= form).  `cube_luck` (a cube.CubeLuck), with `cube` alone: the results are
+        cube.summarize_cube_luck's, with `cube_luck_scale` ("fit" or a float) as its scale."""
+        _check_modes("run", luck, bearoff, cube, truncate, cube_bearoff, cube_truncate=cube_truncate,
+                     cube_luck=cube_luck)
         pos = _records(positions)
         P = pos.shape[0]
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
@@ -627,15 +712,15 @@ class Rollout:
             tally, unf, tr, *extra = self.run_lanes(
                 player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck, bearoff=bearoff, cube=cube,
                 cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None, truncate=truncate,
-                cube_bearoff=cube_bearoff, cube_truncate=cube_truncate)
+                cube_bearoff=cube_bearoff, cube_truncate=cube_truncate, cube_luck=cube_luck)
             sums = [tally, unf] + extra                            # the modes' tallies in run_lanes' order
             totals = sums if totals is None else [a + b for a, b in zip(totals, sums)]
             if trace:
                 tr.update(group=grp, starts=starts, games_per_lane=G)
         self.eng.set_starts(None)
         rows, unf, *extra = (t.cpu().tolist() for t in totals)
-        summary = _summary(luck, bearoff, cube, truncate, cube_bearoff, cube_truncate)
-        scale = () if luck is None else (luck_scale,)
+        summary = _summary(luck, bearoff, cube, truncate, cube_bearoff, cube_truncate, cube_luck)
+        scale = (luck_scale,) if luck is not None else (cube_luck_scale,) if cube_luck is not None else ()
         res = [summary(rows[p], *(e[p] for e in extra), *scale, unf[p]) for p in range(P)]
         table = bearoff if bearoff is not None else cube_bearoff
         if table is not None and table.kind != "two-sided":
@@ -644,10 +729,12 @@ class Rollout:
         return (res, tr) if trace else res
 
 
-def _summary(luck, bearoff, cube, truncate, cube_bearoff, cube_truncate=None):
+def _summary(luck, bearoff, cube, truncate, cube_bearoff, cube_truncate=None, cube_luck=None):
     """The summary of a position's rows by the modes of the run (after _check_modes): a function
-    (tally_row, *the modes' rows in run_lanes' order, [luck_scale with luck,] unfinished)."""
+    (tally_row, *the modes' rows in run_lanes' order, [the scale with luck or cube_luck,] unfinished)."""
     if cube is not None:
+        if cube_luck is not None:
+            return summarize_cube_luck
         if cube_truncate is not None and cube_bearoff is not None:
             return lambda t, c, cut, tr, unf=0: summarize_cube_truncated(t, c, tr, unf, cut_row=cut)
         if cube_truncate is not None:
@@ -779,23 +866,29 @@ def load_positions(path: str) -> torch.Tensor:
     return out
 
 
-def _luck_scale(text: str):
+def _luck_scale(text: str, option: str = "--luck-scale"):
     if text == "fit":
         return text
     try:
         v = float(text)
     except ValueError:
-        raise argparse.ArgumentTypeError(f"--luck-scale takes 'fit' or a number, got {text!r}")
+        raise argparse.ArgumentTypeError(f"{option} takes 'fit' or a number, got {text!r}")
     if not math.isfinite(v):
-        raise argparse.ArgumentTypeError("--luck-scale must be finite")
+        raise argparse.ArgumentTypeError(f"{option} must be finite")
     return v
+
+
+def _cube_luck_scale(text: str):
+    return _luck_scale(text, "--cube-luck-scale")
 
 
 class _Parser(argparse.ArgumentParser):
     """--top-k is an error for any player but a 2ply one with weights; --luck and --cube need
     weights; --cube goes with neither --luck nor a bearoff cut; --truncate needs a net and goes
     with neither a bearoff cut nor --cube; --cube-truncate and its options need --cube and go with
-    none of --luck, --bearoff, --bearoff1 and --truncate."""
+    none of --luck, --bearoff, --bearoff1 and --truncate; --cube-luck and its options need --cube and
+    weights and go with none of --luck, --bearoff, --bearoff1, --truncate, --cube-bearoff and
+    --cube-truncate."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -865,6 +958,26 @@ class _Parser(argparse.ArgumentParser):
             if math.isnan(ns.cube_truncate_scale):
                 self.error("--cube-truncate-scale must be a number")
             for name, lo, hi in (("cube_life", 0.0, 1.0), ("cube_win_value", 1.0, 3.0), ("cube_loss_value", 1.0, 3.0)):
+                if not lo <= getattr(ns, name) <= hi:
+                    self.error(f"--{name.replace('_', '-')} takes a number in [{lo:g}, {hi:g}]")
+        if not ns.cube_luck:
+            if (ns.cube_luck_net is not None or ns.cube_luck_scale != "fit" or ns.cube_luck_life != 0.68
+                    or ns.cube_luck_win_value != 1.0 or ns.cube_luck_loss_value != 1.0 or ns.cube_luck_value_scale != 1.0):
+                self.error("--cube-luck-net, --cube-luck-scale, --cube-luck-life, --cube-luck-win-value, "
+                           "--cube-luck-loss-value and --cube-luck-value-scale need --cube-luck")
+        else:
+            if not ns.cube:
+                self.error("--cube-luck needs --cube")
+            if ns.net == "random" and ns.cube_luck_net is None:
+                self.error("--cube-luck needs --net with weights or --cube-luck-net (the luck is measured by a net's "
+                           "value head)")
+            for name in ("luck", "bearoff", "bearoff1", "truncate", "cube_bearoff", "cube_truncate"):
+                if getattr(ns, name) not in (None, False):
+                    self.error(f"--cube-luck and --{name.replace('_', '-')} cannot be combined")
+            if math.isnan(ns.cube_luck_value_scale):
+                self.error("--cube-luck-value-scale must be a number")
+            for name, lo, hi in (("cube_luck_life", 0.0, 1.0), ("cube_luck_win_value", 1.0, 3.0),
+                                 ("cube_luck_loss_value", 1.0, 3.0)):
                 if not lo <= getattr(ns, name) <= hi:
                     self.error(f"--{name.replace('_', '-')} takes a number in [{lo:g}, {hi:g}]")
         if ns.trials < 1 or ns.batch < 1:
@@ -946,6 +1059,23 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cube-truncate-net", default=None, metavar="PATH",
                     help="the state_dict whose value head scores the truncated games (default: --cube-net if "
                          "given, else the player's net)")
+    ap.add_argument("--cube-luck", action="store_true",
+                    help="with --cube: the luck-adjusted (variance-reduced) cubeful estimate, the luck of a roll "
+                         "being Janowski's cube-life equity after it minus its mean over the 21 rolls; needs weights; "
+                         "not with --luck, --bearoff, --bearoff1, --truncate, --cube-bearoff or --cube-truncate")
+    ap.add_argument("--cube-luck-net", default=None, metavar="PATH",
+                    help="the state_dict whose value head measures the luck (default: --cube-net if given, else "
+                         "the player's net)")
+    ap.add_argument("--cube-luck-scale", type=_cube_luck_scale, default="fit",
+                    help="'fit' (the control-variate coefficient of the games) or a fixed number")
+    ap.add_argument("--cube-luck-life", type=float, default=0.68, metavar="X",
+                    help="the cube life of the luck's equity in [0, 1]: 0 is the cubeless luck times the cube")
+    ap.add_argument("--cube-luck-win-value", type=float, default=1.0, metavar="W",
+                    help="mean points of a won game in [1, 3]")
+    ap.add_argument("--cube-luck-loss-value", type=float, default=1.0, metavar="L",
+                    help="mean points of a lost game in [1, 3]")
+    ap.add_argument("--cube-luck-value-scale", type=float, default=1.0, metavar="S",
+                    help="points per unit of the net's value")
     ap.add_argument("--cube-decision", action="store_true",
                     help="per position: no double / double, take / double, pass for the side on roll with a "
                          "centred cube, and the verdict")
@@ -1012,18 +1142,29 @@ def main(argv=None):
                                 life=CubeLife(args.cube_life, args.cube_win_value, args.cube_loss_value))
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
+    cluck = None
+    if args.cube_luck:
+        from .cube import CubeLife, CubeLuck
+        from .search import ValueHead
+        lnet = args.cube_luck_net if args.cube_luck_net is not None else args.cube_net
+        cluck = CubeLuck(ValueHead(net if lnet is None else load_net(lnet, dev)), scale=args.cube_luck_value_scale,
+                         life=CubeLife(args.cube_luck_life, args.cube_luck_win_value, args.cube_luck_loss_value))
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
     if args.cube_decision:
         # one line per position: the three equities and the verdict; the summary counts both rollouts' games
         res = []
         for i in range(positions.shape[0]):
             d = rollout_cube_decision(ro, player, positions[i], args.trials, rule, first_roll=args.first_roll,
-                                      max_steps=args.max_steps, cube_bearoff=cdb, cube_truncate=ctrunc)
+                                      max_steps=args.max_steps, cube_bearoff=cdb, cube_truncate=ctrunc,
+                                      cube_luck=cluck, cube_luck_scale=args.cube_luck_scale)
             print(json.dumps(dict(position=i, cube_decision=True, **d)), flush=True)
             res.extend(d["rollouts"])
     else:
         res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, luck=vh,
                      luck_scale=args.luck_scale, bearoff=dbs.get(args.bearoff) or dbs1.get(args.bearoff1), cube=rule,
-                     truncate=trunc, cube_bearoff=cdb, cube_truncate=ctrunc)
+                     truncate=trunc, cube_bearoff=cdb, cube_truncate=ctrunc, cube_luck=cluck,
+                     cube_luck_scale=args.cube_luck_scale)
     dt = time.perf_counter() - t0
     for i, r in enumerate(res if not args.cube_decision else ()):
         print(json.dumps(dict(position=i, **r)), flush=True)
@@ -1066,6 +1207,10 @@ def main(argv=None):
                        cube_loss_value=args.cube_loss_value, cube_truncate_scale=args.cube_truncate_scale,
                        cube_truncate_lookahead=args.cube_truncate_lookahead, cube_truncate_net=args.cube_truncate_net,
                        truncated_games=tg, truncated_share=tg / games if games else 0.0)
+    if cluck is not None:
+        summary.update(cube_luck=True, cube_luck_net=args.cube_luck_net, cube_luck_scale=args.cube_luck_scale,
+                       cube_luck_life=args.cube_luck_life, cube_luck_win_value=args.cube_luck_win_value,
+                       cube_luck_loss_value=args.cube_luck_loss_value, cube_luck_value_scale=args.cube_luck_value_scale)
     print(json.dumps(summary), flush=True)
     return res, summary
 

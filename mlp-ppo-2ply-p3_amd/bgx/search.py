@@ -182,6 +182,27 @@ def roll_luck(eng: Engine, vh: ValueHead, sel: torch.Tensor | None = None, out=N
     return luck, mean, {"leaves": int(stats[0]), "jobs": int(stats[1]), "rows": int(stats[2])}
 
 
+def roll_values(eng: Engine, vh: ValueHead, sel: torch.Tensor | None = None, out: torch.Tensor | None = None):
+    """roll_luck's 21 values themselves (bgx_roll_values): values f32[B, 21],
+    values[i, r] = v_r, the best 1-ply value of lane i's mover for roll r in the 21 rolls' order
+    (V of the position itself when it cannot move).  Returns (values, stats {leaves, jobs,
+    rows}).  `sel` as in roll_luck: only lanes with sel != 0 are computed and written; `out`
+    (float32[B, 21]) keeps the other rows as they were, else they are NaN.  Synchronises the
+    stream, as roll_luck does."""
+    L = _lib.load()
+    B, dev = eng.batch, eng.device
+    _check_sel(eng, sel)
+    if out is None:
+        out = torch.full((B, 21), float("nan"), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev
+          or not out.is_contiguous() or out.shape != (B, 21)):
+        raise ValueError("roll_values: out must be a contiguous float32[B, 21] tensor on the engine's device")
+    stats = (ctypes.c_uint64 * 3)()
+    check(L.bgx_roll_values(eng._h, _ptr(vh.packed), vh.hidden, vh.bias, _ptr(sel), _ptr(out),
+                            ctypes.cast(stats, ctypes.c_void_p), _stream(dev)), "bgx_roll_values")
+    return out, {"leaves": int(stats[0]), "jobs": int(stats[1]), "rows": int(stats[2])}
+
+
 def value_lanes(records, vh: ValueHead, sel: torch.Tensor | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
     """The static value V(enc(X, m)) of lane records under `vh` (bgx_value_lanes):
     the board and the mover (byte 52) of each record, the value head's own output for them --

@@ -33,6 +33,11 @@ CUBE_CUT_SPLIT = 30                 # sum Yq^2 = cut_y2_hi * 2^30 + cut_y2_lo
 CUBE_TRUNC_FIELDS = ("cube_trunc_games", "cube_trunc_plies", "cube_trunc_y", "cube_trunc_y2_lo", "cube_trunc_y2_hi",
                      "cube_trunc_log2")
 CUBE_TRUNC_ONE = 1 << 16            # Yq = rint(q * CUBE_TRUNC_ONE) * 2^k, |q| <= 3
+# cube_luck_tally int64[n_groups][5] (bgx_rollout_cube_luck_field): the luck of cubeful games
+# (DESIGN.md §18), fixed point, 2^-16 points; the squares split as the cut tallies' (CUBE_CUT_SPLIT)
+CUBE_LUCK_FIELDS = ("cube_luck", "cube_luck2_lo", "cube_luck2_hi", "cube_yluck", "cube_luck_games")
+CUBE_LUCK_ONE = 65536               # Lq = rint(L * CUBE_LUCK_ONE), L in points
+CUBE_LUCK_CLAMP = 1 << 31           # |Lq| <= CUBE_LUCK_CLAMP
 
 
 # ------------------------------------------------------------------ what the summaries share --
@@ -249,6 +254,47 @@ def summarize_cube(tally_row, cube_row, unfinished: int = 0) -> dict:
              equity_cubeful_stderr=math.sqrt(var_num / (n * n * (n - 1))) if n > 1 else 0.0,
              unfinished=int(unfinished), played_out=played)
     return _cube_rates(r, n)
+
+
+def summarize_cube_luck(tally_row, cube_row, luck_row, scale="fit", unfinished: int = 0) -> dict:
+    """summarize_cube(tally_row, cube_row, unfinished) plus the luck-adjusted cubeful estimate from
+    the row's 5 luck sums (CUBE_LUCK_FIELDS), with summarize_luck's formulas on y, a
+    game's cubeful result in points (played out and passed games alike), and L, its luck in
+    points (the sum over its rolls of 2^k times the cubeful luck of the roll, signed for the start
+    mover).  E[L] = 0, so any constant c leaves the mean unbiased.  From the integer sums, n =
+    games, sum y = CUBE_POINTS, sum y^2 = CUBE_POINTS2, sum L = LUCK / 2^16, sum L^2 =
+    (LUCK2_HI 2^30 + LUCK2_LO) / 2^32, sum y L = YLUCK / 2^16:
+        equity_cubeful_luck = (sum y - c sum L) / n
+        var_a = (sum y^2 - 2 c sum y L + c^2 sum L^2 - n equity_cubeful_luck^2) / (n - 1), >= 0
+        equity_cubeful_luck_stderr = sqrt(var_a / n)        variance_ratio = var_a / var_y
+    (variance_ratio 1.0 when var_y is 0; n < 2: the stderr is 0).  `scale` = "fit": c = cov(y, L) /
+    var(L) of these games, numerator and denominator as exact integers (0 when var(L) is 0); a
+    float: that fixed c.  Adds luck_scale (c), luck_mean (sum L / n), equity_cubeful_luck,
+    equity_cubeful_luck_stderr, variance_ratio and the 5 sums under their names.  Raises ValueError
+    when the luck row counts other games than the cube row."""
+    r = summarize_cube(tally_row, cube_row, unfinished)
+    k = _row(luck_row, CUBE_LUCK_FIELDS, "summarize_cube_luck: a luck row")
+    n, one = r["games"], CUBE_LUCK_ONE
+    if k[4] != n:
+        raise ValueError(f"summarize_cube_luck: the luck row counts {k[4]} games, the cube row {n}")
+    sy, sy2 = r["cube_points"], r["cube_points2"]
+    il, il2, iyl = k[0], (k[2] << CUBE_CUT_SPLIT) + k[1], k[3]                        # 2^-16, 2^-32, 2^-16
+    if scale == "fit":
+        # numerator (2^-16) and denominator (2^-32) times n, as exact integers: a constant result gives 0
+        num, den = n * iyl - sy * il, n * il2 - il * il
+        c = one * (num / den) if den > 0 else 0.0
+    else:
+        c = float(scale)
+    sl, sl2, syl = il / one, il2 / (one * one), iyl / one
+    inv = 1.0 / n if n > 0 else 0.0
+    eq = (sy - c * sl) * inv
+    raw = r["equity_cubeful"]
+    var_a = max(sy2 - 2.0 * c * syl + c * c * sl2 - n * eq * eq, 0.0) / (n - 1) if n > 1 else 0.0
+    var_y = max(sy2 - n * raw * raw, 0.0) / (n - 1) if n > 1 else 0.0
+    r.update(zip(CUBE_LUCK_FIELDS, k))
+    r.update(luck_scale=c, luck_mean=sl * inv, equity_cubeful_luck=eq, equity_cubeful_luck_stderr=math.sqrt(var_a * inv),
+             variance_ratio=var_a / var_y if var_y > 0.0 else 1.0)
+    return r
 
 
 def _cube_rates(r, n, log2: int = 0, plies: int = 0):

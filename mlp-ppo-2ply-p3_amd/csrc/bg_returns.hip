@@ -298,6 +298,9 @@ extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, floa
 // truncated cubeful rollouts and the static cube evaluator: bg_cube.h's byte decoding, the helpers
 #include "bg_cube_trunc.h"
 
+// luck-adjusted cubeful rollouts: bg_cube_trunc.h's rule per roll, bg_cube.h's decision, the helpers
+#include "bg_cube_luck.h"
+
 // the cubeful exact bearoff table: bg_cube.h's byte decoding, bg_bearoff1.h's records and helpers
 #include "bg_bearoff_cube.h"
 

@@ -1752,6 +1752,18 @@ __global__ __launch_bounds__(256) void k_luck_reduce(Args A, const uint8_t* sel,
     if (mean_out) mean_out[i] = mean;
 }
 
+// bgx_roll_values: the 21 values themselves, values[i][r] = v_r = -minv[row][r]; one thread per
+// (lane, roll), so a wave's stores are contiguous.
+__global__ __launch_bounds__(256) void k_luck_values(Args A, const uint8_t* sel, const int32_t* lane_off,
+                                                     const int64_t* total, const int32_t* minv, float* values) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)A.B * 21) return;
+    const int i = (int)(idx / 21), r = (int)(idx - (int64_t)i * 21);
+    const int row = luck_row(sel, i, lane_off, *total);
+    if (row < 0) return;
+    values[idx] = -unord_f32(minv[(size_t)row * 21 + r]);
+}
+
 }  // namespace
 
 static int value_tiles16(int H) { return (H + 15) / 16; }   // 16 hidden units (hi + lo rows) per MFMA tile
@@ -2196,9 +2208,10 @@ static int two_ply_search(bgx_engine* e, const float* vpacked, int32_t hidden, f
 
 // bgx_roll_luck: the 2-ply stages on rows made from the lanes themselves, with the luck form
 // of the pack (k_luck_pack) behind the 2-ply workspace (LuckLayout).
+// luck_out (with mean_out) and values_out (bgx_roll_values: the 21 values) are each optional; one is given.
 static int roll_luck(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
-                     float* luck_out, float* mean_out, uint64_t* stats_host, void* stream) {
-    if (!e || !vpacked || !luck_out || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
+                     float* luck_out, float* mean_out, float* values_out, uint64_t* stats_host, void* stream) {
+    if (!e || !vpacked || (!luck_out && !values_out) || bgx_value_packed_size(hidden) < 0) return BGX_EINVAL;
     const int NT = value_tiles16(hidden);
     hipStream_t s = (hipStream_t)stream;
     EngineCall call(e, s);
@@ -2233,9 +2246,16 @@ static int roll_luck(bgx_engine* e, const float* vpacked, int32_t hidden, float 
     const SearchCall c{e, s, lpack, hidden, NT, -value_bias, sel};
     const int rc = search_rows(c, L, rows, jobs);
     if (rc != BGX_OK) return rc;
-    hipLaunchKernelGGL(k_luck_reduce, dim3((A.B + 255) / 256), dim3(256), 0, s, A, sel, L.lane_off.at(ws), &ctr->rows,
-                       L.minv.at(ws), luck_out, mean_out);
-    BGX_CK_LAUNCH();
+    if (luck_out) {
+        hipLaunchKernelGGL(k_luck_reduce, dim3((A.B + 255) / 256), dim3(256), 0, s, A, sel, L.lane_off.at(ws),
+                           &ctr->rows, L.minv.at(ws), luck_out, mean_out);
+        BGX_CK_LAUNCH();
+    }
+    if (values_out) {
+        hipLaunchKernelGGL(k_luck_values, dim3((unsigned)(((int64_t)A.B * 21 + 255) / 256)), dim3(256), 0, s, A, sel,
+                           L.lane_off.at(ws), &ctr->rows, L.minv.at(ws), values_out);
+        BGX_CK_LAUNCH();
+    }
     if (stats_host) {
         unsigned long long lv = 0;
         BGX_CK(hipMemcpyAsync(&lv, &ctr->leaves, 8, hipMemcpyDeviceToHost, s));
@@ -2251,7 +2271,14 @@ extern "C" {
 
 int bgx_roll_luck(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
                   float* luck_out, float* mean_out, uint64_t* stats_host, void* stream) {
-    return roll_luck(e, vpacked, hidden, value_bias, sel, luck_out, mean_out, stats_host, stream);
+    if (!luck_out) return BGX_EINVAL;
+    return roll_luck(e, vpacked, hidden, value_bias, sel, luck_out, mean_out, nullptr, stats_host, stream);
+}
+
+int bgx_roll_values(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, const uint8_t* sel,
+                    float* values_out, uint64_t* stats_host, void* stream) {
+    if (!values_out) return BGX_EINVAL;
+    return roll_luck(e, vpacked, hidden, value_bias, sel, nullptr, nullptr, values_out, stats_host, stream);
 }
 
 int bgx_two_ply(bgx_engine* e, const float* vpacked, int32_t hidden, float value_bias, int32_t* best_out,

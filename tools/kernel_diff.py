@@ -18,7 +18,7 @@ import sys
 import isa_lint
 
 ADDR = re.compile(r"\s*// [0-9A-F]+: ([0-9A-F]{8}( [0-9A-F]{8})*)")       # "// address: encoding" -> encoding
-PCREL = re.compile(r"0x[0-9a-f]{8}|\b[0-9A-F]{8}$")
+PCREL = re.compile(r"0x[0-9a-f]+|\b[0-9A-F]{8}$")        # the literal as printed (any width) and as encoded
 
 
 def kernels_of(lib: str) -> dict:
