@@ -1058,6 +1058,60 @@ int bgx_rollout_cube_luck_flush(const uint8_t* starts_dev, const int32_t* group_
                                 int32_t cap, int32_t jacoby, const uint8_t* cube_dev, float* lane_luck_dev,
                                 int64_t* cube_luck_tally_dev, void* stream);
 
+/* ---- luck of the arena (csrc/bg_arena_luck.h; bgx/arena.py; no counterpart in
+ * the reference) ----
+ * The luck adjustment of bgx_rollout_luck_* for the cubeless head-to-head arena, beside the state
+ * of bgx_arena_begin / bgx_arena_advance.  Two things differ from a rollout.  The sign: there is
+ * no start record, a game's luck is kept from A's side, so a roll's luck counts + where A is on
+ * move (sel_a) and - where B is (sel_b).  The opening roll: an arena game begins with the engine's
+ * standard reset, whose first roll is drawn with doubles rejected, so on a game's first ply the
+ * mean is taken over the 15 non-doubles at 1/15 each, not over the 21 rolls at 1/36 and 2/36.
+ * State, the caller's: lane_luck float[n] (the running sum of the lane's current game), fresh
+ * uint8[n] (the lane's record holds an opening roll) and luck_tally int64[8]
+ * (bgx_arena_luck_field; entries 5..7 stay zero).
+ * bgx_arena_luck_begin: once after bgx_arena_begin: lane_luck = 0, fresh = 1, luck_tally = 0.
+ * bgx_arena_luck_add: before the players act, with values21 float[n][21] = bgx_roll_values' v_r
+ * of the lanes with sel_a | sel_b.  Every lane with sel_a[i] | sel_b[i] whose record is not
+ * game_over, with (d0, d1) the record's roll (bytes 53, 54):
+ *   fresh[i] == 0: mean = fma(p_20, v_20, ... fma(p_0, v_0, 0)), p_r = 1/36 for doubles, else 2/36
+ *                  (bgx_roll_luck's mean_out and luck_out bit for bit)
+ *   fresh[i] != 0: mean = fma(1/15, v_r, mean) over the 15 non-doubles, r ascending, from 0; the
+ *                  doubles' values are not read into the chain
+ *   luck = v_(the record's roll) - mean in fp32   (0 when the bytes hold no roll, and 0 for a
+ *          double while fresh: it cannot have been drawn)
+ *   lane_luck[i] += sel_a[i] ? luck : -luck (one fp32 add), fresh[i] = 0,
+ * and luck_out[i] = luck (the mover's view), mean_out[i] = mean where they are given.  No other
+ * lane is written.  Either mean is the expectation of v under the distribution the roll was drawn
+ * from, given the position and the mover, so the luck has mean zero given the history.
+ * bgx_arena_luck_flush: after bgx_step and BEFORE bgx_arena_advance (games_done and the
+ * selections are still the step's), with the step's done and info.  A lane with sel_a | sel_b and
+ * games_done < games_per_lane whose game bgx_arena_advance will count (done, a winner) books it:
+ * res = A's result as advance books it (+-1 / 2 / 3; 0 points for a score outside 1..3),
+ * Lq = llrintf(lane_luck[i] * 65536) clamped to +-2^21 (0 when not finite; round half even:
+ * bgx_rollout_luck_flush's), and
+ *   LUCK += Lq, LUCK2_LO += Lq^2 & (2^30 - 1), LUCK2_HI += Lq^2 >> 30, RESLUCK += res * Lq,
+ *   LUCK_GAMES += 1.
+ * Every done of such a lane, counted or not, gets lane_luck[i] = 0 and fresh[i] = 1: the record
+ * is the next game's opening already.  LUCK_GAMES equals tally[BGX_ARENA_GAMES].  |Lq| <= 2^21 and
+ * |res| <= 3: the sums hold 2^33 games at the clamp.
+ * One thread per lane, 256 per block; the sums combined per wave before the 64-bit atomics;
+ * integers, so run-to-run identical.  No allocation and no synchronisation: graph-capturable.
+ * BGX_EINVAL for n <= 0, games_per_lane < 0 or a NULL pointer other than luck_out / mean_out. */
+enum bgx_arena_luck_field {
+    BGX_ARENA_LUCK = 0,           /* sum of Lq (2^-16 points), A's view */
+    BGX_ARENA_LUCK2_LO = 1,       /* sum of Lq^2 & (2^30 - 1) */
+    BGX_ARENA_LUCK2_HI = 2,       /* sum of Lq^2 >> 30: sum Lq^2 = LUCK2_HI 2^30 + LUCK2_LO (2^-32) */
+    BGX_ARENA_RESLUCK = 3,        /* sum of res * Lq (2^-16), res = A's points of the game */
+    BGX_ARENA_LUCK_GAMES = 4      /* games booked: equals tally[BGX_ARENA_GAMES] */
+};
+int bgx_arena_luck_begin(int32_t n, float* lane_luck_dev, uint8_t* fresh_dev, int64_t* luck_tally_dev, void* stream);
+int bgx_arena_luck_add(const uint8_t* records_dev, const uint8_t* sel_a_dev, const uint8_t* sel_b_dev,
+                       const float* values21_dev, int32_t n, float* lane_luck_dev, uint8_t* fresh_dev,
+                       float* luck_out_or_null, float* mean_out_or_null, void* stream);
+int bgx_arena_luck_flush(const uint8_t* sel_a_dev, const uint8_t* sel_b_dev, const uint8_t* done_dev,
+                         const int32_t* info_dev, const int32_t* games_done_dev, int32_t n, int32_t games_per_lane,
+                         float* lane_luck_dev, uint8_t* fresh_dev, int64_t* luck_tally_dev, void* stream);
+
 /* ---- PPO update loss head (ppo_agent.py:268-305), fused ----
  * For n rows: masked log-softmax of the logits (dtype 0 = fp32, 1 = fp16, row
  * stride ld_logits; mask from the legal count in bytes 60-61 of each 64-byte

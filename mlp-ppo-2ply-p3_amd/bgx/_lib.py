@@ -123,6 +123,9 @@ SIGNATURES = {
     "bgx_rollout_cube_luck_add": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "bgx_rollout_cube_luck_pass": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, BgxCubeRule, _P, _P, _P, _P]),
     "bgx_rollout_cube_luck_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "bgx_arena_luck_begin": (ctypes.c_int, [_I32, _P, _P, _P, _P]),
+    "bgx_arena_luck_add": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
+    "bgx_arena_luck_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
     "bgx_random_act": (ctypes.c_int, [_P, _I32, ctypes.c_uint64, ctypes.c_uint32, _P, _P]),
     "bgx_ppo_head": (ctypes.c_int, [_P, _I32, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _I32, _I32, ctypes.c_float,
                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, _P, ctypes.c_int64, _P, _P, _P]),

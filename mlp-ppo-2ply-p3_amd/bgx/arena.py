@@ -21,6 +21,15 @@ result.
 
     python -m bgx.arena --a new.pt --b old.pt --max-steps 4000 --cube --cube-lookahead-a 0 \\
         --cube-lookahead-b 0 --cube-double-a 0.35
+
+--luck: the cubeless result with every roll's luck subtracted as a control variate (DESIGN.md §19;
+csrc/bg_arena_luck.h): the mover's best 1-ply value after the roll that came minus its mean over
+the rolls it was drawn from -- the 21 rolls, or on a game's first ply the 15 non-doubles of the
+opening roll -- summed per game from A's side.  The result gains ppg_luck_a, ppg_luck_stderr,
+variance_ratio, luck_scale and luck_mean.
+
+    python -m bgx.arena --a new.pt --b old.pt --player-a 2ply --top-k-a 4 --player-b 2ply --top-k-b 4 \\
+        --max-steps 4000 --luck
 """
 from __future__ import annotations
 
@@ -34,7 +43,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .engine import Engine, R_CUR, R_NM0, R_NM1, _ptr, _stream
+from .engine import Engine, R_CUR, R_NM0, R_NM1, R_ROLL0, R_ROLL1, _ptr, _stream
 
 # tally int64[16] (include/bgx.h bgx_arena_field); entries 14, 15 stay zero
 FIELDS = ("games", "wins_a", "wins_b", "points_a", "points_b", "gammons_a", "gammons_b", "backgammons_a",
@@ -43,6 +52,10 @@ ACTIVE = FIELDS.index("active_lanes")
 # cube_tally int64[16] (include/bgx.h bgx_arena_cube_field); entries 11..15 stay zero
 CUBE_FIELDS = ("cube_games", "cube_points_a", "cube_points2", "cube_wins_a", "cube_log2", "pass_games", "pass_plies",
                "passes_a", "passes_b", "doubles_a", "doubles_b")
+# luck_tally int64[8] (include/bgx.h bgx_arena_luck_field): fixed point, 2^-16 points; entries 5..7 stay zero
+LUCK_FIELDS = ("luck_sum", "luck2_lo", "luck2_hi", "resluck", "luck_games")
+LUCK_ONE = 65536                # Lq = rint(L * LUCK_ONE), clamped to +-2^21 (replay.luck_q)
+LUCK_SPLIT = 30                 # sum Lq^2 = luck2_hi * 2^30 + luck2_lo
 TRACE_LIMIT = 1 << 22           # trace=True: batch x max_steps entries per traced field
 SYNC_EVERY = 16                 # sync-free players: steps between host reads of the active-lane count
 
@@ -244,6 +257,151 @@ def arena_cube_reference(trace, batch: int, games_per_lane: int, rule_a, rule_b)
     return dict(tally=tally, cube_tally=ct, games_done=games, cube=states, dsel=dsels, offer=offers, passed=passes)
 
 
+# --------------------------------------------------------------------- luck --
+def summarize_luck(tally, luck_tally, steps: int, unfinished: int, scale="fit") -> dict:
+    """summarize(tally, steps, unfinished) plus the luck-adjusted estimate from the 5 luck sums
+    (LUCK_FIELDS; DESIGN.md §19, with §10's formulas).  A game's adjusted result is res - c L: res
+    A's points, L the game's luck from A's side (over its rolls, the value after the roll that came
+    minus its expectation under the distribution the roll was drawn from; + on A's rolls, - on
+    B's).  E[L] = 0, so any constant c leaves the mean unbiased.  In fp64 from exact Python
+    integers, n = games, sum res = points_a - points_b, sum res^2 as summarize forms it,
+    sum L = LUCK / 2^16, sum L^2 = (LUCK2_HI 2^30 + LUCK2_LO) / 2^32, sum res L = RESLUCK / 2^16:
+        ppg_luck_a = (sum res - c sum L) / n
+        var_y = (sum res^2 - 2 c sum res L + c^2 sum L^2 - n ppg_luck_a^2) / (n - 1), >= 0
+        ppg_luck_stderr = sqrt(var_y / n)        variance_ratio = var_y / var_res
+    (variance_ratio 1.0 when var_res is 0; n < 2: the standard errors are 0).  `scale` = "fit":
+    c = cov(res, L) / var(L) of these games, numerator and denominator as exact integers (0 when
+    the denominator is 0); fitted on the same games it biases ppg_luck_a by O(1/n).  A float: that
+    fixed c (1.0 when the net's values are in points).  Adds ppg_luck_a, ppg_luck_stderr,
+    variance_ratio, luck_scale (c), luck_mean = sum L / n with luck_mean_stderr, and the 5 sums
+    under their names.  Raises ValueError when LUCK_GAMES != games."""
+    r = summarize(tally, steps, unfinished)
+    k = [int(v) for v in luck_tally]
+    if len(k) < len(LUCK_FIELDS):
+        raise ValueError(f"summarize_luck: the luck tally has {len(k)} entries, needs {len(LUCK_FIELDS)}")
+    n = r["games"]
+    if k[4] != n:
+        raise ValueError(f"summarize_luck: the luck tally counts {k[4]} games, the plain tally {n}")
+    sr = r["points_a"] - r["points_b"]
+    sr2 = sum(r[f"wins_{x}"] + 3 * r[f"gammons_{x}"] + 8 * r[f"backgammons_{x}"] for x in "ab")
+    il, il2, irl = k[0], (k[2] << LUCK_SPLIT) + k[1], k[3]                          # 2^-16, 2^-32, 2^-16
+    den = n * il2 - il * il                                                          # n^2 var(L), 2^-32
+    if scale == "fit":
+        c = LUCK_ONE * ((n * irl - sr * il) / den) if den > 0 else 0.0
+    else:
+        c = float(scale)
+    sl, sl2, srl = il / LUCK_ONE, il2 / (LUCK_ONE * LUCK_ONE), irl / LUCK_ONE
+    eq = (sr - c * sl) / n if n > 0 else 0.0
+    var_y = max(sr2 - 2.0 * c * srl + c * c * sl2 - n * eq * eq, 0.0) / (n - 1) if n > 1 else 0.0
+    var_r = max(sr2 - n * r["ppg_a"] ** 2, 0.0) / (n - 1) if n > 1 else 0.0
+    r.update(zip(LUCK_FIELDS, k))
+    r.update(ppg_luck_a=eq, ppg_luck_stderr=math.sqrt(var_y / n) if n > 0 else 0.0,
+             variance_ratio=var_y / var_r if var_r > 0.0 else 1.0, luck_scale=c, luck_mean=sl / n if n > 0 else 0.0,
+             luck_mean_stderr=math.sqrt(max(den, 0) / (n * n * (n - 1))) / LUCK_ONE if n > 1 else 0.0)
+    return r
+
+
+class ArenaLuck:
+    """The luck adjustment of an arena match: `value`, the search.ValueHead whose
+    best 1-ply values of the 21 rolls give each roll's luck (either side's net, or a third one: the
+    luck has mean zero whatever the net, a better one removes more variance), and `scale`, "fit" or
+    the fixed coefficient c of summarize_luck."""
+
+    def __init__(self, value, scale="fit"):
+        from .search import ValueHead
+        if not isinstance(value, ValueHead):
+            raise ValueError("ArenaLuck: value must be a search.ValueHead")
+        if scale != "fit":
+            scale = float(scale)
+            if math.isnan(scale):
+                raise ValueError("ArenaLuck: scale is NaN")
+        self.value, self.scale = value, scale
+
+
+_NOT_DOUBLE = [r for r, (a, b) in enumerate((a, b) for a in range(1, 7) for b in range(a, 7)) if a != b]
+
+
+def arena_roll_luck_reference(values21, d0, d1, opening):
+    """arena_roll_luck of csrc/bg_arena_luck.h (bgx_arena_luck_add's arithmetic) on arrays in numpy
+    float32, bit for bit: (luck f32[n], mean f32[n]) for the per-roll values `values21` f32[n, 21]
+    of the movers holding the rolls (d0, d1) (record bytes 53, 54).  `opening` == 0: the mean is
+    the fp32 FMA chain sum p_r v_r over r = 0..20 with p_r = 1/36 for doubles, else 2/36 (§10's);
+    != 0 (the roll was drawn as a game's first, doubles rejected): the chain of 1/15 v_r over the 15
+    non-doubles, r ascending -- the doubles' values do not enter it.  Each step is formed exactly
+    and rounded once (cube.fma32).  luck = v of the roll - mean; 0 without a roll, and 0 for a
+    double at an opening.  NaN and infinite values propagate as in the C++."""
+    from .cube import ROLL_P, fma32, roll_index
+    f = np.float32
+    v = np.asarray(values21, f).reshape(-1, 21)
+    n = v.shape[0]
+    op = np.broadcast_to(np.asarray(opening).reshape(-1) != 0, (n,))
+    idx = roll_index(np.stack([np.broadcast_to(np.asarray(d0).reshape(-1), (n,)),
+                               np.broadcast_to(np.asarray(d1).reshape(-1), (n,))], axis=1))
+    with np.errstate(all="ignore"):
+        mid, opn = np.zeros(n, f), np.zeros(n, f)
+        for r in range(21):
+            mid = fma32(ROLL_P[r], v[:, r], mid)
+        for r in _NOT_DOUBLE:
+            opn = fma32(f(1.0) / f(15.0), v[:, r], opn)
+        mean = np.where(op, opn, mid).astype(f)
+        mine = v[np.arange(n), np.maximum(idx, 0)]
+        drawn = (idx >= 0) & ~(op & ~np.isin(idx, _NOT_DOUBLE))
+        luck = np.where(drawn, (mine - mean).astype(f), f(0)).astype(f)
+    return luck, mean
+
+
+def arena_luck_reference(trace, batch: int, games_per_lane: int) -> dict:
+    """A traced luck-adjusted match (Arena.play(trace=True, luck=...)) replayed on the host with
+    the kernels' arithmetic (include/bgx.h bgx_arena_luck_*).  Read from the trace: owner (0 none,
+    1 A, 2 B), done, info, luck_values f32[steps, B, 21] and luck_roll uint8[steps, B, 2].  Each
+    step, the lanes with an owner get arena_roll_luck_reference of their values, roll and the
+    replay's own `fresh`, added to the lane's fp32 sum with A's sign; after the step a counted game
+    (an active lane, done, a winner) books replay.luck_q of the sum against A's points, and every
+    done of an active lane zeroes the sum and sets fresh.  Returns dict(luck_tally int64[8],
+    games_done int64[B], lane_luck f32[B] (the sums left at the end), and [steps, B] each: luck and
+    mean f32 (the mover's view, NaN off the selection) and opening uint8)."""
+    from .replay import luck_q
+
+    def arr(k, dt):
+        return np.asarray(torch.as_tensor(trace[k]).cpu()).astype(dt)
+
+    f = np.float32
+    owner, done, info = arr("owner", np.int64), arr("done", np.int64), arr("info", np.int64)
+    vals, roll = arr("luck_values", f), arr("luck_roll", np.int64)
+    B, G, T = int(batch), int(games_per_lane), done.shape[0]
+    lane = np.arange(B, dtype=np.int64)
+    games, lane_luck, fresh = np.zeros(B, np.int64), np.zeros(B, f), np.ones(B, bool)
+    lt = [0] * 8
+    lucks, means = np.full((T, B), np.nan, f), np.full((T, B), np.nan, f)
+    opening = np.zeros((T, B), np.uint8)
+    for t in range(T):
+        sel = owner[t] != 0
+        s = np.nonzero(sel)[0]
+        if len(s):
+            l, m = arena_roll_luck_reference(vals[t, s], roll[t, s, 0], roll[t, s, 1], fresh[s])
+            lucks[t, s], means[t, s], opening[t, s] = l, m, fresh[s]
+            with np.errstate(all="ignore"):
+                lane_luck[s] = (lane_luck[s] + np.where(owner[t, s] == 1, l, -l).astype(f)).astype(f)
+            fresh[s] = False
+        dn = sel & (games < G) & (done[t] != 0)
+        winner, score = ((info[t] >> 8) & 0xFF) - 1, (info[t] >> 16) & 0xFF
+        fin = dn & (winner >= 0)
+        pts = np.where((score >= 1) & (score <= 3), score, 0)
+        res = np.where((winner == 0) == (((lane + games) & 1) == 0), pts, -pts)
+        for i in np.nonzero(fin)[0]:
+            lq = int(luck_q(lane_luck[i:i + 1])[0])
+            lt[0] += lq
+            lt[1] += (lq * lq) & ((1 << LUCK_SPLIT) - 1)
+            lt[2] += (lq * lq) >> LUCK_SPLIT
+            lt[3] += int(res[i]) * lq
+            lt[4] += 1
+        lane_luck[dn] = 0.0
+        fresh[dn] = True
+        games = games + fin
+    return dict(luck_tally=np.asarray(lt, np.int64), games_done=games, lane_luck=lane_luck, luck=lucks, mean=means,
+                opening=opening)
+
+
 # ------------------------------------------------------------------ players --
 # A player is any object with act(eng, sel, step) -> int32[B] on the engine's device; only
 # the entries with sel != 0 are read.  `sync_free` (default False): act never waits for the
@@ -365,6 +523,7 @@ class Arena:
         self.tally = torch.zeros(16, dtype=torch.int64, device=dev)
         self.actions = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.cube_state = None          # play(cube=...): the cube stage's arrays, made on first use
+        self.luck_state = None          # play(luck=...): the luck stage's arrays, made on first use
 
     def _act(self, player, sel, step):
         a = player.act(self.eng, sel, step)
@@ -380,7 +539,7 @@ class Arena:
             raise ValueError("a cube rule's equity must be a contiguous float32[B] tensor on the engine's device")
         return e
 
-    def play(self, a, b, max_steps: int, trace: bool = False, cube=None):
+    def play(self, a, b, max_steps: int, trace: bool = False, cube=None, luck=None):
         """begin; then [a.act, b.act, merge, step, advance] until no lane is active or
         `max_steps` env steps ran (weak greedy players can shuffle for thousands of steps:
         the result then reports `unfinished_lanes` instead of hanging).  Returns the
@@ -395,10 +554,31 @@ class Arena:
         cube (the state before the decision), cube_mover (the side on roll there), dsel and offer
         (0 none, 1 A, 2 B), eq_offer (the equity the side on roll decided on, NaN off dsel),
         eq_resp (the doubler's equity as the other side sees it, NaN off offer) and passed.
-        cube=None is exactly the path and result without the argument."""
+        cube=None is exactly the path and result without the argument.
+
+        `luck` (an ArenaLuck, or a bare search.ValueHead for ArenaLuck(value)):
+        every roll's luck is taken as a control variate.  Each step is then [roll_values on
+        sel_a | sel_b; arena_luck_add; a.act, b.act, merge, step; arena_luck_flush; advance].
+        roll_values synchronises, so the active-lane count is read every step.  The result is
+        summarize_luck's; the trace gains luck and luck_mean (f32, the mover's view, NaN off the
+        selection), luck_opening (uint8: the roll was a game's first and is taken against the
+        opening distribution), luck_roll (uint8[steps, B, 2], the roll bytes) and luck_values
+        (f32[steps, B, 21], NaN off the selection), whose 21 entries count towards TRACE_LIMIT.
+        `luck` together with `cube` raises ValueError: the cubeful arena's luck is not
+        implemented.  luck=None is exactly the path and result without the argument."""
         max_steps = int(max_steps)
         if max_steps < 0:
             raise ValueError(f"play: max_steps {max_steps} must be >= 0")
+        if luck is not None and not isinstance(luck, ArenaLuck):
+            from .search import ValueHead
+            if not isinstance(luck, ValueHead):
+                raise ValueError("play: luck must be an ArenaLuck, a search.ValueHead or None")
+            luck = ArenaLuck(luck)
+        if luck is not None and cube is not None:
+            raise ValueError("play: luck together with cube is not implemented (the cubeful arena's luck)")
+        if trace and luck is not None and self.B * max_steps * 21 > TRACE_LIMIT:
+            raise ValueError(f"play: trace=True with luck holds batch x max_steps x 21 = {self.B * max_steps * 21} "
+                             f"entries in luck_values; the limit is {TRACE_LIMIT} (it is for tests and small batches)")
         if trace and self.B * max_steps > TRACE_LIMIT:
             raise ValueError(f"play: trace=True holds batch x max_steps = {self.B * max_steps} entries per field; "
                              f"the limit is {TRACE_LIMIT} (it is for tests and small batches)")
@@ -435,9 +615,46 @@ class Arena:
                            for k, dt in (("cube", torch.uint8), ("cube_mover", torch.uint8), ("dsel", torch.uint8),
                                          ("offer", torch.uint8), ("eq_offer", torch.float32),
                                          ("eq_resp", torch.float32), ("passed", torch.uint8))})
+        if luck is not None:
+            from .search import roll_values
+            every = 1                   # roll_values waits for the device every step
+            if self.luck_state is None:
+                self.luck_state = dict(lane_luck=torch.zeros(self.B, dtype=torch.float32, device=dev),
+                                       fresh=torch.zeros(self.B, dtype=torch.uint8, device=dev),
+                                       tally=torch.zeros(8, dtype=torch.int64, device=dev),
+                                       sel=torch.zeros(self.B, dtype=torch.uint8, device=dev),
+                                       values=torch.zeros(self.B, 21, dtype=torch.float32, device=dev))
+            ls = self.luck_state
+            lstate = (_ptr(ls["lane_luck"]), _ptr(ls["fresh"]))
+            check(L.bgx_arena_luck_begin(self.B, *lstate, _ptr(ls["tally"]), _stream(dev)), "bgx_arena_luck_begin")
+            l_out = m_out = None
+            if trace:
+                tr.update({k: torch.zeros(max_steps, self.B, *shape, dtype=dt, device=dev)
+                           for k, dt, shape in (("luck", torch.float32, ()), ("luck_mean", torch.float32, ()),
+                                                ("luck_opening", torch.uint8, ()), ("luck_roll", torch.uint8, (2,)),
+                                                ("luck_values", torch.float32, (21,)))})
+                l_out = torch.empty(self.B, dtype=torch.float32, device=dev)
+                m_out = torch.empty(self.B, dtype=torch.float32, device=dev)
         steps = 0
         active = int(self.tally[ACTIVE].item())
         while active > 0 and steps < max_steps:
+            if luck is not None:
+                torch.bitwise_or(self.sel_a, self.sel_b, out=ls["sel"])
+                roll_values(eng, luck.value, sel=ls["sel"], out=ls["values"])
+                if trace:
+                    nan = float("nan")
+                    on = ls["sel"] != 0
+                    eng.records(out=rec)
+                    tr["luck_opening"][steps] = ls["fresh"] * ls["sel"]
+                    tr["luck_roll"][steps] = rec[:, R_ROLL0:R_ROLL1 + 1]
+                    tr["luck_values"][steps] = torch.where(on[:, None], ls["values"], nan)
+                    l_out.fill_(nan)
+                    m_out.fill_(nan)
+                check(L.bgx_arena_luck_add(recs, _ptr(self.sel_a), _ptr(self.sel_b), _ptr(ls["values"]), self.B, *lstate,
+                                           _ptr(l_out), _ptr(m_out), _stream(dev)), "bgx_arena_luck_add")
+                if trace:
+                    tr["luck"][steps] = l_out
+                    tr["luck_mean"][steps] = m_out
             if cube is not None:
                 check(L.bgx_arena_cube_sel(recs, _ptr(self.sel_a), _ptr(self.sel_b), cstate[1], cstate[0], self.B,
                                            cube.cap, _ptr(cs["dsel_a"]), _ptr(cs["dsel_b"]), st), "bgx_arena_cube_sel")
@@ -481,6 +698,9 @@ class Arena:
                 check(L.bgx_arena_cube_flush(_ptr(self.sel_a), _ptr(self.sel_b), _ptr(done), _ptr(info), state[0],
                                              self.B, int(cube.jacoby), cube.cap, *cstate, _ptr(cs["tally"]), st),
                       "bgx_arena_cube_flush")
+            if luck is not None:
+                check(L.bgx_arena_luck_flush(_ptr(self.sel_a), _ptr(self.sel_b), _ptr(done), _ptr(info), state[0], self.B,
+                                             self.G, *lstate, _ptr(ls["tally"]), _stream(dev)), "bgx_arena_luck_flush")
             check(L.bgx_arena_advance(recs, _ptr(done), _ptr(info), self.B, self.G, *state, _stream(dev)),
                   "bgx_arena_advance")
             if trace:
@@ -492,6 +712,8 @@ class Arena:
         tally = self.tally.cpu().tolist()
         if cube is not None:
             res = summarize_cube(tally, cs["tally"].cpu().tolist(), steps, tally[ACTIVE])
+        elif luck is not None:
+            res = summarize_luck(tally, ls["tally"].cpu().tolist(), steps, tally[ACTIVE], luck.scale)
         else:
             res = summarize(tally, steps, tally[ACTIVE])
         if trace:
@@ -539,7 +761,9 @@ CUBE_SIDE_DEFAULTS = {"cube_double": 0.40, "cube_pass": 0.50, "cube_too_good": m
 
 class _Parser(argparse.ArgumentParser):
     """The move-filter options are an error for any player but a 2ply one with weights; a cube
-    option is an error without --cube, a side's cube option for a `random` side (it has no rule)."""
+    option is an error without --cube, a side's cube option for a `random` side (it has no rule);
+    --luck is an error with --cube and, without --luck-net, for two `random` sides; --luck-net and
+    --luck-scale need --luck."""
 
     def parse_args(self, args=None, namespace=None):
         ns = super().parse_args(args, namespace)
@@ -580,7 +804,27 @@ class _Parser(argparse.ArgumentParser):
             ns.cube_cap = 6
         if not 0 <= ns.cube_cap <= 10:
             self.error("--cube-cap takes a number in 0..10")
+        if not ns.luck and (ns.luck_net is not None or ns.luck_scale is not None):
+            self.error("--luck-net / --luck-scale need --luck")
+        if ns.luck and ns.cube:
+            self.error("--luck with --cube is not implemented (the cubeful arena's luck)")
+        if ns.luck and ns.luck_net is None and ns.a == "random" and ns.b == "random":
+            self.error("--luck needs a value head: both sides are random, give --luck-net")
+        if ns.luck_scale is None:
+            ns.luck_scale = "fit"
         return ns
+
+
+def _luck_scale(text: str):
+    if text == "fit":
+        return text
+    try:
+        v = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--luck-scale takes 'fit' or a number, got {text!r}")
+    if math.isnan(v):
+        raise argparse.ArgumentTypeError("--luck-scale is NaN")
+    return v
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -626,7 +870,25 @@ def build_parser() -> argparse.ArgumentParser:
         ap.add_argument(f"--cube-lookahead-{side}", type=int, default=None, choices=[0, 1],
                         help=f"{S}'s equity: 0 the head's static value (sync-free), 1 its mean best 1-ply value over "
                              "the 21 rolls (default)")
+    ap.add_argument("--luck", action="store_true",
+                    help="luck-adjusted result: every roll's luck is a control variate (adds ppg_luck_a, "
+                         "ppg_luck_stderr, variance_ratio, luck_scale, luck_mean); costs one 1-ply search over the 21 "
+                         "rolls per step")
+    ap.add_argument("--luck-net", default=None, metavar="PATH",
+                    help="the net whose value head gives the luck (default: A's weights, else B's)")
+    ap.add_argument("--luck-scale", type=_luck_scale, default=None, metavar="fit|FLOAT",
+                    help="the control variate's coefficient: 'fit' (default) or a fixed number")
     return ap
+
+
+def luck_from_args(args, nets, device):
+    """The ArenaLuck of a parsed command line (None without --luck): on --luck-net's value head,
+    else A's weights, else B's."""
+    if not args.luck:
+        return None
+    from .search import ValueHead
+    net = load_net(args.luck_net, device) if args.luck_net is not None else nets[0] if nets[0] is not None else nets[1]
+    return ArenaLuck(ValueHead(net), scale=args.luck_scale)
 
 
 def cube_from_args(args, nets, device):
@@ -672,8 +934,11 @@ def main(argv=None):
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     cube = cube_from_args(args, nets, dev)
-    res = arena.play(players[0], players[1], max_steps=args.max_steps, cube=cube)
+    luck = luck_from_args(args, nets, dev)
+    res = arena.play(players[0], players[1], max_steps=args.max_steps, cube=cube, **({"luck": luck} if luck else {}))
     dt = time.perf_counter() - t0
+    if luck is not None:
+        res.update(luck=True, luck_net=args.luck_net)
     res.update(a=args.a, b=args.b, player_a="random" if nets[0] is None else args.player_a,
                player_b="random" if nets[1] is None else args.player_b, batch=args.batch,
                games_per_lane=args.games_per_lane, max_steps=args.max_steps, seed=args.seed, seconds=dt,

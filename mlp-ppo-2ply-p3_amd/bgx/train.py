@@ -595,7 +595,8 @@ class PPOTrainer:
         torch.save(self.net.state_dict(), path)
 
     def evaluate(self, opponent="random", player: str = "policy", batch: int = 4096, games_per_lane: int = 2,
-                 max_steps: int = 4000, opponent_player: str = "policy", top_k=None, margin=None, cube=False):
+                 max_steps: int = 4000, opponent_player: str = "policy", top_k=None, margin=None, cube=False,
+                 luck=False):
         """The current weights as player A of a head-to-head match (bgx.arena) against
         `opponent`: "random", a PolicyNet or the path of a saved state_dict (playing as
         `opponent_player`).  `player`: how A decides ("policy" sample, "greedy" argmax,
@@ -603,6 +604,9 @@ class PPOTrainer:
         `cube`: True plays money games with the doubling cube, each side by a
         default cube.CubeRule on its own weights' value head (a random opponent has no rule); an
         arena.ArenaCube is used as given.  The result is then arena.summarize_cube's.
+        `luck`: True takes every roll's luck from the current weights' value head as a control
+        variate; an arena.ArenaLuck is used as given.  The result is then
+        arena.summarize_luck's.  Not together with `cube` (ValueError).
         Returns the arena's result dict.  Training is not disturbed: the
         match runs on an engine and seeds of its own (the k-th evaluation of a trainer is
         seeded from (seed, k)), the players pack the weights into buffers of their own, and
@@ -612,6 +616,8 @@ class PPOTrainer:
             raise NotImplementedError("PPOTrainer.evaluate runs on one rank only: multi-rank evaluation is not "
                                       "implemented (evaluate a saved checkpoint with python -m bgx.arena)")
         from . import arena as AR
+        if luck and cube:
+            raise ValueError("PPOTrainer.evaluate: luck together with cube is not implemented")
         self._evals_done += 1
         base = (self.seed * 1_000_003 + 15_485_863 * self._evals_done) & (2**63 - 1)
         if isinstance(opponent, str) and opponent != "random":
@@ -624,18 +630,27 @@ class PPOTrainer:
             from .search import ValueHead
             cube = AR.ArenaCube(CubeRule(ValueHead(self.net)),
                                 None if opponent is None or isinstance(opponent, str) else CubeRule(ValueHead(opponent)))
+        if luck is True:
+            from .search import ValueHead
+            luck = AR.ArenaLuck(ValueHead(self.net))
+        if luck:
+            return ar.play(a, b, max_steps=max_steps, luck=luck)
         return ar.play(a, b, max_steps=max_steps, cube=cube or None)
 
 
 def eval_metrics(ev: dict) -> dict:
     """An evaluation's entries of the metrics line.  With the cube (arena.summarize_cube's result)
     eval_win_rate and eval_ppg are those of the games played to the end, eval_games counts every
-    game, and eval_ppg_cubeful and eval_pass_share are added."""
+    game, and eval_ppg_cubeful and eval_pass_share are added.  With the luck adjustment
+    (arena.summarize_luck's result) eval_ppg_luck, eval_ppg_luck_stderr and eval_variance_ratio are."""
     plain = ev.get("played_out", ev)
     m = {"eval_win_rate": plain["win_rate_a"], "eval_ppg": plain["ppg_a"], "eval_games": ev["games"],
          "eval_unfinished": ev["unfinished_lanes"]}
     if "played_out" in ev:
         m.update(eval_ppg_cubeful=ev["ppg_cubeful_a"], eval_pass_share=ev["pass_share"])
+    if "ppg_luck_a" in ev:
+        m.update(eval_ppg_luck=ev["ppg_luck_a"], eval_ppg_luck_stderr=ev["ppg_luck_stderr"],
+                 eval_variance_ratio=ev["variance_ratio"])
     return m
 
 
@@ -665,7 +680,12 @@ def main():
                     help="--eval-player 2ply: ... within this 1-ply value of the best move")
     ap.add_argument("--eval-cube", action="store_true",
                     help="evaluate at money play with the doubling cube: adds eval_ppg_cubeful and eval_pass_share")
+    ap.add_argument("--eval-luck", action="store_true",
+                    help="luck-adjusted evaluation on the current weights' value head: adds eval_ppg_luck, "
+                         "eval_ppg_luck_stderr and eval_variance_ratio")
     args = ap.parse_args()
+    if args.eval_luck and args.eval_cube:
+        ap.error("--eval-luck with --eval-cube is not implemented")
     if (args.eval_top_k is not None or args.eval_margin is not None) and args.eval_player != "2ply":
         ap.error("--eval-top-k / --eval-margin need --eval-player 2ply")
     ws = int(os.environ.get("WORLD_SIZE", "1"))
@@ -688,7 +708,8 @@ def main():
         if args.eval_every > 0 and (u + 1) % args.eval_every == 0:
             ev = tr.evaluate(args.eval_opponent, player=args.eval_player, batch=args.eval_batch,
                              games_per_lane=args.eval_games, max_steps=args.eval_max_steps,
-                             top_k=args.eval_top_k, margin=args.eval_margin, cube=args.eval_cube)
+                             top_k=args.eval_top_k, margin=args.eval_margin, cube=args.eval_cube,
+                             **({"luck": True} if args.eval_luck else {}))
             m.update(eval_metrics(ev))
         if tr.rank == 0:
             print(json.dumps(m), flush=True)

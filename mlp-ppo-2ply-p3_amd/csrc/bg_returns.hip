@@ -306,3 +306,6 @@ extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, floa
 
 // the doubling cube of the head-to-head arena: bg_cube.h's rule in two halves, the same helpers
 #include "bg_arena_cube.h"
+
+// luck-adjusted arena results: bg_cube_luck.h's roll index, weights and rounding, the helpers
+#include "bg_arena_luck.h"
