@@ -797,6 +797,119 @@ int bgx_arena_cube_flush(const uint8_t* sel_a_dev, const uint8_t* sel_b_dev, con
                          const int32_t* info_dev, const int32_t* games_done_dev, int32_t n, int32_t jacoby, int32_t cap,
                          uint8_t* cube_dev, int32_t* plies_dev, int64_t* cube_tally_dev, void* stream);
 
+/* ---- match play in the arena: matches to L points, Crawford rule, cube decisions on a match
+ * equity table (csrc/bg_match.h; bgx/match.py, bgx/arena.py; no counterpart in the
+ * reference) ----
+ * Beside the state of bgx_arena_begin the caller owns, per lane: away uint8[n, 2], the points A
+ * and B still need, each in 1..L (L = length in 1..25); craw uint8[n], 0 before the Crawford game,
+ * 1 the Crawford game, 2 after it; cube uint8[n], the cube byte of the blocks above, read with cap
+ * 10; plies int32[n]; matches_done int32[n]; seat0 uint8[n], 1 when A sat as PLAYER1 in the first
+ * game of the lane's current match; retire uint8[n], flush's note to retire; and match_tally
+ * int64[16] (bgx_arena_match_field).
+ * The tables: met float[(L + 1)^2], met[i (L + 1) + j] the chance that the side needing i wins the
+ * match against the side needing j at the start of a game; rows and columns at 1 hold the Crawford
+ * game's values.  pc float[L + 1]: pc[j] the trailer's chance after the Crawford game when it
+ * needs j and the leader 1; pc[1] = 0.5.  met_after(me, opp, craw_now) is the value of the next
+ * game after this game's points are taken off: me <= 0 gives 1, opp <= 0 gives 0; with craw_now !=
+ * 0 the next game is post-Crawford: me == 1 gives 1 - pc[opp], else pc[me]; with craw_now == 0 it
+ * is met[me][opp].  Indices past L read L: the function is total.
+ * The rule of a side, bgx_match_rule: window in [0, 1]; win_gammons / loss_gammons in [0, 1], the
+ * share of the owner's wins / losses that are gammons (backgammons are not modelled).  Every fp32
+ * product, sum and difference below is rounded once, none contracted.
+ * Win probability of the side on roll from a value v: gw = the owner's win_gammons, gl = its
+ * loss_gammons when the owner is on roll, swapped when the owner answers a double (it then
+ * evaluates the doubler's chances); W = 1 + gw, L_ = 1 + gl; c = scale v clamped to [-L_, W] by
+ * comparisons (a NaN stays a NaN); p = (c + L_) / (W + L_).
+ * The side on roll needs x, the other y, the cube shows v = 2^k:
+ *   win(n)  = (1 - gw) met_after(x - n, y) + gw met_after(x - 2n, y)
+ *   loss(n) = (1 - gl) (1 - met_after(y - n, x)) + gl (1 - met_after(y - 2n, x))
+ *   ND = loss(v) + p (win(v) - loss(v));  DT = loss(2v) + p (win(2v) - loss(2v));  DP = met_after(x - v, y)
+ * Access, the side on roll may double: plies > 0, the record not game_over, the lane active, craw
+ * != 1, the cube below 2^10 and centred or the mover's, and x > v (else the cube is dead for a side
+ * that wins the match with this game anyway).
+ * Offer: with access the side on roll doubles iff ND <= DP (not too good) and either DT - ND >=
+ * window (DP - ND) (window 0 the dead-cube doubling point, 1 the cash point) or y <= v and DT > ND
+ * (the free double: losing this game loses the match at any cube).  A NaN never doubles.
+ * Answer: the other side passes iff DT' > DP' in its own numbers: its own value of the position
+ * (the doubler's value as it estimates it), its own scale, its shares swapped.  A tie or a NaN
+ * takes.  Take: k += 1, owner = 2 - m (the taker).  Pass: the doubler scores v points.
+ * End of a game: the winner's away drops by s 2^k, s = info's game_score for a played-out game (no
+ * Jacoby rule in a match), 1 for a pass.  Winner's away <= 0: the match ends, away = (L, L), craw =
+ * 0, matches_done += 1.  Else craw 0 -> 1 when the winner's away is now 1, and 1 -> 2.  cube = 0,
+ * plies = 0.
+ * The quota is matches: bgx_arena_begin / bgx_arena_advance / bgx_arena_cube_reseat are called
+ * with games_per_lane = matches_per_lane (2 L - 1) (it must fit int32), which no lane reaches by
+ * playing, and a lane that finishes its last match is retired by games_done = games_per_lane,
+ * sel_a = sel_b = 0 and tally[BGX_ARENA_ACTIVE] -= 1: by match_respond on a pass, by match_retire
+ * after bgx_arena_advance has counted the game on a played-out one.  The plain tally counts the
+ * played-out games of counted matches.
+ * Per step: match_sel; A's value on dsel_a and B's on dsel_b; match_offer; B's value on off_a and
+ * A's on off_b; match_respond; bgx_reset with the mask; bgx_arena_cube_reseat; the players' act;
+ * bgx_arena_merge; bgx_step; match_flush; bgx_arena_advance; match_retire.  match_begin once after
+ * bgx_arena_begin.
+ * bgx_arena_match_begin: away = (L, L), craw = cube = plies = matches_done = retire = 0, seat0 =
+ * the seat of game 0, match_tally = 0.
+ * bgx_arena_match_sel: dsel_x_out[i] = 1 when sel_x[i] != 0 and side x has access; else 0.
+ * bgx_arena_match_offer: off_x_out[i] = 1 when sel_x[i] != 0, dsel_x[i] != 0, access holds (tested
+ * again) and side x offers by rule_x on eq_x[i]; DOUBLES_A / DOUBLES_B count them.
+ * bgx_arena_match_respond: on an active lane with access, sel_a and off_a set, B answers by rule_b
+ * on eq_b[i]; with sel_b and off_b set, A by rule_a on eq_a[i].  A pass scores the game (GAMES,
+ * PASS_GAMES, POINTS_x, PASSES_x of the side that gave up, LOG2 += k, PASS_PLIES += plies, the
+ * Crawford counts and the match counts), games_done += 1 (or = games_per_lane: the lane's last
+ * match), sel_a = sel_b = 0 until the reseat, reset_mask_out[i] = 1; every other lane gets 0.
+ * bgx_arena_match_flush: after bgx_step and BEFORE bgx_arena_advance.  On a lane with sel_a or
+ * sel_b set: a done with a winner is scored at the cube's value as above; the lane's last match
+ * sets retire[i] = 1.  Any done resets cube and plies; a lane without a done gets plies += 1.
+ * bgx_arena_match_retire: after bgx_arena_advance: retires the flagged lanes, clears the flag.
+ * All sums are integers, hence run-to-run identical.  Plain kernels, one thread per lane, no
+ * allocation and no synchronisation: graph-capturable.  BGX_EINVAL for n <= 0, a NULL pointer,
+ * length outside 1..25, matches_per_lane < 0, games_per_lane != matches_per_lane (2 length - 1)
+ * (match_respond), a NaN scale, or window or a gammon share outside [0, 1] (a NaN included). */
+typedef struct {
+    float scale, window, win_gammons, loss_gammons;
+} bgx_match_rule;
+enum bgx_arena_match_field {
+    BGX_ARENA_MATCH_MATCHES = 0,              /* matches that ended */
+    BGX_ARENA_MATCH_WINS_A = 1,               /* of them, won by A */
+    BGX_ARENA_MATCH_GAMES = 2,                /* games that ended, played out or passed */
+    BGX_ARENA_MATCH_PASS_GAMES = 3,           /* games ended by a passed double */
+    BGX_ARENA_MATCH_POINTS_A = 4,             BGX_ARENA_MATCH_POINTS_B = 5,   /* cube-multiplied points scored */
+    BGX_ARENA_MATCH_DOUBLES_A = 6,            BGX_ARENA_MATCH_DOUBLES_B = 7,  /* doubles offered */
+    BGX_ARENA_MATCH_PASSES_A = 8,             BGX_ARENA_MATCH_PASSES_B = 9,   /* the side that gave up */
+    BGX_ARENA_MATCH_LOG2 = 10,                /* sum of k at the game's end */
+    BGX_ARENA_MATCH_CRAWFORD_GAMES = 11,      /* games played as the Crawford game */
+    BGX_ARENA_MATCH_POST_CRAWFORD_GAMES = 12, /* games played after it */
+    BGX_ARENA_MATCH_PASS_PLIES = 13,          /* the steps of the passed games */
+    BGX_ARENA_MATCH_WINS_A_SEAT0 = 14,        /* matches won by A in which A sat as PLAYER1 in the first game */
+    BGX_ARENA_MATCH_MATCHES_SEAT0 = 15        /* matches in which A sat as PLAYER1 in the first game */
+};
+int bgx_arena_match_begin(int32_t n, int32_t length, uint8_t* away_dev, uint8_t* craw_dev, uint8_t* cube_dev,
+                          int32_t* plies_dev, int32_t* matches_done_dev, uint8_t* seat0_dev, uint8_t* retire_dev,
+                          int64_t* match_tally_dev, void* stream);
+int bgx_arena_match_sel(const uint8_t* records_dev, const uint8_t* sel_a_dev, const uint8_t* sel_b_dev,
+                        const int32_t* plies_dev, const uint8_t* cube_dev, const uint8_t* away_dev,
+                        const uint8_t* craw_dev, int32_t n, uint8_t* dsel_a_out, uint8_t* dsel_b_out, void* stream);
+int bgx_arena_match_offer(const uint8_t* records_dev, const uint8_t* sel_a_dev, const uint8_t* sel_b_dev,
+                          const uint8_t* dsel_a_dev, const uint8_t* dsel_b_dev, const float* eq_a_dev,
+                          const float* eq_b_dev, bgx_match_rule rule_a, bgx_match_rule rule_b, const float* met_dev,
+                          const float* pc_dev, int32_t length, const int32_t* plies_dev, const uint8_t* cube_dev,
+                          const uint8_t* away_dev, const uint8_t* craw_dev, int32_t n, uint8_t* off_a_out,
+                          uint8_t* off_b_out, int64_t* match_tally_dev, void* stream);
+int bgx_arena_match_respond(const uint8_t* records_dev, const uint8_t* off_a_dev, const uint8_t* off_b_dev,
+                            const float* eq_a_dev, const float* eq_b_dev, bgx_match_rule rule_a, bgx_match_rule rule_b,
+                            const float* met_dev, const float* pc_dev, int32_t length, int32_t n,
+                            int32_t games_per_lane, int32_t matches_per_lane, uint8_t* cube_dev, int32_t* plies_dev,
+                            uint8_t* away_dev, uint8_t* craw_dev, int32_t* matches_done_dev, uint8_t* seat0_dev,
+                            int32_t* games_done_dev, uint8_t* sel_a_dev, uint8_t* sel_b_dev, int64_t* tally_dev,
+                            int64_t* match_tally_dev, uint8_t* reset_mask_out, void* stream);
+int bgx_arena_match_flush(const uint8_t* sel_a_dev, const uint8_t* sel_b_dev, const uint8_t* done_dev,
+                          const int32_t* info_dev, const int32_t* games_done_dev, int32_t n, int32_t length,
+                          int32_t matches_per_lane, uint8_t* cube_dev, int32_t* plies_dev, uint8_t* away_dev,
+                          uint8_t* craw_dev, int32_t* matches_done_dev, uint8_t* seat0_dev, uint8_t* retire_dev,
+                          int64_t* match_tally_dev, void* stream);
+int bgx_arena_match_retire(int32_t n, int32_t games_per_lane, uint8_t* retire_dev, int32_t* games_done_dev,
+                           uint8_t* sel_a_dev, uint8_t* sel_b_dev, int64_t* tally_dev, void* stream);
+
 /* ---- truncated position rollouts (csrc/bg_trunc.h; bgx/rollout.py; no
  * counterpart in the reference) ----
  * A game that has run `horizon` plies without ending stops there and is scored with a value of

@@ -27,6 +27,12 @@ class BgxCubeRule(ctypes.Structure):
                 ("too_good_at", ctypes.c_float), ("cap", _I32), ("jacoby", _I32)]
 
 
+class BgxMatchRule(ctypes.Structure):
+    """include/bgx.h bgx_match_rule, passed by value."""
+    _fields_ = [("scale", ctypes.c_float), ("window", ctypes.c_float), ("win_gammons", ctypes.c_float),
+                ("loss_gammons", ctypes.c_float)]
+
+
 class BgxCubeLife(ctypes.Structure):
     """include/bgx.h bgx_cube_life, passed by value."""
     _fields_ = [("cube_life", ctypes.c_float), ("win_value", ctypes.c_float), ("loss_value", ctypes.c_float)]
@@ -123,6 +129,14 @@ SIGNATURES = {
     "bgx_rollout_cube_luck_add": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "bgx_rollout_cube_luck_pass": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, BgxCubeRule, _P, _P, _P, _P]),
     "bgx_rollout_cube_luck_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _P, _P, _P, _P]),
+    "bgx_arena_match_begin": (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "bgx_arena_match_sel": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, _I32, _P, _P, _P]),
+    "bgx_arena_match_offer": (ctypes.c_int, [_P, _P, _P, _P, _P, _P, _P, BgxMatchRule, BgxMatchRule, _P, _P, _I32, _P,
+                                             _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "bgx_arena_match_respond": (ctypes.c_int, [_P, _P, _P, _P, _P, BgxMatchRule, BgxMatchRule, _P, _P, _I32, _I32, _I32,
+                                               _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "bgx_arena_match_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "bgx_arena_match_retire": (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P]),
     "bgx_arena_luck_begin": (ctypes.c_int, [_I32, _P, _P, _P, _P]),
     "bgx_arena_luck_add": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "bgx_arena_luck_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),

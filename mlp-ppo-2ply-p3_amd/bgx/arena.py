@@ -30,6 +30,14 @@ variance_ratio, luck_scale and luck_mean.
 
     python -m bgx.arena --a new.pt --b old.pt --player-a 2ply --top-k-a 4 --player-b 2ply --top-k-b 4 \\
         --max-steps 4000 --luck
+
+--match N: matches to N points instead of single games (csrc/bg_match.h; bgx/match.py):
+the lanes keep the match score, the Crawford rule holds, each side doubles, takes and passes by its
+own MatchRule -- the chance of winning the match on a match equity table -- and --games-per-lane
+counts matches.  The result is A's match win rate.
+
+    python -m bgx.arena --a new.pt --b old.pt --max-steps 20000 --match 7 --games-per-lane 1 \\
+        --match-lookahead-a 0 --match-lookahead-b 0
 """
 from __future__ import annotations
 
@@ -524,6 +532,7 @@ class Arena:
         self.actions = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.cube_state = None          # play(cube=...): the cube stage's arrays, made on first use
         self.luck_state = None          # play(luck=...): the luck stage's arrays, made on first use
+        self.match_state = None         # play(match=...): the match stage's arrays, made on first use
 
     def _act(self, player, sel, step):
         a = player.act(self.eng, sel, step)
@@ -532,14 +541,14 @@ class Arena:
             raise ValueError("a player's act must return a contiguous int32[B] tensor on the engine's device")
         return a
 
-    def _equity(self, rule, sel, out):
-        e = rule.equity(self.eng, sel, self.cube_state["scratch"], out)
+    def _equity(self, rule, sel, out, scratch=None):
+        e = rule.equity(self.eng, sel, self.cube_state["scratch"] if scratch is None else scratch, out)
         if (not isinstance(e, torch.Tensor) or e.dtype != torch.float32 or e.device != self.eng.device
                 or not e.is_contiguous() or e.numel() != self.B):
             raise ValueError("a cube rule's equity must be a contiguous float32[B] tensor on the engine's device")
         return e
 
-    def play(self, a, b, max_steps: int, trace: bool = False, cube=None, luck=None):
+    def play(self, a, b, max_steps: int, trace: bool = False, cube=None, luck=None, match=None):
         """begin; then [a.act, b.act, merge, step, advance] until no lane is active or
         `max_steps` env steps ran (weak greedy players can shuffle for thousands of steps:
         the result then reports `unfinished_lanes` instead of hanging).  Returns the
@@ -565,7 +574,23 @@ class Arena:
         opening distribution), luck_roll (uint8[steps, B, 2], the roll bytes) and luck_values
         (f32[steps, B, 21], NaN off the selection), whose 21 entries count towards TRACE_LIMIT.
         `luck` together with `cube` raises ValueError: the cubeful arena's luck is not
-        implemented.  luck=None is exactly the path and result without the argument."""
+        implemented.  luck=None is exactly the path and result without the argument.
+
+        `match` (a match.ArenaMatch): matches to match.length points with the
+        Crawford rule and cube decisions on the match equity table; `games_per_lane` then counts
+        MATCHES per lane.  Each step is [match_sel; A's value on dsel_a, B's on dsel_b; match_offer;
+        B's value on off_a, A's on off_b; match_respond; reset(mask); arena_cube_reseat; a.act,
+        b.act, merge, step; match_flush; arena_advance; match_retire].  The host reads the
+        active-lane count every SYNC_EVERY steps only when both players and both rules are
+        sync-free.  The result is match.summarize_match's; the trace gains away (uint8[steps, B, 2],
+        the points A and B need), craw, cube, cube_mover, dsel, offer, eq_offer, eq_resp and passed,
+        all taken before the decision; the two-wide field counts towards TRACE_LIMIT.  `match`
+        together with `cube` or `luck` raises ValueError.  match=None is exactly the path and result
+        without the argument."""
+        if match is not None:
+            if cube is not None or luck is not None:
+                raise ValueError("play: match together with cube or luck is not implemented")
+            return self._play_match(a, b, max_steps, trace, match)
         max_steps = int(max_steps)
         if max_steps < 0:
             raise ValueError(f"play: max_steps {max_steps} must be >= 0")
@@ -721,6 +746,114 @@ class Arena:
         return res
 
 
+    def _play_match(self, a, b, max_steps: int, trace: bool, match):
+        """play(match=...): the match path, beside the plain one."""
+        from .match import ArenaMatch, summarize_match
+        max_steps = int(max_steps)
+        if max_steps < 0:
+            raise ValueError(f"play: max_steps {max_steps} must be >= 0")
+        if not isinstance(match, ArenaMatch):
+            raise ValueError("play: match must be a match.ArenaMatch or None")
+        if trace and self.B * max_steps * 2 > TRACE_LIMIT:
+            raise ValueError(f"play: trace=True with match holds batch x max_steps x 2 = {self.B * max_steps * 2} "
+                             f"entries in away; the limit is {TRACE_LIMIT} (it is for tests and small batches)")
+        L, eng, dev = _lib.load(), self.eng, self.eng.device
+        Lm, M, G = match.length, self.G, match.games_quota(self.G)
+        recs, st = ctypes.c_void_p(eng.lanes_ptr()), _stream(dev)
+        state = (_ptr(self.games_done), _ptr(self.sel_a), _ptr(self.sel_b), _ptr(self.tally))
+        if self.match_state is None:
+            u8 = lambda *s: torch.zeros(self.B, *s, dtype=torch.uint8, device=dev)      # noqa: E731
+            f32 = lambda: torch.zeros(self.B, dtype=torch.float32, device=dev)          # noqa: E731
+            i32 = lambda: torch.zeros(self.B, dtype=torch.int32, device=dev)            # noqa: E731
+            self.match_state = dict(away=u8(2), craw=u8(), cube=u8(), plies=i32(), matches_done=i32(), seat0=u8(),
+                                    retire=u8(), tally=torch.zeros(16, dtype=torch.int64, device=dev), dsel_a=u8(),
+                                    dsel_b=u8(), off_a=u8(), off_b=u8(), mask=u8(), eq_a=f32(), eq_b=f32(),
+                                    er_a=f32(), er_b=f32(), scratch=f32())
+        ms = self.match_state
+        met, pc = (_ptr(t) for t in match.tables(dev))
+        ra, rb = match.rule_a.struct(), match.rule_b.struct()
+        cube_p, plies_p, away_p, craw_p = (_ptr(ms[k]) for k in ("cube", "plies", "away", "craw"))
+        lane = (away_p, craw_p, _ptr(ms["matches_done"]), _ptr(ms["seat0"]))
+        eng.reset(want_obs=False)
+        check(L.bgx_arena_begin(recs, self.B, G, *state, st), "bgx_arena_begin")
+        check(L.bgx_arena_match_begin(self.B, Lm, away_p, craw_p, cube_p, plies_p, lane[2], lane[3], _ptr(ms["retire"]),
+                                      _ptr(ms["tally"]), st), "bgx_arena_match_begin")
+        tr = None
+        if trace:
+            tr = {k: torch.zeros(max_steps, self.B, *shape, dtype=dt, device=dev)
+                  for k, dt, shape in (("mover", torch.uint8, ()), ("n_moves", torch.int32, ()),
+                                       ("action", torch.int32, ()), ("owner", torch.uint8, ()),
+                                       ("done", torch.uint8, ()), ("info", torch.int32, ()),
+                                       ("away", torch.uint8, (2,)), ("craw", torch.uint8, ()),
+                                       ("cube", torch.uint8, ()), ("cube_mover", torch.uint8, ()),
+                                       ("dsel", torch.uint8, ()), ("offer", torch.uint8, ()),
+                                       ("eq_offer", torch.float32, ()), ("eq_resp", torch.float32, ()),
+                                       ("passed", torch.uint8, ()))}
+            rec = torch.empty(self.B, 64, dtype=torch.uint8, device=dev)
+        sync_free = getattr(a, "sync_free", False) and getattr(b, "sync_free", False) and match.sync_free
+        every = SYNC_EVERY if sync_free else 1
+        steps = 0
+        active = int(self.tally[ACTIVE].item())
+        while active > 0 and steps < max_steps:
+            check(L.bgx_arena_match_sel(recs, state[1], state[2], plies_p, cube_p, away_p, craw_p, self.B,
+                                        _ptr(ms["dsel_a"]), _ptr(ms["dsel_b"]), st), "bgx_arena_match_sel")
+            if trace:
+                eng.records(out=rec)
+                tr["away"][steps] = ms["away"]
+                tr["craw"][steps] = ms["craw"]
+                tr["cube"][steps] = ms["cube"]
+                tr["cube_mover"][steps] = rec[:, R_CUR]
+                tr["dsel"][steps] = ms["dsel_a"] + 2 * ms["dsel_b"]
+            eq_a = self._equity(match.rule_a, ms["dsel_a"], ms["eq_a"], ms["scratch"])
+            eq_b = self._equity(match.rule_b, ms["dsel_b"], ms["eq_b"], ms["scratch"])
+            check(L.bgx_arena_match_offer(recs, state[1], state[2], _ptr(ms["dsel_a"]), _ptr(ms["dsel_b"]), _ptr(eq_a),
+                                          _ptr(eq_b), ra, rb, met, pc, Lm, plies_p, cube_p, away_p, craw_p, self.B,
+                                          _ptr(ms["off_a"]), _ptr(ms["off_b"]), _ptr(ms["tally"]), st),
+                  "bgx_arena_match_offer")
+            # the doubler's value as the other side sees it: B's on A's doubles, A's on B's
+            er_b = self._equity(match.rule_b, ms["off_a"], ms["er_b"], ms["scratch"])
+            er_a = self._equity(match.rule_a, ms["off_b"], ms["er_a"], ms["scratch"])
+            check(L.bgx_arena_match_respond(recs, _ptr(ms["off_a"]), _ptr(ms["off_b"]), _ptr(er_a), _ptr(er_b), ra, rb,
+                                            met, pc, Lm, self.B, G, M, cube_p, plies_p, *lane, *state[:3],
+                                            _ptr(self.tally), _ptr(ms["tally"]), _ptr(ms["mask"]), st),
+                  "bgx_arena_match_respond")
+            if trace:
+                nan = float("nan")
+                tr["offer"][steps] = ms["off_a"] + 2 * ms["off_b"]
+                tr["eq_offer"][steps] = torch.where(ms["dsel_a"] != 0, eq_a, torch.where(ms["dsel_b"] != 0, eq_b, nan))
+                tr["eq_resp"][steps] = torch.where(ms["off_a"] != 0, er_b, torch.where(ms["off_b"] != 0, er_a, nan))
+                tr["passed"][steps] = ms["mask"]
+            eng.reset(lane_mask=ms["mask"], want_obs=False)
+            check(L.bgx_arena_cube_reseat(recs, _ptr(ms["mask"]), self.B, G, *state[:3], st), "bgx_arena_cube_reseat")
+            act_a = self._act(a, self.sel_a, steps)
+            act_b = self._act(b, self.sel_b, steps)
+            check(L.bgx_arena_merge(state[1], state[2], _ptr(act_a), _ptr(act_b), self.B, _ptr(self.actions), st),
+                  "bgx_arena_merge")
+            if trace:
+                eng.records(out=rec)
+                tr["mover"][steps] = rec[:, R_CUR]
+                tr["n_moves"][steps] = rec[:, R_NM0].to(torch.int32) | (rec[:, R_NM1].to(torch.int32) << 8)
+                tr["action"][steps] = self.actions
+                tr["owner"][steps] = self.sel_a + 2 * self.sel_b
+            _, _, done, info = eng.step(self.actions, want_obs=False, want_info=True)
+            check(L.bgx_arena_match_flush(state[1], state[2], _ptr(done), _ptr(info), state[0], self.B, Lm, M, cube_p,
+                                          plies_p, *lane, _ptr(ms["retire"]), _ptr(ms["tally"]), st),
+                  "bgx_arena_match_flush")
+            check(L.bgx_arena_advance(recs, _ptr(done), _ptr(info), self.B, G, *state, st), "bgx_arena_advance")
+            check(L.bgx_arena_match_retire(self.B, G, _ptr(ms["retire"]), *state, st), "bgx_arena_match_retire")
+            if trace:
+                tr["done"][steps] = done
+                tr["info"][steps] = info
+            steps += 1
+            if steps % every == 0 or steps == max_steps:
+                active = int(self.tally[ACTIVE].item())
+        tally = self.tally.cpu().tolist()
+        res = summarize_match(tally, ms["tally"].cpu().tolist(), steps, tally[ACTIVE])
+        if trace:
+            return res, {k: v[:steps] for k, v in tr.items()}
+        return res
+
+
 # ------------------------------------------------------------- command line --
 PLAYER_KINDS = ("policy", "greedy", "1ply", "2ply")
 
@@ -812,7 +945,46 @@ class _Parser(argparse.ArgumentParser):
             self.error("--luck needs a value head: both sides are random, give --luck-net")
         if ns.luck_scale is None:
             ns.luck_scale = "fit"
+        self._match_args(ns)
         return ns
+
+    def _match_args(self, ns):
+        """--match N: not with --cube or --luck; a --match-* option needs it, a side's for a side
+        with weights."""
+        if ns.match is not None and (ns.cube or ns.luck):
+            self.error("--match with --cube or --luck is not implemented")
+        if ns.match is not None and not 1 <= ns.match <= 25:
+            self.error("--match takes a match length in 1..25")
+        if ns.met is not None and ns.match is None:
+            self.error("--met needs --match")
+        for side in "ab":
+            given = [k for k in MATCH_SIDE_DEFAULTS if getattr(ns, f"{k}_{side}") is not None]
+            flags = ", ".join("--" + k.replace("_", "-") + "-" + side for k in given)
+            if given and ns.match is None:
+                self.error(f"{flags} need --match")
+            if given and getattr(ns, side) == "random":
+                self.error(f"{flags}: a random side has no match rule")
+            for k, v in MATCH_SIDE_DEFAULTS.items():
+                if getattr(ns, f"{k}_{side}") is None:
+                    setattr(ns, f"{k}_{side}", v)
+            if math.isnan(getattr(ns, f"match_scale_{side}")):
+                self.error(f"--match-scale-{side} is NaN")
+            if not 0.0 <= getattr(ns, f"match_window_{side}") <= 1.0:
+                self.error(f"--match-window-{side} takes a number in [0, 1]")
+
+
+MATCH_SIDE_DEFAULTS = {"match_window": 0.65, "match_gammons": (0.25, 0.25), "match_lookahead": 1, "match_net": None,
+                       "match_scale": 1.0}
+
+
+def _gammon_shares(text: str):
+    try:
+        w, l = (float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"--match-gammons takes W,L (two shares in [0, 1]), got {text!r}")
+    if not (0.0 <= w <= 1.0 and 0.0 <= l <= 1.0):
+        raise argparse.ArgumentTypeError(f"--match-gammons takes two shares in [0, 1], got {text!r}")
+    return w, l
 
 
 def _luck_scale(text: str):
@@ -878,7 +1050,52 @@ def build_parser() -> argparse.ArgumentParser:
                     help="the net whose value head gives the luck (default: A's weights, else B's)")
     ap.add_argument("--luck-scale", type=_luck_scale, default=None, metavar="fit|FLOAT",
                     help="the control variate's coefficient: 'fit' (default) or a fixed number")
+    ap.add_argument("--match", type=int, default=None, metavar="N",
+                    help="matches to N points (1..25) with the Crawford rule and cube decisions on a match equity "
+                         "table; --games-per-lane then counts matches and the result is A's match win rate")
+    ap.add_argument("--met", default=None, metavar="FILE",
+                    help="the match equity table, JSON {length, met, post_crawford} (match.load_met; its length must "
+                         "be N; default: match.met_table(N), a cubeless-play table)")
+    for side in "ab":
+        S = side.upper()
+        ap.add_argument(f"--match-window-{side}", type=float, default=None,
+                        help=f"{S} doubles from this share of the way between the dead-cube doubling point (0) and "
+                             "the cash point (1) on (default 0.65)")
+        ap.add_argument(f"--match-gammons-{side}", type=_gammon_shares, default=None, metavar="W,L",
+                        help=f"the share of {S}'s wins and of its losses that are gammons (default 0.25,0.25)")
+        ap.add_argument(f"--match-lookahead-{side}", type=int, default=None, choices=[0, 1],
+                        help=f"{S}'s value: 0 the head's static value (sync-free), 1 its mean best 1-ply value over "
+                             "the 21 rolls (default)")
+        ap.add_argument(f"--match-net-{side}", default=None, metavar="PATH",
+                        help=f"the net whose value head gives {S}'s value (default: {S}'s own weights)")
+        ap.add_argument(f"--match-scale-{side}", type=float, default=None,
+                        help=f"points per unit of {S}'s value (default 1.0)")
     return ap
+
+
+def match_from_args(args, nets, device):
+    """The match.ArenaMatch of a parsed command line (None without --match): a side with weights
+    gets a MatchRule on its --match-net-x, else its own net; a random side has no rule."""
+    if args.match is None:
+        return None
+    from .match import ArenaMatch, MatchRule, load_met
+    from .search import ValueHead
+    met = None
+    if args.met is not None:
+        length, *met = load_met(args.met)
+        if length != args.match:
+            raise ValueError(f"--met {args.met} is a table for matches to {length}, --match asks for {args.match}")
+    rules = []
+    for side, net in zip("ab", nets):
+        if net is None:
+            rules.append(None)
+            continue
+        path = getattr(args, f"match_net_{side}")
+        w, l = getattr(args, f"match_gammons_{side}")
+        rules.append(MatchRule(ValueHead(net if path is None else load_net(path, device)),
+                               scale=getattr(args, f"match_scale_{side}"), window=getattr(args, f"match_window_{side}"),
+                               win_gammons=w, loss_gammons=l, lookahead=getattr(args, f"match_lookahead_{side}")))
+    return ArenaMatch(args.match, *rules, met=met)
 
 
 def luck_from_args(args, nets, device):
@@ -935,10 +1152,16 @@ def main(argv=None):
     t0 = time.perf_counter()
     cube = cube_from_args(args, nets, dev)
     luck = luck_from_args(args, nets, dev)
-    res = arena.play(players[0], players[1], max_steps=args.max_steps, cube=cube, **({"luck": luck} if luck else {}))
+    match = match_from_args(args, nets, dev)
+    res = arena.play(players[0], players[1], max_steps=args.max_steps, cube=cube, **({"luck": luck} if luck else {}),
+                     **({"match": match} if match else {}))
     dt = time.perf_counter() - t0
     if luck is not None:
         res.update(luck=True, luck_net=args.luck_net)
+    if match is not None:
+        res.update(match=args.match, met=args.met, matches_per_s=res["matches"] / dt if dt > 0 else 0.0,
+                   **{f"{k}_{side}": getattr(args, f"{k}_{side}")
+                      for side, n in zip("ab", nets) if n is not None for k in MATCH_SIDE_DEFAULTS})
     res.update(a=args.a, b=args.b, player_a="random" if nets[0] is None else args.player_a,
                player_b="random" if nets[1] is None else args.player_b, batch=args.batch,
                games_per_lane=args.games_per_lane, max_steps=args.max_steps, seed=args.seed, seconds=dt,

@@ -309,3 +309,6 @@ extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, floa
 
 // luck-adjusted arena results: bg_cube_luck.h's roll index, weights and rounding, the helpers
 #include "bg_arena_luck.h"
+
+// match play in the arena: bg_arena_cube.h's seat rule and take, bg_cube_trunc.h's ct_ arithmetic
+#include "bg_match.h"
