@@ -910,6 +910,82 @@ int bgx_arena_match_flush(const uint8_t* sel_a_dev, const uint8_t* sel_b_dev, co
 int bgx_arena_match_retire(int32_t n, int32_t games_per_lane, uint8_t* retire_dev, int32_t* games_done_dev,
                            uint8_t* sel_a_dev, uint8_t* sel_b_dev, int64_t* tally_dev, void* stream);
 
+/* ---- match-score rollouts: position rollouts at a fixed match score, the result a histogram of
+ * outcomes (csrc/bg_match_rollout.h; bgx/match.py, bgx/rollout.py; no counterpart
+ * in the reference) ----
+ * A match rollout plays single games from the lanes' start records at a fixed score; it never
+ * carries a score from game to game.  Beside the state of bgx_rollout_begin / bgx_rollout_advance
+ * the caller owns, per tally group: away uint8[n_groups, 2], the points PLAYER1 (mover byte 0)
+ * and PLAYER2 still need, each in 1..L (L = length in 1..25); craw uint8[n_groups], 0 before the
+ * Crawford game, 1 the Crawford game, 2 after it; per lane: cube0 uint8[n], the cube byte every
+ * game on the lane starts with, and cube uint8[n], the current one, both read with cap 10
+ * (bgx_rollout_cube_begin with cap 10 initialises cube from cube0); dsel and reset_mask uint8[n];
+ * value float[n], the value of the side on roll by the rule's own source; and match_hist
+ * int64[n_groups][96] (bgx_rollout_match_field), zeroed by the caller.  The tables met and pc,
+ * met_after, the rule bgx_match_rule, ND / DT / DP, access, offer and answer are those of the
+ * block above, with one rule for both sides: the side on roll (record byte 52 = m) needs x =
+ * away[g][m], the other y = away[g][1 - m], and the offer and the answer are made on the same
+ * value[i], the answer with the shares swapped.  Indices are total as in met_after: a hand-set
+ * score cannot read outside the tables (x = 0 gives no access).
+ * The decision of a step: without access none.  With access the side on roll doubles iff the offer
+ * rule holds; then the other side passes iff the answer rule holds, else it takes: k += 1, owner =
+ * 2 - m.  A pass ends the game: the doubler wins 2^k (k before the double).  A played-out game
+ * gives its winner s 2^k, s = info's game_score in 1..3, with no Jacoby rule.  A NaN value never
+ * doubles and never passes.
+ * The histogram: bins 0..87, index won * 44 + kind * 11 + k, won = 1 when the start record's mover
+ * (starts byte 52) won the game, kind 0 a pass and 1 / 2 / 3 the played-out score, k in 0..10 the
+ * cube at the end (before the double for a pass).  Entries 88..93 are the sums below; 94 and 95
+ * stay zero.  The host turns the bins into the match-winning chance with met_after.
+ * Per step: match_sel; the value on dsel; match_decide; bgx_reset with the mask; the player's act;
+ * bgx_arena_merge; bgx_step; match_flush; bgx_rollout_advance.
+ * bgx_rollout_match_sel: dsel_out[i] = 1 when sel[i] != 0, the group is valid and the side on
+ * roll has access by the lane's record, plies[i], cube[i] and its group's score; else 0.
+ * bgx_rollout_match_decide: on a lane with dsel[i] != 0 and a valid group, access tested again
+ * (with sel[i] as the lane's activity): the decision above on value[i].  A double counts
+ * DOUBLES_START when the side on roll is the start record's mover, else DOUBLES_OTHER.  A take
+ * turns the cube.  A pass adds 1 to its bin, GAMES and PASS_GAMES, k to LOG2 and plies[i] to
+ * PASS_PLIES; games_done[i] += 1, plies[i] = 0, cube[i] = cube0[i]; the lane's last game: sel[i] =
+ * 0 and active drops; reset_mask_out[i] = 1.  Every other lane gets reset_mask_out[i] = 0.
+ * bgx_rollout_match_flush: after bgx_step and BEFORE bgx_rollout_advance.  A done with a winner on
+ * a lane with sel[i] != 0 and a valid group adds 1 to its bin at the cube's k and to GAMES, and k
+ * to LOG2.  Any done puts cube0[i] back.
+ * bgx_match_decision: the static answer per lane, no rollout state: records uint8[n, 64], cube
+ * uint8[n], away uint8[n, 2] (by player), craw uint8[n], value float[n].  values_out float[n, 3] =
+ * ND, DT, DP of the side on roll; flags_out uint8[n]: bit 0 access (without the plies > 0 term),
+ * bit 1 it offers (access and the offer rule), bit 2 the other side passes a double (the answer
+ * rule, whether or not one is offered), bit 3 too good (ND > DP).  A NaN value gives NaN for ND
+ * and DT and clears bits 1 to 3.
+ * All sums are integers, hence run-to-run identical.  Plain kernels, one thread per lane, no
+ * allocation and no synchronisation: graph-capturable.  BGX_EINVAL for a NULL pointer, n <= 0,
+ * n_groups <= 0, games_per_lane < 0, length outside 1..25, a NaN scale, or window or a gammon
+ * share outside [0, 1] (a NaN included). */
+#define BGX_ROLLOUT_MATCH_BINS 88
+#define BGX_ROLLOUT_MATCH_ROW 96
+enum bgx_rollout_match_field {
+    BGX_ROLLOUT_MATCH_GAMES = 88,          /* games that ended, played out or passed: the sum of the bins */
+    BGX_ROLLOUT_MATCH_PASS_GAMES = 89,     /* games ended by a passed double */
+    BGX_ROLLOUT_MATCH_DOUBLES_START = 90,  /* doubles offered by the start mover's side */
+    BGX_ROLLOUT_MATCH_DOUBLES_OTHER = 91,  /* doubles offered by the other side */
+    BGX_ROLLOUT_MATCH_PASS_PLIES = 92,     /* the steps of the passed games */
+    BGX_ROLLOUT_MATCH_LOG2 = 93            /* sum of k at the game's end */
+};
+int bgx_rollout_match_sel(const uint8_t* records_dev, const int32_t* group_dev, int32_t n_groups,
+                          const int32_t* plies_dev, const uint8_t* sel_dev, const uint8_t* cube_dev,
+                          const uint8_t* away_dev, const uint8_t* craw_dev, int32_t n, uint8_t* dsel_out, void* stream);
+int bgx_rollout_match_decide(const uint8_t* records_dev, const uint8_t* starts_dev, const int32_t* group_dev,
+                             const uint8_t* dsel_dev, const float* value_dev, int32_t n, int32_t n_groups,
+                             int32_t games_per_lane, bgx_match_rule rule, const float* met_dev, const float* pc_dev,
+                             int32_t length, const uint8_t* away_dev, const uint8_t* craw_dev, const uint8_t* cube0_dev,
+                             uint8_t* cube_dev, int32_t* games_done_dev, int32_t* plies_dev, uint8_t* sel_dev,
+                             int64_t* match_hist_dev, int64_t* active_dev, uint8_t* reset_mask_out, void* stream);
+int bgx_rollout_match_flush(const uint8_t* starts_dev, const int32_t* group_dev, const uint8_t* sel_dev,
+                            const uint8_t* done_dev, const int32_t* info_dev, int32_t n, int32_t n_groups,
+                            const uint8_t* cube0_dev, uint8_t* cube_dev, int64_t* match_hist_dev, void* stream);
+int bgx_match_decision(const uint8_t* records_dev, const uint8_t* cube_dev, const uint8_t* away_dev,
+                       const uint8_t* craw_dev, const float* value_dev, int32_t n, bgx_match_rule rule,
+                       const float* met_dev, const float* pc_dev, int32_t length, float* values_out, uint8_t* flags_out,
+                       void* stream);
+
 /* ---- truncated position rollouts (csrc/bg_trunc.h; bgx/rollout.py; no
  * counterpart in the reference) ----
  * A game that has run `horizon` plies without ending stops there and is scored with a value of

@@ -137,6 +137,11 @@ SIGNATURES = {
                                                _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "bgx_arena_match_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "bgx_arena_match_retire": (ctypes.c_int, [_I32, _I32, _P, _P, _P, _P, _P, _P]),
+    "bgx_rollout_match_sel": (ctypes.c_int, [_P, _P, _I32, _P, _P, _P, _P, _P, _I32, _P, _P]),
+    "bgx_rollout_match_decide": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _I32, BgxMatchRule, _P, _P, _I32, _P, _P,
+                                                _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "bgx_rollout_match_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),
+    "bgx_match_decision": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, BgxMatchRule, _P, _P, _I32, _P, _P, _P]),
     "bgx_arena_luck_begin": (ctypes.c_int, [_I32, _P, _P, _P, _P]),
     "bgx_arena_luck_add": (ctypes.c_int, [_P, _P, _P, _P, _I32, _P, _P, _P, _P, _P]),
     "bgx_arena_luck_flush": (ctypes.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P]),

@@ -9,6 +9,14 @@ pair of rules with the table (ArenaMatch), the summary (summarize_match) and the
 of the kernels: match_decision_reference (part 1 of csrc/bg_match.h on arrays, bit for bit in numpy
 float32) and arena_match_reference (the replay of a traced run).  Arena.play(match=...) of
 bgx/arena.py drives the device side.
+
+Match-score rollouts (csrc/bg_match_rollout.h; include/bgx.h "match-score
+rollouts"; Rollout.run(match=...) of bgx/rollout.py drives the device side): RolloutMatch,
+validate_score, outcome_mwc, summarize_match_rollout, rollout_match_reference (the replay of a traced
+run), static_match_decision and rollout_match_decision.
+
+    python -m bgx.rollout --net ckpt.pt --player 1ply --positions pos.json --match 7 --match-score 3,5
+    python -m bgx.rollout --net ckpt.pt --player 1ply --positions pos.json --match 7 --match-score 3,5 --match-decision
 """
 from __future__ import annotations
 
@@ -445,3 +453,303 @@ def arena_match_reference(trace, batch: int, matches_per_lane: int, match: Arena
     tally[ACTIVE] = int((games < G).sum())
     return dict(tally=tally, match_tally=mt, games_done=games, matches_done=matches, away=s_away, craw=s_craw,
                 cube=s_cube.astype(np.uint8), dsel=dsels, offer=offers, passed=passes)
+
+
+# ------------------------------------------------- match-score rollouts --
+# match_hist int64[n_groups, 96] (include/bgx.h bgx_rollout_match_field): bins 0..87, index
+# won * 44 + kind * 11 + k, then the six sums below at 88..93; 94 and 95 stay zero
+MATCH_BINS, MATCH_HIST_ROW = 88, 96
+MATCH_HIST_FIELDS = ("games", "pass_games", "doubles_start", "doubles_other", "pass_plies", "cube_log2")
+
+
+def match_bin(won, kind, k):
+    """match_bin of csrc/bg_match_rollout.h on ints or arrays."""
+    return np.asarray(won).astype(np.int64) * 44 + np.clip(kind, 0, 3) * 11 + np.clip(k, 0, MAX_CAP)
+
+
+class RolloutMatch:
+    """Match play of a rollout: single games at a fixed score of a match to
+    `length` points, the cube decisions of both sides by one `rule` (a MatchRule, or None for the
+    NaN rule: nobody doubles), `met` = (met, pc) as met_table returns them, or None for
+    met_table(length)."""
+
+    def __init__(self, length: int, rule, met=None):
+        self.length = _check_length(length, "RolloutMatch")
+        if rule is not None and not isinstance(rule, MatchRule):
+            raise ValueError("RolloutMatch: rule must be a match.MatchRule or None")
+        if met is None:
+            met = met_table(self.length)
+        if not isinstance(met, (tuple, list)) or len(met) != 2:
+            raise ValueError("RolloutMatch: met must be (met, pc) or None")
+        self.met, self.pc = check_met(self.length, *met)
+        self.has_rule = rule is not None
+        self.rule = rule if rule is not None else MatchRule(_NanValue())
+        self.sync_free = self.rule.sync_free
+        self._dev = None
+
+    tables = ArenaMatch.tables
+
+
+def validate_score(length: int, away, crawford=0):
+    """((a1, a2), crawford) as ints for a score of a match to `length`: PLAYER1 needs a1, PLAYER2
+    a2.  ValueError for an away outside 1..L, `crawford` outside 0..2, `crawford` 1 or 2 with no
+    side at 1, and `crawford` 0 with a side at 1 unless both are (1-away / 1-away is reached only
+    through a Crawford game, but its value does not depend on the state, so 0 is allowed there)."""
+    L = _check_length(length, "validate_score")
+    try:
+        a = [int(v) for v in away]
+        ok = len(a) == 2 and all(int(v) == v and not isinstance(v, bool) for v in away)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or not all(1 <= v <= L for v in a):
+        raise ValueError(f"validate_score: away must be two numbers of points in 1..{L}, got {away!r}")
+    if isinstance(crawford, bool) or crawford not in (0, 1, 2):
+        raise ValueError(f"validate_score: crawford must be 0, 1 or 2, got {crawford!r}")
+    c = int(crawford)
+    if c != 0 and 1 not in a:
+        raise ValueError(f"validate_score: crawford {c} at {a[0]}-away / {a[1]}-away, where no side needs 1 point")
+    if c == 0 and 1 in a and a != [1, 1]:
+        raise ValueError(f"validate_score: {a[0]}-away / {a[1]}-away is the Crawford game or a later one: crawford "
+                         "must be 1 or 2")
+    return (a[0], a[1]), c
+
+
+def met_after64(met, pc, length: int, me, opp, craw):
+    """met_after of csrc/bg_match.h on ints or arrays, the fp32 table values promoted to fp64."""
+    L = int(length)
+    m2, p = np.asarray(met, F).reshape(L + 1, L + 1).astype(np.float64), np.asarray(pc, F).reshape(L + 1).astype(np.float64)
+    me, opp = np.asarray(me, np.int64), np.asarray(opp, np.int64)
+    mc, oc = np.clip(me, 1, L), np.clip(opp, 1, L)
+    r = np.where(np.asarray(craw) != 0, np.where(mc == 1, 1.0 - p[oc], p[mc]), m2[mc, oc])
+    return np.where(me <= 0, 1.0, np.where(opp <= 0, 0.0, r))
+
+
+def outcome_mwc(met, pc, length: int, away, crawford: int, start_mover: int) -> np.ndarray:
+    """float64[88]: the start mover's match-winning chance after each bin's outcome at the score
+    `away` = (a1, a2), `crawford`.  With x_s the start mover's away and y_s the other's, points =
+    max(kind, 1) << k: a win gives met_after(x_s - points, y_s, crawford), a loss 1 -
+    met_after(y_s - points, x_s, crawford)."""
+    s = int(start_mover) & 1
+    xs, ys = int(away[s]), int(away[1 - s])
+    kind, k = np.divmod(np.arange(44), 11)
+    points = np.maximum(kind, 1) << k
+    win = met_after64(met, pc, length, xs - points, ys, crawford)
+    loss = 1.0 - met_after64(met, pc, length, ys - points, xs, crawford)
+    return np.concatenate([loss, win])
+
+
+def summarize_match_rollout(tally_row, hist_row, mwc88, unfinished: int = 0, cube_k: int = 0) -> dict:
+    """One position's match-score result from its plain tally row (the games played to the end),
+    its 96 histogram entries and outcome_mwc's 88 values, all from the integers: `games`; `mwc` =
+    sum(bin * mwc88) / games, the start mover's match-winning chance, with `mwc_stderr` = sqrt(sum(bin
+    (mwc88 - mwc)^2) / (games - 1) / games) (None below 2 games); `mwc_normalized` = (2 mwc - (W + L))
+    / (W - L) with W and L the chance after winning / losing a plain game at the starting cube
+    2^`cube_k` (None when they are equal): +-1 is winning / losing one current cube; `pass_share`,
+    `doubles_per_game_start` / `_other`, `mean_cube_log2`, the six sums under their names
+    (MATCH_HIST_FIELDS), `match_hist` (the 96 entries), `unfinished` and `played_out` =
+    summarize(tally_row, unfinished).  Without games the rates are 0.  Raises ValueError when a bin
+    is negative, GAMES != the sum of the bins or != the plain tally's games + PASS_GAMES, PASS_GAMES
+    != the sum of the pass bins, or the played-out bins summed over k differ from the plain tally's
+    win / gammon / backgammon counts."""
+    from .tally import summarize
+    played = summarize(tally_row, unfinished)
+    h = [int(v) for v in hist_row]
+    m = np.asarray(mwc88, np.float64).reshape(-1)
+    if len(h) != MATCH_HIST_ROW or m.shape[0] != MATCH_BINS:
+        raise ValueError(f"summarize_match_rollout: need {MATCH_HIST_ROW} histogram entries and {MATCH_BINS} values, "
+                         f"got {len(h)} and {m.shape[0]}")
+    bins = np.asarray(h[:MATCH_BINS], np.int64)
+    r = dict(zip(MATCH_HIST_FIELDS, h[MATCH_BINS:]))
+    n = r["games"]
+    if (bins < 0).any():
+        raise ValueError("summarize_match_rollout: a bin count is negative")
+    if n != int(bins.sum()):
+        raise ValueError(f"summarize_match_rollout: GAMES is {n}, the bins hold {int(bins.sum())}")
+    if n != played["games"] + r["pass_games"]:
+        raise ValueError(f"summarize_match_rollout: the histogram counts {n} games, the plain tally {played['games']} "
+                         f"and {r['pass_games']} passed")
+    by = bins.reshape(2, 4, 11).sum(axis=2)                 # [won, kind]
+    if int(by[:, 0].sum()) != r["pass_games"]:
+        raise ValueError(f"summarize_match_rollout: PASS_GAMES is {r['pass_games']}, the pass bins hold {int(by[:, 0].sum())}")
+    want = [played[f"{w}{s}"] for w in ("loss", "win") for s in (1, 2, 3)]
+    if [int(v) for v in by[:, 1:].reshape(-1)] != want:
+        raise ValueError(f"summarize_match_rollout: the played-out bins hold {by[:, 1:].tolist()} (losses, wins by "
+                         f"score), the plain tally {want}")
+
+    def ratio(a, b):
+        return a / b if b > 0 else 0.0
+
+    mwc = float((bins * m).sum() / n) if n > 0 else 0.0
+    se = math.sqrt(float((bins * (m - mwc) ** 2).sum()) / (n - 1) / n) if n >= 2 else None
+    k0 = min(max(int(cube_k), 0), MAX_CAP)
+    W, L_ = float(m[44 + 11 + k0]), float(m[11 + k0])
+    r.update(mwc=mwc, mwc_stderr=se, mwc_normalized=(2.0 * mwc - (W + L_)) / (W - L_) if W != L_ else None,
+             pass_share=ratio(r["pass_games"], n), doubles_per_game_start=ratio(r["doubles_start"], n),
+             doubles_per_game_other=ratio(r["doubles_other"], n), mean_cube_log2=ratio(r["cube_log2"], n),
+             match_hist=h, unfinished=int(unfinished), played_out=played)
+    return r
+
+
+def rollout_match_reference(trace, starts, group, n_groups: int, games_per_lane: int, match: RolloutMatch, away, craw,
+                            cube0=None) -> dict:
+    """A traced match-score run (run_lanes(trace=True, match=...)) replayed on the host with the
+    kernels' arithmetic (include/bgx.h bgx_rollout_match_*), through replay.LaneReplay and
+    match_decision_reference.  Read from the trace, [steps, B] each: match_mover (the side on roll
+    before the decision), match_value (the rule's value there), done and info; the lane records are
+    taken as not game_over, which holds between the steps of an auto-reset engine.  `away`
+    [n_groups, 2] and `craw` [n_groups] the groups' score, `cube0` uint8[B] the lanes' starting
+    cubes (None: centred at 1).  Returns dict(match_hist int64[P, 96], tally int64[P, 8], cube
+    uint8[steps, B] = the states before each decision, dsel bool[steps, B], action uint8[steps, B]
+    (0 none, 1 take, 2 pass), mask bool[steps, B], games_done int64[B], active int)."""
+    from .cube import sanitise
+    from .replay import LaneReplay, result_of
+
+    def host(x):
+        return np.asarray(torch.as_tensor(x).cpu())
+    mover, value = host(trace["match_mover"]).astype(np.int64), host(trace["match_value"]).astype(F)
+    done, info = host(trace["done"]), host(trace["info"])
+    P, L = int(n_groups), match.length
+    rp = LaneReplay(host(starts), host(group), P, games_per_lane)
+    B, T = rp.B, done.shape[0]
+    c0 = np.zeros(B, np.uint8) if cube0 is None else sanitise(host(cube0), MAX_CAP)
+    cube = c0.copy()
+    away, craw = np.asarray(away, np.int64).reshape(P, 2), np.asarray(craw, np.int64).reshape(P)
+    gi = np.clip(rp.group, 0, P - 1)
+    start = rp.start_cur.astype(np.int64) & 1
+    hist = np.zeros((P, MATCH_HIST_ROW), np.int64)
+    fld = {name: MATCH_BINS + i for i, name in enumerate(MATCH_HIST_FIELDS)}
+    states, dsels = np.zeros((T, B), np.uint8), np.zeros((T, B), bool)
+    actions, masks = np.zeros((T, B), np.uint8), np.zeros((T, B), bool)
+
+    def add(lanes, col, v=1):
+        np.add.at(hist, (gi[lanes], np.broadcast_to(col, (B,))[lanes]), np.broadcast_to(v, (B,))[lanes])
+
+    for t in range(T):
+        states[t] = cube
+        m = mover[t] & 1
+        k = np.minimum(cube.astype(np.int64) & 15, MAX_CAP)
+        d = match_decision_reference(match.met, match.pc, L, away[gi, m], away[gi, 1 - m], craw[gi], cube, m, rp.plies,
+                                     value[t], match.rule, active=rp.sel)
+        offer = d["offer"]
+        pas = offer & d["passes"]
+        take = offer & ~pas
+        dsels[t], masks[t], actions[t] = d["access"], pas, np.where(pas, 2, np.where(take, 1, 0))
+        mine = m == start
+        add(pas, match_bin(mine, 0, k))
+        for name, v in (("games", 1), ("pass_games", 1), ("pass_plies", rp.plies), ("cube_log2", k)):
+            add(pas, fld[name], v)
+        add(offer & mine, fld["doubles_start"])
+        add(offer & ~mine, fld["doubles_other"])
+        cube = np.where(pas, c0, np.where(take, (k + 1) | ((2 - m) << 4), cube)).astype(np.uint8)
+        rp.end(pas)
+        # the step, match_flush and advance
+        winner, score = result_of(info[t])
+        dn = done[t] != 0
+        fin = rp.sel & dn & (winner >= 0)
+        k = np.minimum(cube.astype(np.int64) & 15, MAX_CAP)
+        add(fin, match_bin(winner == start, score, k))
+        add(fin, fld["games"])
+        add(fin, fld["cube_log2"], k)
+        cube = np.where(dn, c0, cube).astype(np.uint8)
+        rp.advance(done[t], info[t])
+    return dict(match_hist=hist, tally=rp.tallies["tally"], cube=states, dsel=dsels, action=actions, mask=masks,
+                games_done=rp.games, active=rp.active)
+
+
+def _lane_bytes(name, v, n, dev, width=None):
+    """`v` as a contiguous uint8 tensor [n] or [n, width] on `dev`: a tensor of that shape, or one
+    entry (an int, or `width` ints) for every lane."""
+    shape = (n,) if width is None else (n, width)
+    if isinstance(v, torch.Tensor):
+        if v.shape != shape or v.dtype != torch.uint8 or v.device != dev or not v.is_contiguous():
+            raise ValueError(f"static_match_decision: {name} must be a contiguous uint8{list(shape)} tensor on {dev}")
+        return v
+    a = np.asarray(v, np.int64)
+    if a.shape != shape[1:] or (a < 0).any() or (a > 255).any():
+        raise ValueError(f"static_match_decision: {name} must be a uint8{list(shape)} tensor or one entry for all lanes")
+    return torch.from_numpy(np.ascontiguousarray(np.broadcast_to(a.astype(np.uint8), shape))).to(dev)
+
+
+def static_match_decision(eng_or_records, head_or_values, match: RolloutMatch, away, crawford=0, cube=None):
+    """"Double or not, take or pass?" at a match score with no rollout (bgx_match_decision):
+    (values f32[n, 3], flags uint8[n]) for an Engine's lane records or a contiguous uint8[n, 64]
+    tensor on the GPU.  values = ND, DT, DP, the match-winning chances of the record's mover by
+    `match`'s rule and tables; flags bit 0: the mover has access (without the first-ply term), 1:
+    it doubles, 2: the other side passes a double, 3: too good (ND > DP).  `head_or_values`: a
+    search.ValueHead (its static value of the records, search.value_lanes) or float32[n] values of
+    the side on roll on the records' device.  `away` uint8[n, 2] by player or one pair for all,
+    `crawford` uint8[n] or one state, `cube` uint8[n] cube bytes, one (k, owner) pair or None
+    (centred at 1).  Sync-free."""
+    from .arena import _stream
+    from .cube import pack
+    from .engine import Engine, _ptr
+    from .search import value_lanes
+    import ctypes
+    if not isinstance(match, RolloutMatch):
+        raise ValueError("static_match_decision: match must be a match.RolloutMatch")
+    r = eng_or_records
+    if isinstance(r, Engine):
+        n, dev, rp = r.batch, r.device, ctypes.c_void_p(r.lanes_ptr())
+    else:
+        if (not isinstance(r, torch.Tensor) or r.dtype != torch.uint8 or r.dim() != 2 or r.shape[1] != 64
+                or not r.is_contiguous() or not r.is_cuda):
+            raise ValueError("static_match_decision: records must be an Engine or a contiguous uint8[n, 64] tensor on "
+                             "the GPU")
+        n, dev, rp = r.shape[0], r.device, _ptr(r)
+    if isinstance(head_or_values, torch.Tensor):
+        value = head_or_values
+        if value.shape != (n,) or value.dtype != torch.float32 or value.device != dev or not value.is_contiguous():
+            raise ValueError(f"static_match_decision: values must be a contiguous float32[{n}] tensor on {dev}")
+    else:
+        value = value_lanes(r, head_or_values)
+    if cube is None:
+        cube = 0
+    elif not isinstance(cube, torch.Tensor):
+        cube = pack(*cube)
+    aw, cr, cb = _lane_bytes("away", away, n, dev, 2), _lane_bytes("crawford", crawford, n, dev), _lane_bytes("cube", cube, n, dev)
+    met, pc = match.tables(dev)
+    values = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().bgx_match_decision(rp, _ptr(cb), _ptr(aw), _ptr(cr), _ptr(value), n, match.rule.struct(),
+                                              _ptr(met), _ptr(pc), match.length, _ptr(values), _ptr(flags), _stream(dev)),
+               "bgx_match_decision")
+    return values, flags
+
+
+def rollout_match_decision(rollout, player, record, trials: int, match: RolloutMatch, away, crawford: int = 0,
+                           cube=(0, 0), first_roll: str = "stratified", max_steps: int = 4000) -> dict:
+    """"Double or not, take or pass?" at a match score for the side on roll in `record` (uint8[64]:
+    board and mover) at `away` = (PLAYER1's, PLAYER2's points to go), `crawford`, holding the cube
+    `cube` = (k, owner).  The position is rolled out twice in one run, as two groups over the same
+    start records: "no double", with the cube as given, and "double, take", with k + 1 owned by
+    the opponent.  No cube action happens on a game's first ply, so both start after the decision
+    asked about.  Returns `no_double` and `double_take`, the match-winning chances of the side on
+    roll, each with its `_stderr`; `double_pass` = met_after(x - 2^k, y, crawford) with stderr 0;
+    the verdict: `double` iff min(double_take, double_pass) > no_double, `take` iff double_take <=
+    double_pass; `cube`, `away`, `crawford` and the two summaries (`rollouts`).  ValueError when
+    the side on roll has no access at that score: the Crawford game, a cube that is not its own
+    or at the cap, or x <= 2^k (winning this game wins the match)."""
+    if not isinstance(match, RolloutMatch):
+        raise ValueError("rollout_match_decision: match must be a match.RolloutMatch")
+    rec = torch.as_tensor(record).reshape(-1)
+    if rec.numel() != 64 or rec.dtype != torch.uint8:
+        raise ValueError("rollout_match_decision: record must be 64 bytes (uint8)")
+    (a1, a2), cr = validate_score(match.length, away, crawford)
+    k, owner = int(cube[0]), int(cube[1])
+    mover = int(rec[52]) & 1
+    x, y = ((a1, a2), (a2, a1))[mover]
+    if cr == 1:
+        raise ValueError("rollout_match_decision: no double in the Crawford game")
+    if not 0 <= k < MAX_CAP or owner not in (0, mover + 1) or (owner == 0) != (k == 0):
+        raise ValueError(f"rollout_match_decision: cube {(k, owner)} gives the mover (PLAYER{mover + 1}) no double")
+    if x <= (1 << k):
+        raise ValueError(f"rollout_match_decision: the side on roll needs {x} with the cube at {1 << k}: the cube is "
+                         "dead, winning this game wins the match")
+    pos = torch.stack([rec.cpu(), rec.cpu()])
+    res = rollout.run(player, pos, trials, first_roll=first_roll, max_steps=max_steps, match=match,
+                      match_away=(a1, a2), match_crawford=cr, cube_start=[(k, owner), (k + 1, 2 - mover)])
+    nd, dt = res[0]["mwc"], res[1]["mwc"]
+    dp = float(met_after64(match.met, match.pc, match.length, x - (1 << k), y, cr))
+    return dict(no_double=nd, no_double_stderr=res[0]["mwc_stderr"], double_take=dt, double_take_stderr=res[1]["mwc_stderr"],
+                double_pass=dp, double_pass_stderr=0.0, double=bool(min(dt, dp) > nd), take=bool(dt <= dp),
+                cube=[k, owner], away=[a1, a2], crawford=cr, rollouts=res)

@@ -29,6 +29,10 @@ Janowski's equity after it minus its mean over the 21 rolls, times the cube.  --
 has run N plies stops there and is scored by a net's value head (bgx/truncate.py),
 which makes the slow players affordable; with --luck the dice noise of the plies played goes too (summarize_truncated_luck).  The
 estimate then carries the net's own error, which no standard error shows.
+--match N --match-score A1,A2: the position at a score of a match to N points (bgx/match.py):
+single games with cube decisions by one match rule for both sides, the result the mover's match-winning
+chance on a match equity table (match.summarize_match_rollout); --match-decision answers "double or not,
+take or pass?" per position in that chance.  It goes with no other mode.
 """
 from __future__ import annotations
 
@@ -161,12 +165,22 @@ def _records(positions) -> torch.Tensor:
 
 
 def _check_modes(where: str, luck=None, bearoff=None, cube=None, truncate=None, cube_bearoff=None, cube0=None,
-                 types: bool = False, cube_truncate=None, cube_luck=None) -> None:
+                 types: bool = False, cube_truncate=None, match=None, cube_luck=None) -> None:
     """The combinations of modes that Rollout.run and run_lanes refuse, as ValueError(f"{where}: ...")
     for the first one that applies.  `types` (run_lanes): also what only the lanes can tell --
     a cube_bearoff that is no cubeful table, a truncate that is no Truncation, a cube_truncate that
     is no CubeTruncation, a cube_luck that is no CubeLuck, cube0 without cube -- each at its place in
-    the order.  Nothing here touches the engine or the library."""
+    the order.  `match` goes with no other mode and is asked first.  Nothing here
+    touches the engine or the library."""
+    if match is not None:
+        for name, other in (("luck", luck), ("bearoff", bearoff), ("cube", cube), ("truncate", truncate),
+                            ("cube_bearoff", cube_bearoff), ("cube_truncate", cube_truncate), ("cube_luck", cube_luck)):
+            if other is not None:
+                raise ValueError(f"{where}: match together with {name} is not supported")
+        if types:
+            from .match import RolloutMatch
+            if not isinstance(match, RolloutMatch):
+                raise ValueError(f"{where}: match must be a match.RolloutMatch")
     if cube_luck is not None:
         if cube is None:
             raise ValueError(f"{where}: cube_luck without cube")
@@ -204,7 +218,7 @@ def _check_modes(where: str, luck=None, bearoff=None, cube=None, truncate=None, 
     for a, b, x, y in (("bearoff", "luck", bearoff, luck), ("cube", "luck", cube, luck), ("cube", "bearoff", cube, bearoff)):
         if x is not None and y is not None:
             raise ValueError(f"{where}: {a} together with {b} is not supported")
-    if types and cube is None and cube0 is not None:
+    if types and cube is None and match is None and cube0 is not None:
         raise ValueError(f"{where}: cube0 without cube")
 
 
@@ -343,6 +357,81 @@ class _CubeStage(_Stage):
         check(c.L.bgx_rollout_cube_flush(_ptr(c.starts), _ptr(c.grp), c.lanes[2], _ptr(done), _ptr(info), c.B, c.P,
                                          self.struct, _ptr(self.c0), _ptr(self.state), _ptr(self.tally), c.stream),
               "bgx_rollout_cube_flush")
+
+
+class _MatchStage(_Stage):
+    """`match` (a match.RolloutMatch): single games at a fixed match score,
+    `match_score` = (away [n_groups, 2], craw [n_groups]) the groups' score and `cube0` uint8[B]
+    the cube every game on the lane starts with (cap 10; None: centred at 1).  After begin:
+    cube_begin; before act: match_sel, the rule's equity on dsel, match_decide, reset(mask); after
+    the step: match_flush.  One rule serves both sides: the side on roll doubles by it, the other
+    answers on the same value.  A passed double ends the game and the masked reset gives the lane
+    its start record again.  Sync-free when the rule's value is.  Result: match_hist
+    int64[n_groups, 96] (match.MATCH_HIST_FIELDS after the 88 bins); the trace gains per step
+    match_cube uint8 (the state before the decision), match_mover (the side on roll there),
+    match_dsel (the lanes that may double), match_value (NaN off match_dsel) and match_action (0
+    none, 1 take, 2 pass)."""
+
+    def __init__(self, c: _Pass, match, score, cube0):
+        from .cube import MAX_CAP, validate_cube0
+        from .match import MATCH_HIST_ROW, validate_score
+        self.c, self.match, self.rule, self.sync_free = c, match, match.rule, match.sync_free
+        self.c0 = (torch.zeros(c.B, dtype=torch.uint8, device=c.dev) if cube0 is None
+                   else torch.as_tensor(cube0).to(c.dev).contiguous())
+        if self.c0.shape != (c.B,) or self.c0.dtype != torch.uint8:
+            raise ValueError(f"run_lanes: cube0 must be uint8[{c.B}]")
+        validate_cube0(self.c0, MAX_CAP)
+        if not isinstance(score, (tuple, list)) or len(score) != 2:
+            raise ValueError("run_lanes: match needs match_score = (away [n_groups, 2], craw [n_groups])")
+        away, craw = (np.asarray(torch.as_tensor(v).cpu()) for v in score)
+        if away.shape != (c.P, 2) or craw.shape != (c.P,):
+            raise ValueError(f"run_lanes: match_score must be (away [{c.P}, 2], craw [{c.P}])")
+        for a, k in zip(away.tolist(), craw.tolist()):
+            validate_score(match.length, a, k)
+        self.away = torch.from_numpy(away.astype(np.uint8)).to(c.dev).contiguous()
+        self.craw = torch.from_numpy(craw.astype(np.uint8)).to(c.dev).contiguous()
+        self.cap, self.struct = MAX_CAP, match.rule.struct()
+        self.met, self.pc = match.tables(c.dev)
+        self.tally = torch.zeros(c.P, MATCH_HIST_ROW, dtype=torch.int64, device=c.dev)
+        self.state, self.dsel, self.mask, self.before = c.lane_buffers(4, torch.uint8)
+        self.ebuf, self.escratch = c.lane_buffers(2, torch.float32, float("nan"))
+        c.traced(("match_cube", torch.uint8), ("match_mover", torch.uint8), ("match_dsel", torch.uint8),
+                 ("match_value", torch.float32), ("match_action", torch.uint8))
+
+    def after_begin(self):
+        c = self.c
+        check(c.L.bgx_rollout_cube_begin(_ptr(self.c0), c.B, self.cap, _ptr(self.state), c.stream),
+              "bgx_rollout_cube_begin")
+
+    def before_act(self, step):
+        c, tr = self.c, self.c.tr
+        check(c.L.bgx_rollout_match_sel(c.recs, _ptr(c.grp), c.P, c.lanes[1], c.lanes[2], _ptr(self.state),
+                                        _ptr(self.away), _ptr(self.craw), c.B, _ptr(self.dsel), c.stream),
+              "bgx_rollout_match_sel")
+        v = self.rule.equity(c.eng, self.dsel, self.escratch, self.ebuf)
+        if tr is not None:
+            c.eng.records(out=c.rec)
+            self.before.copy_(self.state)
+            tr["match_cube"][step] = self.state
+            tr["match_mover"][step] = c.rec[:, R_CUR]
+            tr["match_dsel"][step] = self.dsel
+            tr["match_value"][step] = torch.where(self.dsel != 0, v, float("nan"))
+        check(c.L.bgx_rollout_match_decide(c.recs, _ptr(c.starts), _ptr(c.grp), _ptr(self.dsel), _ptr(v), c.B, c.P, c.G,
+                                           self.struct, _ptr(self.met), _ptr(self.pc), self.match.length,
+                                           _ptr(self.away), _ptr(self.craw), _ptr(self.c0), _ptr(self.state), *c.lanes,
+                                           _ptr(self.tally), c.active, _ptr(self.mask), c.stream),
+              "bgx_rollout_match_decide")
+        if tr is not None:
+            # a take is the one decision that raises the cube's k; a pass is the mask
+            took = ((self.state & 15) > (self.before & 15)) & (self.mask == 0)
+            tr["match_action"][step] = torch.where(self.mask != 0, 2, took.to(torch.uint8)).to(torch.uint8)
+        c.reset(self.mask)
+
+    def after_step(self, done, info):
+        c = self.c
+        check(c.L.bgx_rollout_match_flush(_ptr(c.starts), _ptr(c.grp), c.lanes[2], _ptr(done), _ptr(info), c.B, c.P,
+                                          _ptr(self.c0), _ptr(self.state), _ptr(self.tally), c.stream),
+              "bgx_rollout_match_flush")
 
 
 class _CubeLuckStage(_Stage):
@@ -556,7 +645,7 @@ class Rollout:
 
     def run_lanes(self, player, starts, group, n_groups: int, games_per_lane: int, max_steps: int = 4000,
                   trace: bool = False, luck=None, bearoff=None, cube=None, cube0=None, truncate=None,
-                  cube_bearoff=None, cube_truncate=None, cube_luck=None):
+                  cube_bearoff=None, cube_truncate=None, cube_luck=None, match=None, match_score=None):
         """One pass on explicit lanes: `starts` uint8[B, 64] start records (a valid one on idle
         lanes too), `group` int32[B] lane -> tally row in [0, n_groups) or -1 (idle),
         `games_per_lane` games on every lane that has a row.  set_starts, reset, begin, then
@@ -590,6 +679,10 @@ class Rollout:
         `cube_luck` (a cube.CubeLuck), with `cube` alone: the luck of every roll of the cubeful games
         (the parenthesised calls above, made from inside the cube stage) -> cube_tally,
         cube_luck_tally.
+        `match` (a match.RolloutMatch), `match_score` = (away [n_groups, 2], craw [n_groups]), `cube0`:
+        single games at a fixed match score (match_sel, the rule's value, match_decide,
+        reset(mask) before act and match_flush after the step, where the cube's calls sit) -> match_hist.
+        It goes with no other mode.
         Each None: nothing changes; all None: exactly the three results above.
 
         Together: `truncate` with `luck` IS supported (..., luck_tally, trunc_tally;
@@ -600,7 +693,9 @@ class Rollout:
         `luck` or `bearoff`), nor do other three-way summaries (`truncate`, `cube_bearoff` or
         `cube_truncate` with others; `cube_luck` with anything but `cube`)."""
         _check_modes("run_lanes", luck, bearoff, cube, truncate, cube_bearoff, cube0, types=True,
-                     cube_truncate=cube_truncate, cube_luck=cube_luck)
+                     cube_truncate=cube_truncate, cube_luck=cube_luck, match=match)
+        if match is None and match_score is not None:
+            raise ValueError("run_lanes: match_score without match")
         max_steps, G, P = int(max_steps), int(games_per_lane), int(n_groups)
         if max_steps < 0 or G < 0 or P <= 0:
             raise ValueError(f"run_lanes: max_steps {max_steps}, games_per_lane {G} must be >= 0, n_groups {P} > 0")
@@ -628,7 +723,9 @@ class Rollout:
         trunc_stage = _TruncStage(c, truncate, luck is not None) if truncate is not None else None
         ctrunc_stage = _CubeTruncStage(c, cube_truncate, cube_stage) if cube_truncate is not None else None
         cluck_stage = _CubeLuckStage(c, cube_luck, cube_stage) if cube_luck is not None else None
-        stages = [s for s in (luck_stage, cube_stage, cut_stage, trunc_stage, ctrunc_stage, cluck_stage) if s is not None]
+        match_stage = _MatchStage(c, match, match_score, cube0) if match is not None else None
+        stages = [s for s in (luck_stage, cube_stage, cut_stage, trunc_stage, ctrunc_stage, cluck_stage, match_stage)
+                  if s is not None]
         for s in stages:
             s.after_begin()
         every = SYNC_EVERY if getattr(player, "sync_free", False) and all(s.sync_free for s in stages) else 1
@@ -671,7 +768,8 @@ class Rollout:
 
     def run(self, player, positions, trials: int, first_roll: str = "stratified", max_steps: int = 4000,
             trace: bool = False, luck=None, luck_scale="fit", bearoff=None, cube=None, cube_start=(0, 0),
-            truncate=None, cube_bearoff=None, cube_truncate=None, cube_luck=None, cube_luck_scale="fit"):
+            truncate=None, cube_bearoff=None, cube_truncate=None, cube_luck=None, cube_luck_scale="fit", match=None,
+            match_away=None, match_crawford=0):
         """Roll out every position (uint8 [P, 64] records: board and mover are read, the roll
         bytes come from the layout) `trials` times with `player` (any arena player object)
         on both sides: run_lanes per pass of the layout, at most `max_steps` env steps each
@@ -692,14 +790,35 @@ class Rollout:
         `bearoff_kind` = "cubeful".  `cube_truncate` (a cube.CubeTruncation), with
         `cube`: the results are cube.summarize_cube_truncated's (with `cube_bearoff` too, its
         cut_row= form).  `cube_luck` (a cube.CubeLuck), with `cube` alone: the results are
-        cube.summarize_cube_luck's, with `cube_luck_scale` ("fit" or a float) as its scale."""
+        cube.summarize_cube_luck's, with `cube_luck_scale` ("fit" or a float) as its scale.  `match` (a
+        match.RolloutMatch), alone: single games at the score `match_away` = (a1, a2),
+        the points PLAYER1 and PLAYER2 still need, or one pair per position, with the Crawford state
+        `match_crawford` (0 before, 1 the Crawford game, 2 after it; or one per position) and the
+        starting cube `cube_start`; the results are match.summarize_match_rollout's, `mwc` the
+        match-winning chance of the position's mover."""
         _check_modes("run", luck, bearoff, cube, truncate, cube_bearoff, cube_truncate=cube_truncate,
-                     cube_luck=cube_luck)
+                     cube_luck=cube_luck, match=match)
         pos = _records(positions)
         P = pos.shape[0]
+        score = None
+        if match is not None:
+            from .match import RolloutMatch, outcome_mwc, summarize_match_rollout, validate_score
+            if not isinstance(match, RolloutMatch):
+                raise ValueError("run: match must be a match.RolloutMatch")
+            if match_away is None:
+                raise ValueError("run: match needs match_away = (a1, a2) or one pair per position")
+            aw, cr = np.asarray(match_away), np.asarray(match_crawford)
+            if aw.shape not in ((2,), (P, 2)) or cr.shape not in ((), (P,)):
+                raise ValueError(f"run: match_away must be (a1, a2) or one pair per position and match_crawford one state "
+                                 f"or one per position, got shapes {aw.shape} and {cr.shape}")
+            checked = [validate_score(match.length, a, c) for a, c in zip(np.broadcast_to(aw, (P, 2)).tolist(),
+                                                                          np.broadcast_to(cr, (P,)).tolist())]
+            score = (np.asarray([a for a, _ in checked], np.uint8), np.asarray([c for _, c in checked], np.uint8))
+        elif match_away is not None:
+            raise ValueError("run: match_away without match")
         group, roll, G, passes = layout(P, int(trials), first_roll, self.B)
         totals = tr = None
-        if cube is not None:
+        if cube is not None or match is not None:
             from .cube import pack
             cs = np.asarray(cube_start, np.int64)
             if cs.shape not in ((2,), (P, 2)):
@@ -711,8 +830,9 @@ class Rollout:
             starts[:, R_ROLL0:R_ROLL1 + 1] = torch.from_numpy(roll[k])
             tally, unf, tr, *extra = self.run_lanes(
                 player, starts, grp, P, G, max_steps=max_steps, trace=trace, luck=luck, bearoff=bearoff, cube=cube,
-                cube0=start_byte[grp.clamp(min=0).long()] if cube is not None else None, truncate=truncate,
-                cube_bearoff=cube_bearoff, cube_truncate=cube_truncate, cube_luck=cube_luck)
+                cube0=start_byte[grp.clamp(min=0).long()] if cube is not None or match is not None else None,
+                truncate=truncate, cube_bearoff=cube_bearoff, cube_truncate=cube_truncate, cube_luck=cube_luck,
+                match=match, match_score=score)
             sums = [tally, unf] + extra                            # the modes' tallies in run_lanes' order
             totals = sums if totals is None else [a + b for a, b in zip(totals, sums)]
             if trace:
@@ -721,6 +841,13 @@ class Rollout:
         rows, unf, *extra = (t.cpu().tolist() for t in totals)
         summary = _summary(luck, bearoff, cube, truncate, cube_bearoff, cube_truncate, cube_luck)
         scale = (luck_scale,) if luck is not None else (cube_luck_scale,) if cube_luck is not None else ()
+        if match is not None:
+            ks = np.broadcast_to(cs, (P, 2))[:, 0]
+            res = [summarize_match_rollout(rows[p], extra[0][p],
+                                           outcome_mwc(match.met, match.pc, match.length, score[0][p], int(score[1][p]),
+                                                       int(pos[p, R_CUR])), unf[p], cube_k=int(ks[p]))
+                   for p in range(P)]
+            return (res, tr) if trace else res
         res = [summary(rows[p], *(e[p] for e in extra), *scale, unf[p]) for p in range(P)]
         table = bearoff if bearoff is not None else cube_bearoff
         if table is not None and table.kind != "two-sided":
@@ -980,9 +1107,60 @@ class _Parser(argparse.ArgumentParser):
                                  ("cube_luck_loss_value", 1.0, 3.0)):
                 if not lo <= getattr(ns, name) <= hi:
                     self.error(f"--{name.replace('_', '-')} takes a number in [{lo:g}, {hi:g}]")
+        self._match_args(ns)
         if ns.trials < 1 or ns.batch < 1:
             self.error("--trials and --batch must be >= 1")
         return ns
+
+    def _match_args(self, ns):
+        """--match N needs --match-score and goes with none of --cube, --luck, a bearoff cut and
+        --truncate; every other --match-* option and --met need it; the rule's options need weights."""
+        rule_opts = ("match_window", "match_gammons", "match_lookahead", "match_net", "match_scale")
+        opts = ("match_score", "match_crawford", "met", "match_cube") + rule_opts
+        if ns.match is None:
+            given = [o for o in opts if getattr(ns, o) is not None] + (["match_decision"] if ns.match_decision else [])
+            if given:
+                self.error(", ".join("--" + o.replace("_", "-") for o in given) + " need --match")
+            return
+        if not 1 <= ns.match <= 25:
+            self.error("--match takes a match length in 1..25")
+        for name in ("cube", "luck", "bearoff", "bearoff1", "truncate", "cube_bearoff", "cube_truncate", "cube_luck"):
+            if getattr(ns, name) not in (None, False):
+                self.error(f"--match and --{name.replace('_', '-')} cannot be combined")
+        if ns.match_score is None:
+            self.error("--match needs --match-score A1,A2")
+        if ns.net == "random" and ns.match_net is None and any(getattr(ns, o) is not None for o in rule_opts):
+            self.error("--match-window, --match-gammons, --match-lookahead and --match-scale need --net with weights or "
+                       "--match-net (without either nobody doubles)")
+        for name, default in MATCH_DEFAULTS.items():
+            if getattr(ns, name) is None:
+                setattr(ns, name, default)
+        if math.isnan(ns.match_scale):
+            self.error("--match-scale is NaN")
+        if not 0.0 <= ns.match_window <= 1.0:
+            self.error("--match-window takes a number in [0, 1]")
+        from .match import validate_score
+        try:
+            validate_score(ns.match, ns.match_score, ns.match_crawford)
+        except ValueError as e:
+            self.error(str(e))
+        k, owner = ns.match_cube
+        if not 0 <= k <= 10 or owner not in (0, 1, 2) or (owner == 0) != (k == 0):
+            self.error("--match-cube takes K,OWNER with K in 0..10, OWNER 0 (centred, K = 0), 1 or 2")
+
+
+MATCH_DEFAULTS = {"match_crawford": 0, "match_cube": (0, 0), "match_window": 0.65, "match_gammons": (0.25, 0.25),
+                  "match_lookahead": 1, "match_scale": 1.0}
+
+
+def _int_pair(option: str):
+    def parse(text: str):
+        try:
+            a, b = (int(v) for v in text.split(","))
+        except ValueError:
+            raise argparse.ArgumentTypeError(f"{option} takes two whole numbers A,B, got {text!r}")
+        return a, b
+    return parse
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -1079,7 +1257,56 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cube-decision", action="store_true",
                     help="per position: no double / double, take / double, pass for the side on roll with a "
                          "centred cube, and the verdict")
+    from .arena import _gammon_shares
+    ap.add_argument("--match", type=int, default=None, metavar="N",
+                    help="roll the positions out at a score of a match to N points (1..25): the result is the mover's "
+                         "match-winning chance on a match equity table; needs --match-score; not with --cube, --luck, "
+                         "a bearoff cut or --truncate")
+    ap.add_argument("--match-score", type=_int_pair("--match-score"), default=None, metavar="A1,A2",
+                    help="the points PLAYER1 and PLAYER2 still need, each in 1..N")
+    ap.add_argument("--match-crawford", type=int, default=None, choices=(0, 1, 2),
+                    help="0 before the Crawford game (default), 1 the Crawford game, 2 after it")
+    ap.add_argument("--met", default=None, metavar="FILE",
+                    help="the match equity table, JSON {length, met, post_crawford} (match.load_met; its length must "
+                         "be N; default: match.met_table(N), a cubeless-play table)")
+    ap.add_argument("--match-window", type=float, default=None,
+                    help="the side on roll doubles from this share of the way between the dead-cube doubling point (0) "
+                         "and the cash point (1) on (default 0.65)")
+    ap.add_argument("--match-gammons", type=_gammon_shares, default=None, metavar="W,L",
+                    help="the share of the side on roll's wins and of its losses that are gammons (default 0.25,0.25)")
+    ap.add_argument("--match-lookahead", type=int, default=None, choices=(0, 1),
+                    help="0: the value head on the position itself (sync-free); 1 (default): its mean best 1-ply value "
+                         "over the 21 rolls")
+    ap.add_argument("--match-net", default=None, metavar="PATH",
+                    help="the state_dict whose value head makes the cube decisions (default: the player's net)")
+    ap.add_argument("--match-scale", type=float, default=None, help="points per unit of the net's value (default 1)")
+    ap.add_argument("--match-cube", type=_int_pair("--match-cube"), default=None, metavar="K,OWNER",
+                    help="the cube every game starts with: 2^K, OWNER 0 centred, 1 PLAYER1, 2 PLAYER2 (default 0,0)")
+    ap.add_argument("--match-decision", action="store_true",
+                    help="per position: no double / double, take / double, pass for the side on roll in "
+                         "match-winning chance, and the verdict")
     return ap
+
+
+def match_from_args(args, net, device):
+    """The match.RolloutMatch of a parsed command line (None without --match): a MatchRule on
+    --match-net, else on the player's net; without either no rule (nobody doubles)."""
+    if args.match is None:
+        return None
+    from .match import MatchRule, RolloutMatch, load_met
+    from .search import ValueHead
+    met = None
+    if args.met is not None:
+        length, *met = load_met(args.met)
+        if length != args.match:
+            raise ValueError(f"--met {args.met} is a table for matches to {length}, --match asks for {args.match}")
+    vnet = net if args.match_net is None else load_net(args.match_net, device)
+    rule = None
+    if vnet is not None:
+        w, l = args.match_gammons
+        rule = MatchRule(ValueHead(vnet), scale=args.match_scale, window=args.match_window, win_gammons=w,
+                         loss_gammons=l, lookahead=args.match_lookahead)
+    return RolloutMatch(args.match, rule, met=met)
 
 
 def main(argv=None):
@@ -1151,7 +1378,23 @@ def main(argv=None):
                          life=CubeLife(args.cube_luck_life, args.cube_luck_win_value, args.cube_luck_loss_value))
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
-    if args.cube_decision:
+    match = match_from_args(args, net, dev)
+    if match is not None:
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+    if args.match_decision:
+        from .match import rollout_match_decision
+        res = []
+        for i in range(positions.shape[0]):
+            d = rollout_match_decision(ro, player, positions[i], args.trials, match, args.match_score,
+                                       crawford=args.match_crawford, cube=args.match_cube, first_roll=args.first_roll,
+                                       max_steps=args.max_steps)
+            print(json.dumps(dict(position=i, match_decision=True, **d)), flush=True)
+            res.extend(d["rollouts"])
+    elif match is not None:
+        res = ro.run(player, positions, args.trials, first_roll=args.first_roll, max_steps=args.max_steps, match=match,
+                     match_away=args.match_score, match_crawford=args.match_crawford, cube_start=args.match_cube)
+    elif args.cube_decision:
         # one line per position: the three equities and the verdict; the summary counts both rollouts' games
         res = []
         for i in range(positions.shape[0]):
@@ -1166,7 +1409,7 @@ def main(argv=None):
                      truncate=trunc, cube_bearoff=cdb, cube_truncate=ctrunc, cube_luck=cluck,
                      cube_luck_scale=args.cube_luck_scale)
     dt = time.perf_counter() - t0
-    for i, r in enumerate(res if not args.cube_decision else ()):
+    for i, r in enumerate(res if not (args.cube_decision or args.match_decision) else ()):
         print(json.dumps(dict(position=i, **r)), flush=True)
     games = sum(r["games"] for r in res)
     summary = dict(summary=True, positions=int(positions.shape[0]), games=games, unfinished=sum(r["unfinished"] for r in res),
@@ -1211,6 +1454,13 @@ def main(argv=None):
         summary.update(cube_luck=True, cube_luck_net=args.cube_luck_net, cube_luck_scale=args.cube_luck_scale,
                        cube_luck_life=args.cube_luck_life, cube_luck_win_value=args.cube_luck_win_value,
                        cube_luck_loss_value=args.cube_luck_loss_value, cube_luck_value_scale=args.cube_luck_value_scale)
+    if match is not None:
+        summary.update(match=args.match, match_score=list(args.match_score), match_crawford=args.match_crawford,
+                       met=args.met, match_cube=list(args.match_cube), match_decision=args.match_decision,
+                       match_rule=match.has_rule, match_net=args.match_net, match_window=args.match_window,
+                       match_gammons=list(args.match_gammons), match_lookahead=args.match_lookahead,
+                       match_scale=args.match_scale,
+                       pass_share=sum(r["pass_games"] for r in res) / games if games else 0.0)
     print(json.dumps(summary), flush=True)
     return res, summary
 

@@ -312,3 +312,6 @@ extern "C" int bgx_normalize_adv(float* adv, int64_t n, const double* sums, floa
 
 // match play in the arena: bg_arena_cube.h's seat rule and take, bg_cube_trunc.h's ct_ arithmetic
 #include "bg_match.h"
+
+// match-score rollouts: bg_match.h's rule fused into one decision, bg_cube.h's bytes, the helpers
+#include "bg_match_rollout.h"
